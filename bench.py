@@ -285,6 +285,66 @@ def one_launch_hint(scene):
 
 CONFIG_FLAGS = {"headline_nocull": {"useBackfaceCulling": 0}, "cfg2_nocull": {"useBackfaceCulling": 0}}
 
+def scene_with_assets(scene_path, assets):
+    """Makes the generated assets (rendering_amd/assets.py) that scene_path names and returns the scene file to load.  An asset missing from
+    scenes/assets/ is written there when that directory can be written; otherwise (a tree the benchmarking user may not write to) it is
+    generated into a private temporary directory, removed at exit, and a copy of the scene file beside it names it by absolute path.  The
+    generators are deterministic, so the scene is the same either way."""
+    import atexit
+    import re
+    import shutil
+    text = open(scene_path).read()
+    names = sorted(set(re.findall(r"scenes/assets/([\w.]+)", text)) & set(assets._GENERATORS))
+    own = {}
+    for n in names:
+        if os.path.exists(os.path.join(assets.ASSETS, n)):
+            continue
+        try:
+            assets.ensure([n])
+        except OSError:
+            own[n] = None
+    if not own:
+        return scene_path
+    tmp = tempfile.mkdtemp(prefix="bench_assets_")
+    atexit.register(shutil.rmtree, tmp, True)
+    for n in own:
+        own[n] = os.path.join(tmp, n)
+        with open(own[n], "wb") as f:
+            f.write(assets._GENERATORS[n]())
+    copy = os.path.join(tmp, os.path.basename(scene_path))
+    with open(copy, "w") as f:
+        f.write(re.sub(r"scenes/assets/([\w.]+)", lambda m: own.get(m.group(1), m.group(0)), text))
+    return copy
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+DUMP_SAMPLE_PIXELS = 1 << 20
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes what the timed path returned in its last step, {name: (H, W, ...) device tensor}, as out_dir/<name>.npy in float32.
+    When the whole arrays exceed DUMP_BUDGET_BYTES, the same fixed, seeded sample of DUMP_SAMPLE_PIXELS pixels is taken from every one of them
+    (sorted row-major pixel indices, written as pixel_index.npy in float64).  Returns the description that goes into the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = next(iter(arrays.values())).shape[:2]
+    whole = sum(a.numel() for a in arrays.values()) * 4
+    idx = None
+    if whole > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=min(DUMP_SAMPLE_PIXELS, H * W), replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+        idx_t = torch.from_numpy(idx).to(next(iter(arrays.values())).device)
+    files = {}
+    for name, a in arrays.items():
+        if idx is not None:
+            a = a.reshape(H * W, -1).index_select(0, idx_t).reshape((idx.size,) + tuple(a.shape[2:]))
+        v = a.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        files[name] = list(v.shape)
+    if idx is not None:
+        files["pixel_index"] = [int(idx.size)]
+    return {"dir": out_dir, "files": files, "sampled_pixels": None if idx is None else int(idx.size), "seed": None if idx is None else DUMP_SEED}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -306,7 +366,12 @@ def main():
                          "framebuffers) -> config.pipelined_ms_per_frame; never `value` (off by default: its overlapping launches would enter a profiler's per-kernel averages)")
     ap.add_argument("--serial-gather", action="store_true",
                     help="N > 1: rtx_gather on the render stream, frame by frame (default: on a second stream, overlapping the next frame)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): N = 1 the framebuffer and the SSAA mask, "
+                         "N > 1 rank 0's gathered BGR8 image; larger than 64 MB in all -> the same seeded sample of pixels from each (DIR/pixel_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cscene, cw, ch = CONFIGS[args.config]
     custom = bool(args.scene or args.width or args.height or args.no_ssaa)
     args.scene = args.scene or cscene
@@ -338,11 +403,8 @@ def main():
 
     from rendering_amd import assets, parallel
     import rendering_amd as RA
-    if rank == 0:
-        # the generated assets the scene names (the two 250k-triangle meshes are made on demand only), plus the small default set
-        wanted = [os.path.basename(l.split("=", 1)[1].strip()) for l in open(args.scene) if l.startswith("name=scenes/assets/")]
-        assets.ensure()
-        assets.ensure([n for n in wanted if n in assets._GENERATORS])
+    # the generated assets the scene names (the two 250k-triangle meshes are made on demand only)
+    args.scene = scene_with_assets(args.scene, assets)
     if world > 1:
         dist.barrier()
     W, H = args.width, args.height
@@ -485,6 +547,13 @@ def main():
         frame_status = scene.frame_status()
         if frame_status != 0:
             raise SystemExit("bench.py: rtx_frame_status = 0x%x -- a timed frame's single launch gave up; the timing is void" % frame_status)
+    # what the last timed step handed its caller, before anything below renders into the same buffers again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if world > 1:
+            dumped = dump_outputs(args.dump_outputs, {"image": img})
+        else:
+            dumped = dump_outputs(args.dump_outputs, {"framebuffer": fb, "ssaa_mask": mask} if ssaa else {"framebuffer": fb})
 
     # N > 1: what the timed region measured is THROUGHPUT when the exchange of frame k runs beside the rendering of frame k + 1 (the default); the LATENCY of one
     # frame -- render this rank's rows, quantise, gather on the render stream, wait -- is measured here, frame by frame (max over the ranks)
@@ -728,6 +797,8 @@ def main():
     }
     if verified is not None:
         out["config"]["gathered_image_equals_single_gpu_image"] = verified
+    if dumped is not None:
+        out["config"]["dumped_outputs"] = dumped
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.scene, W, H, scene, flags=flags)
         par = (out["cpu_baseline"] or {}).get("parity")

@@ -53,7 +53,9 @@ def test_north_star_4096_sharding_equals_whole_frame(ra, torch_cuda):
 
 def test_north_star_4096_oracle_bands(ra, oracle, torch_cuda):
     """Same frame against the CPU oracle on 8-row bands through the silhouette, the poles and the floor."""
+    from rendering_amd import assets
     torch = torch_cuda
+    assets.ensure(["bumpy_250k.obj"])
     g = ra.Scene("scenes/cfg2_smooth_250k.scene", 4096, 4096)
     fb, _ = render(torch, g, ssaa=False)
     got = fb.cpu().numpy()

@@ -62,6 +62,8 @@ def test_views_of_a_sequence_equal_fresh_scenes_and_the_oracle(ra, oracle, tmp_p
 def test_set_view_does_not_wait_for_the_device(ra):
     """The host time of a new view must not include the frames still queued on the device."""
     import time
+    from rendering_amd import assets
+    assets.ensure(["bumpy_250k.obj"])
     w = h = 2048
     g = ra.Scene("scenes/cfg2_smooth_250k.scene", w, h)
     fb = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
