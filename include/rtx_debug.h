@@ -18,7 +18,7 @@ int rtx_set_frame_mode(rtx_scene* scene, int mode); /* -1 measure and choose (de
  * {qc[3], wlo, qr[3], whi}; rtx_device.h, DESIGN_HISTORY.md 3.1c), plus the record of the whole mesh.  For the CPU tests of their
  * invariants (tests/test_host_cpu.py); cap_wide = records the output arrays hold. */
 int rtx_mesh_flatten_probe(const rtx_mesh* mesh, uint32_t* n_wide, void* wide_out, void* prune_out, uint32_t cap_wide, float* root_rec8);
-int rtx_wide_node_slots(void);      /* slots of a wide node in this build: 4 or 8 */
+int rtx_wide_node_slots(void);      /* slots of a wide node: 8 */
 
 /* Host only: the P of the source copies of the prune records (rtx_device.h PruneRec, csrc/rtx_source.hip sourceP; DESIGN_HISTORY.md 3.1d)
  * for n triangles given as (v0, e1, e2) = 9 floats each, the source point S3, its radius sigma and cam != 0 when the rays start

@@ -18,25 +18,22 @@ struct Node {
 };
 static_assert(sizeof(Node) == 32, "node must be one s_load_dwordx8");
 
-// Four slots = the grandchildren of a binary node (a child that is a leaf takes one slot itself), left to right, in the
-// layout of four Node records.  link > 0: inner node, link - 1 = index of its own WideNode; link < 0: leaf with ~link
-// references from `first`; link == 0: empty slot.  One WideNode = two s_load_dwordx16: one dependent fetch per TWO levels
-// of the reference's tree.  Skipping the boxes of the levels in between is exact: every box lies inside its parent's, and
+// Eight slots = the descendants of a binary node three levels down (a leaf on the way takes one slot itself), left to right, in the
+// layout of eight Node records.  link > 0: inner node, link - 1 = index of its own WideNode; link < 0: leaf with ~link
+// references from `first`; link == 0: empty slot.  One WideNode = four s_load_dwordx16 (the slots are fetched four at a time): one
+// dependent fetch per THREE levels of the reference's tree.  Skipping the boxes of the levels in between is exact: every box lies inside its parent's, and
 // for nested boxes the slab products are monotone in the bounds, so a ray that passes a box passes every box around it --
 // a ray reaches a leaf (objects.cpp:587-631) iff it passes the leaf's OWN box (no NaN: see meshWalk).
-// RTX_WIDE_LEVELS binary levels per wide node: 2 (four slots, rounds 2-4) or 3 (eight slots: the descendants three levels down -- the walk is a chain
-// of dependent fetches, one per wide level, and a third fewer levels is a third fewer visits; the slots are fetched four at a time).
-#ifndef RTX_WIDE_LEVELS
-#define RTX_WIDE_LEVELS 3
-#endif
-constexpr int kWideLevels = RTX_WIDE_LEVELS;
+// Three binary levels per wide node (the first rounds had two: four slots, DESIGN_HISTORY.md): the walk is a chain of dependent fetches, one per wide level, and a third fewer
+// levels is a third fewer visits.  The kernels are written for eight slots (pruneEval8: 16 records x 4 lanes; the walk's slot masks).
+constexpr int kWideLevels = 3;
 constexpr int kWideSlots = 1 << kWideLevels;
 // entries of the walk's per-wave stack in LDS (meshWalk): at most kWideSlots - 1 per wide level + 1 -- rtx_scene_create checks a mesh's depth against it
 // (a deeper tree is walked in the binary form).  Five blocks per CU hold 31 744 B of LDS each (the allocation granule): 72 entries x 16 B x 4 waves fit
 // beside 25 parked fields and the six axis records of pruneEval8 (rtx_kernels.hip, pruneUni).
-constexpr int kWideStackEntries = kWideSlots == 4 ? 56 : (kWideSlots == 8 ? 72 : 124);      // (72: ten wide levels = thirty binary ones need 71; 256 bytes of LDS went to pruneUni's axis records)
+constexpr int kWideStackEntries = 72;      // (ten wide levels = thirty binary ones need 71; 256 bytes of LDS went to pruneUni's axis records)
 struct WideNode { Node slot[kWideSlots]; };
-static_assert(sizeof(WideNode) == 32 * kWideSlots && (kWideSlots == 4 || kWideSlots == 8 || kWideSlots == 16), "wide node = two s_load_dwordx16 per four slots");
+static_assert(kWideSlots == 8 && sizeof(WideNode) == 32 * kWideSlots, "wide node = eight slots, two s_load_dwordx16 per four");
 
 // Leaf references, duplicated per leaf in the reference's DFS-left-first order (objects.cpp:622-629): reference r of the
 // mesh (r = Node::first + position in the leaf) is one entry of three parallel arrays, so that LANE i of a wave reads
@@ -81,8 +78,8 @@ constexpr float kSrcAinfMax = 32.0f;         // the source certificate assumes |
 // the box (interval arithmetic): det / (s1 s2) = dir . q,  Nt / (s1 s2) = v0 . q - orig . q.   No usable bound: q = 0 +- 0, [wlo, whi] = [-inf, +inf] (never rejected).
 struct PlaneRec { float qc[3]; float wlo; float qr[3]; float whi; };
 static_assert(sizeof(PlaneRec) == 32, "plane record = two dwordx4");
-// per wide node: PruneRec[kWideSlots] then PlaneRec[kWideSlots] (slot order) = 64 bytes per slot.  Eight slots: lane 4 r + a of a wave reads words a and 4 + a of
-// record r (r < 8 boxes, r >= 8 planes; a = 3: the records' fourth words) -- rtx_kernels.hip, pruneEval8; other widths: lane k of the first 2 kWideSlots lanes reads record k
+// per wide node: PruneRec[kWideSlots] then PlaneRec[kWideSlots] (slot order) = 64 bytes per slot.  Lane 4 r + a of a wave reads words a and 4 + a of
+// record r (r < 8 boxes, r >= 8 planes; a = 3: the records' fourth words) -- rtx_kernels.hip, pruneEval8
 struct PruneBlock { PruneRec box[kWideSlots]; PlaneRec plane[kWideSlots]; };
 static_assert(sizeof(PruneBlock) == 64 * kWideSlots, "prune block");
 

@@ -8,7 +8,7 @@
 //     (meshWalk): the reference's tree three levels per fetch (rtxd::WideNode: eight slots, scalar loads, a wave-level stack
 //     in LDS), every lane testing the slot boxes on its own ray with the reference's arithmetic; slots whose triangles no ray
 //     of the bundle can hit are dropped beforehand (rtxd::PruneBlock; pruneEval8: the lanes acting as (record, axis) pairs --
-//     the inequalities are those of pruneAlive / planeAlive, which remain for the other node widths);
+//     the inequalities are stated with it as pruneAlive / planeAlive);
 //   * the references of the reached leaves are streamed 64 at a time with the lanes acting as TRIANGLES: the bundle
 //     filter (bundleRejects1/2) keeps what some ray might hit, the survivors are tested exactly (the reference's
 //     Moller-Trumbore, operation by operation) with the lanes acting as rays again, in the reference's order --
@@ -137,7 +137,6 @@ __device__ __forceinline__ float length(V3 a) { return __builtin_sqrtf(len2(a));
 __device__ __forceinline__ float invLenSlow(float l2) { return (float)(1.0 / __builtin_sqrt((double)l2)); }
 __device__ __forceinline__ float invLenD(float l2)
 {
-#if RTX_FAST_INVLEN
 	const float y0 = __builtin_amdgcn_rsqf(l2);
 	const float t = l2 * y0, te = __builtin_fmaf(l2, y0, -t);
 	float e = __builtin_fmaf(-t, y0, 1.0f); e = __builtin_fmaf(-te, y0, e);
@@ -149,9 +148,6 @@ __device__ __forceinline__ float invLenD(float l2)
 	float r = y1;
 	if (!sure) r = invLenSlow(l2);
 	return r;
-#else
-	return invLenSlow(l2);
-#endif
 }
 __device__ __forceinline__ V3 normalized(V3 a)
 {
@@ -455,13 +451,9 @@ __device__ __forceinline__ Bundle makeBundle(bool active, const V3& o, const V3&
 	const float ninf = -__builtin_inff();
 	Bundle B;
 	float lo, hi;
-	// (RTX_BUNDLE_PAIRS: max and min of a coordinate as one pair of interleaved DPP chains, waveMaxMin -- rtx_tuning.h)
-#if RTX_BUNDLE_PAIRS
+	// (max and min of a coordinate as one pair of interleaved DPP chains, waveMaxMin: profiles/r05_ab_*.txt)
 #define RTX_RANGE(x, c, r) hi = active ? (x) : ninf; lo = active ? (x) : -ninf; waveMaxMin(hi, lo); centreRadius(lo, hi, c, r)
-#else
-#define RTX_RANGE(x, c, r) hi = waveMax(active ? (x) : ninf); lo = -waveMax(active ? -(x) : ninf); centreRadius(lo, hi, c, r)
-#endif
-	if (RTX_SAME_ORIGIN && sameOrigin) {
+	if (sameOrigin) {
 		const int first = __builtin_ctzll(ballot(active) | (1ull << 63));
 		B.ocx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.x), first)); B.ocy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.y), first));
 		B.ocz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.z), first));
@@ -506,17 +498,12 @@ __device__ __forceinline__ Bundle makeBundle(bool active, const V3& o, const V3&
 // Magnitudes outside the assumed range (or NaN) make the compares false: nothing is rejected.
 // Evaluated in two stages so that a wave whose 64 references all fail the cheap first stage (orientation and t range:
 // the back of the mesh, everything behind a shadow ray's origin) skips the second (u, v).
-// RTX_FILTER_MASKS: the verdicts as wave masks -- every compare feeds a ballot directly (a v_cmp into an SGPR pair) and the masks are combined on the scalar side.
-// As bools, `ballot(valid && !rej1)` of values that went through the `||` chains' control flow compiled to v_cndmask + v_cmp per ballot.
-#if RTX_FILTER_MASKS
-typedef uint64_t FilterVerdict;
-#else
-typedef bool FilterVerdict;
-#endif
-struct FilterState { float kda, detHi1, sg; FilterVerdict ok; };      // (kept small: it is live across the ballot between the stages)
+// The verdicts are wave masks: every compare feeds a ballot directly (a v_cmp into an SGPR pair) and the masks are combined on the scalar side.
+// (As bools, `ballot(valid && !rej1)` of values that went through the `||` chains' control flow compiled to v_cndmask + v_cmp per ballot: DESIGN.md 3.1.)
+struct FilterState { float kda, detHi1, sg; uint64_t ok; };      // (kept small: it is live across the ballot between the stages)
 
 template <bool CULL>
-__device__ __forceinline__ FilterVerdict bundleRejects1(const Bundle& B, float tmaxB, const RefA& ra, const RefB& rb, const RefC& rc, FilterState& f)
+__device__ __forceinline__ uint64_t bundleRejects1(const Bundle& B, float tmaxB, const RefA& ra, const RefB& rb, const RefC& rc, FilterState& f)
 {
 	const float e1x = rb.e1x, e1y = rb.e1y, e1z = rb.e1z, e2x = rb.e2x, e2y = rc.e2y, e2z = rc.e2z;
 	const float ax = B.ocx - ra.v0x, ay = B.ocy - ra.v0y, az = B.ocz - ra.v0z;
@@ -525,53 +512,34 @@ __device__ __forceinline__ FilterVerdict bundleRejects1(const Bundle& B, float t
 	const float s1 = fabsf(e1x) + fabsf(e1y) + fabsf(e1z), s2 = fabsf(e2x) + fabsf(e2y) + fabsf(e2z);
 	const float s12 = s1 * s2;
 	const float ainf = (fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)) + B.roMax) * (1.0f + 0x1p-20f);
-#if !RTX_FILTER_MASKS
-	const bool tame = s1 < 0x1p20f && s2 < 0x1p20f && ainf < 0x1p41f;
-#endif
 	// det over the bundle
 	float detc = __builtin_fmaf(B.dcz, mz, __builtin_fmaf(B.dcy, my, B.dcx * mx));
 	const float detr = __builtin_fmaf(B.rdz, fabsf(mz), __builtin_fmaf(B.rdy, fabsf(my), B.rdx * fabsf(mx)));
 	const float Ed = __builtin_fmaf(B.kd, s12, kFilterEta);
 	float sg = 1.0f;
-#if RTX_FILTER_MASKS
 	uint64_t usable = ~0ull;
-#else
-	bool usable = true;
-#endif
 	if (!CULL) {
 		// culling off: the tests need the sign of det_c; both signs are handled by mirroring, an uncertain sign by not testing
 		const bool neg = detc + detr + Ed < 0;
-#if RTX_FILTER_MASKS
 		usable = ballot(neg) | ballot(detc - detr - Ed > 0);
-#else
-		usable = neg || detc - detr - Ed > 0;
-#endif
 		sg = neg ? -1.0f : 1.0f;
 		detc *= sg;
 	}
 	const float detHi = detc + detr + Ed;
-#if RTX_FILTER_MASKS
 	f.ok = B.sane ? usable & ballot(s1 < 0x1p20f) & ballot(s2 < 0x1p20f) & ballot(ainf < 0x1p41f) : 0ull;
 	const uint64_t rejO = CULL ? ballot(detHi < 0) & f.ok : 0ull;
 	// (an exit here for passes whose open references all face away -- before the t range -- measured neutral: profiles/r06_ab_control_flow.txt)
-#endif
 	// t: Nt = -(a . m), radius from the origin box
 	const float ntc = -sg * __builtin_fmaf(az, mz, __builtin_fmaf(ay, my, ax * mx));
 	const float ntr = __builtin_fmaf(B.roz, fabsf(mz), __builtin_fmaf(B.roy, fabsf(my), B.rox * fabsf(mx)));
 	const float Et = __builtin_fmaf(kFilterK * ainf, s12, kFilterEta);
 	const float detHi1 = detHi * (1.0f + 0x1p-18f);
 	f.kda = B.kd * ainf; f.detHi1 = detHi1; f.sg = sg;
-#if RTX_FILTER_MASKS
 	return rejO | ((ballot(ntc + ntr < -Et) | ballot(ntc - ntr - Et >= tmaxB * detHi1)) & f.ok);
-#else
-	const bool rej = (CULL && detHi < 0) || ntc + ntr < -Et || ntc - ntr - Et >= tmaxB * detHi1;
-	f.ok = usable && tame && B.sane;
-	return rej && f.ok;
-#endif
 }
 
 template <bool CULL>
-__device__ __forceinline__ FilterVerdict bundleRejects2(const Bundle& B, const RefA& ra, const RefB& rb, const RefC& rc, const FilterState& f, FilterVerdict open = FilterVerdict(0))      // open: the lanes still undecided (mask form)
+__device__ __forceinline__ uint64_t bundleRejects2(const Bundle& B, const RefA& ra, const RefB& rb, const RefC& rc, const FilterState& f, uint64_t open)      // open: the lanes still undecided
 {
 	const float e1x = rb.e1x, e1y = rb.e1y, e1z = rb.e1z, e2x = rb.e2x, e2y = rc.e2y, e2z = rc.e2z;
 	const float ax = B.ocx - ra.v0x, ay = B.ocy - ra.v0y, az = B.ocz - ra.v0z;      // (recomputed: cheaper than three live registers)
@@ -590,10 +558,8 @@ __device__ __forceinline__ FilterVerdict bundleRejects2(const Bundle& B, const R
 	const float Eu = __builtin_fmaf(f.kda, s2, kFilterEta);
 	if (!CULL) nuc *= f.sg;
 	const float nuLo = nuc - nur - Eu;
-#if RTX_FILTER_MASKS
 	const uint64_t rejU = (ballot(nuc + nur < -Eu) | ballot(nuLo > f.detHi1)) & f.ok;
 	if ((open & ~rejU) == 0) return rejU;      // (u decides every open lane: the wave skips v)
-#endif
 	// v: Nv = d . (a x e1)
 	const float wvx = __builtin_fmaf(ay, e1z, -(az * e1y)), wvy = __builtin_fmaf(az, e1x, -(ax * e1z)), wvz = __builtin_fmaf(ax, e1y, -(ay * e1x));
 	float nvc = __builtin_fmaf(B.dcz, wvz, __builtin_fmaf(B.dcy, wvy, B.dcx * wvx));
@@ -603,12 +569,7 @@ __device__ __forceinline__ FilterVerdict bundleRejects2(const Bundle& B, const R
 	const float nvr = (nvrO + __builtin_fmaf(B.rdz, fabsf(wvz), __builtin_fmaf(B.rdy, fabsf(wvy), B.rdx * fabsf(wvx)))) * (1.0f + 0x1p-19f);
 	const float Ev = __builtin_fmaf(f.kda, s1, kFilterEta);
 	if (!CULL) nvc *= f.sg;
-#if RTX_FILTER_MASKS
 	return rejU | ((ballot(nvc + nvr < -Ev) | ballot(nuLo + (nvc - nvr - Ev) > f.detHi1)) & f.ok);
-#else
-	const bool rej = nuc + nur < -Eu || nuLo > f.detHi1 || nvc + nvr < -Ev || nuLo + (nvc - nvr - Ev) > f.detHi1;
-	return rej && f.ok;
-#endif
 }
 
 // The reference's test (objects.cpp:59-95) of the rays in exec against ONE triangle whose record is wave-uniform (read
@@ -688,21 +649,12 @@ __shared__ LeafEntry leafBatch[4][RTX_LEAF_BATCH_MAX];      // per wave of a 256
 // link - 1; link < 0: leaf with ~link references from `first`; mask = the rays that passed the item's own box.
 struct WideItem { int32_t link; uint32_t first, maskLo, maskHi; };
 __shared__ WideItem wideStack[4][kWideStackEntries];      // (kWideSlots - 1 entries per wide level + 4: rtx_scene_create checks the depth)
-// WIDE walk with prune records (rtxd::PruneRec): what the slot test needs from the wave's bundle, per wave, written once per
-// walk: [0..5] the range of 1 / dir over the rays per axis (lo, hi; mirrored so that it is positive), [6..11] the range of
-// the origins per axis in the same mirrored coordinates (lo, hi), [12] 216 dmax, [13] the largest |origin| coordinate,
-// [14] bits 0-2: axis mirrored, bits 3-5: axis usable (1 / dir of one sign over the wave).
-#if RTX_PRUNE_AXIS
-// RTX_PRUNE_AXIS: the same quantities laid out for pruneEval8 -- six records of eight floats per wave, one per (test, axis):
+// WIDE walk with prune records (rtxd::PruneRec): what pruneEval8's slot tests need from the wave's bundle, written once per walk -- six records of
+// eight floats per wave, one per (test, axis):
 // [0..2] box test, axis x / y / z: { 1 / dir lo, hi (mirrored: positive), origin lo, hi (mirrored), the sign bit that mirrors a record's centre, +inf (axis usable) / -inf,
 //                                    216 dmax, the largest |origin| coordinate };
 // [3..5] plane test, axis x / y / z: { dc, rd, oc, ro (the bundle's direction / origin boxes as centre, radius), 2 K dmax, K (|orig| + |vertex|), -, - }
 __shared__ float pruneUni[4][48];
-#else
-__shared__ float pruneUni[4][24];      // ([16..18] the sign bits that mirror a record's centre, [19..21] per axis +inf (usable) / -inf (not))
-#endif
-// the prune records of the root's slots are evaluated too: +-0 with four slots (two levels down: as good as never pruned), -1.6 % with eight
-constexpr bool kPruneRoot = kWideLevels >= 3;
 // 36 u / 1e-8 (u = 2^-24) = 214.6: see pruneSlots
 constexpr float kPruneC = 216.0f;
 // the reference's box test in its min / max form (exact when no NaN can arise, see meshWalk) against a box in SGPRs
@@ -718,9 +670,9 @@ __device__ __forceinline__ bool boxFailsRegular(float blox, float bhix, float bl
 	asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(fx), "v"(fy), "v"(fz));
 	return tn > tf;
 }
-// Can the subtree of a wide-node slot contribute to this walk?  r0 / r1 = the slot's rtxd::PruneRec (true box T of its
-// triangles as centre c / half-extent h, P = max |e1|_1 |e2|_1), pu = the wave's pruneUni block, tmaxB = the largest limit
-// of any open ray.  Returns false only when NO ray of the bundle can have a hit accepted by the reference
+// pruneAlive, the box test of a wide-node slot (evaluated by pruneEval8): can the slot's subtree contribute to this walk?  The slot's rtxd::PruneRec holds the
+// true box T of its triangles as centre c / half-extent h and P = max |e1|_1 |e2|_1; tmaxB = the largest limit of any open ray.  The slot is dropped only
+// when NO ray of the bundle can have a hit accepted by the reference
 // (objects.cpp:59-95) in that subtree with t below its limit:
 //   An accepted hit has det_c >= 1e-8, 0 <= u_c <= 1, 0 <= v_c, u_c + v_c <= 1 (+ one rounding), 0 <= t_c < limit.  With the
 //   identity  det (orig - v0) = -Nt dir + Nu e1 + Nv e2  (Cramer; exact for the fp32 inputs) and the reference's rounding
@@ -735,40 +687,9 @@ __device__ __forceinline__ bool boxFailsRegular(float blox, float bhix, float bl
 // scale for the roundings of this test itself; entry / exit of the inflated box over ALL origins and 1 / dir of the bundle
 // (interval arithmetic, endpoints only: every product is monotone in each factor); alive unless the exit is certainly
 // before the entry, behind the origin, or the entry certainly beyond tmaxB.  NaN compares false -> alive.
-__device__ __forceinline__ bool pruneAlive(const f4v& r0, const f4v& r1, const float* pu, float tmaxB)
-{
-	const f4v ua = *(const f4v*)(pu + 0), ub = *(const f4v*)(pu + 4), uc = *(const f4v*)(pu + 8), ue = *(const f4v*)(pu + 12);
-	// The walk's mirror and usability flags as operands instead of tests: the centre is mirrored by an XOR with the axis' sign bit, and an axis that is
-	// not usable (1 / dir changes sign over the bundle) drops out through one more operand of the min / max: cap = -inf gives entry -inf, exit +inf --
-	// whatever the products are, NaN included (v_min / v_max return the other operand); on a usable axis cap = +inf changes nothing (the products of
-	// finite records with finite reciprocals are never NaN).  18 VALU instructions fewer per evaluation than the flag tests.
-	const f4v uf = *(const f4v*)(pu + 16), ug = *(const f4v*)(pu + 20);
-	const float cx = __uint_as_float(__float_as_uint(r0.x) ^ __float_as_uint(uf.x)), cy = __uint_as_float(__float_as_uint(r0.y) ^ __float_as_uint(uf.y));
-	const float cz = __uint_as_float(__float_as_uint(r0.z) ^ __float_as_uint(uf.z));
-	const float capX = uf.w, capY = ug.x, capZ = ug.y;
-	// largest |orig - vertex| coordinate over the bundle and the box
-	const float ainf = fmaxf(fmaxf(fmaxf(cx - ub.z, ub.w - cx) + r1.x, fmaxf(cy - uc.x, uc.y - cy) + r1.y), fmaxf(cz - uc.z, uc.w - cz) + r1.z);
-	// P of the walk's source copy (rtxd::PruneRec: the camera's, a point light's) holds for origins within kSrcAinfMax of the box;
-	// beyond, and in copy 0 (r0.w == r1.w), the unconditional Pgen
-	const float Pn = ainf <= kSrcAinfMax ? r0.w : r1.w;
-	const float rho = __builtin_fmaf(ue.x * ainf, Pn, 0x1p-17f * (ainf + ue.y)) * (1.0f + 0x1p-20f) + 1e-30f;
-	const float hx = r1.x + rho, hy = r1.y + rho, hz = r1.z + rho;
-	const float inf = __builtin_inff();
-	// per axis (mirrored so that 1 / dir > 0): entry >= (lo' - o_hi) inv, exit <= (hi' - o_lo) inv over the ranges
-	const float ax = (cx - hx) - ub.w, bx = (cx + hx) - ub.z;
-	const float ay = (cy - hy) - uc.y, by = (cy + hy) - uc.x;
-	const float az = (cz - hz) - uc.w, bz = (cz + hz) - uc.z;
-	(void)inf;
-	const float ex = fminf(fminf(ax * ua.x, ax * ua.y), capX), fx = fmaxf(fmaxf(bx * ua.x, bx * ua.y), -capX);
-	const float ey = fminf(fminf(ay * ua.z, ay * ua.w), capY), fy = fmaxf(fmaxf(by * ua.z, by * ua.w), -capY);
-	const float ez = fminf(fminf(az * ub.x, az * ub.y), capZ), fz = fmaxf(fmaxf(bz * ub.x, bz * ub.y), -capZ);
-	const float ent = fmaxf(fmaxf(ex, ey), ez), ext = fminf(fminf(fx, fy), fz);
-	return !(ent > ext || ext < 0.0f || ent > tmaxB * (1.0f + 0x1p-18f));
-}
-
-
-// The first stage of the bundle filter (bundleRejects1) for ALL triangles below a wide-node slot at once.  r0 / r1 = the slot's
-// rtxd::PlaneRec: every triangle's scaled plane normal q = (e2 x e1) / (s1 s2) lies in the box qc +- qr and its plane offset
+//
+// planeAlive, the plane test of a wide-node slot (evaluated by pruneEval8): the first stage of the bundle filter (bundleRejects1) for ALL triangles below
+// the slot at once.  The slot's rtxd::PlaneRec: every triangle's scaled plane normal q = (e2 x e1) / (s1 s2) lies in the box qc +- qr and its plane offset
 // v0 . q in [wlo, whi].  Dividing the filter's inequalities by s1 s2 > 0:
 //     det / (s1 s2) = dir . q,   Nt / (s1 s2) = v0 . q - orig . q,   Ed / (s1 s2) = K dmax,   Et / (s1 s2) = K ainf,
 // so with the range of dir . q and orig . q over the bundle's boxes x the normal box (exact for boxes: centre product +-
@@ -780,29 +701,13 @@ __device__ __forceinline__ bool pruneAlive(const f4v& r0, const f4v& r1, const f
 //     (b) whi - min orig . q + eB < 0                             => t_c < 0                                  (objects.cpp:91)
 //     (c) wlo - max orig . q - eB >= tmaxB (max dir . q + 2 kd) (1 + 2^-18)  => t_c >= every ray's limit      (scene.cpp:740)
 // NaN compares false -> alive; qr < 0 (no bound for this slot) -> alive.
-__device__ __forceinline__ bool planeAlive(const f4v& r0, const f4v& r1, const Bundle& B, float eB, float tmaxB)
-{
-	const float ax = fabsf(r0.x) + r1.x, ay = fabsf(r0.y) + r1.y, az = fabsf(r0.z) + r1.z;      // |qc| + qr
-	const float dqHi = __builtin_fmaf(B.rdz, az, __builtin_fmaf(fabsf(B.dcz), r1.z, __builtin_fmaf(B.dcz, r0.z,
-	                   __builtin_fmaf(B.rdy, ay, __builtin_fmaf(fabsf(B.dcy), r1.y, __builtin_fmaf(B.dcy, r0.y,
-	                   __builtin_fmaf(B.rdx, ax, __builtin_fmaf(fabsf(B.dcx), r1.x, B.dcx * r0.x))))))));
-	const float oqC = __builtin_fmaf(B.ocz, r0.z, __builtin_fmaf(B.ocy, r0.y, B.ocx * r0.x));
-	const float oqR = __builtin_fmaf(B.roz, az, __builtin_fmaf(fabsf(B.ocz), r1.z, __builtin_fmaf(B.roy, ay, __builtin_fmaf(fabsf(B.ocy), r1.y,
-	                  __builtin_fmaf(B.rox, ax, fabsf(B.ocx) * r1.x)))));
-	const float detHi = dqHi + 2.0f * B.kd;
-	const float ntHi = (r1.w - (oqC - oqR)) + eB, ntLo = (r0.w - (oqC + oqR)) - eB;
-	const bool dead = detHi < 0.0f || ntHi < 0.0f || (detHi > 0.0f && ntLo >= tmaxB * (detHi * (1.0f + 0x1p-18f)));
-	return !(dead && r1.x >= 0.0f);
-}
 
-#if RTX_PRUNE_AXIS
-// pruneAlive and planeAlive of the eight slots of one wide node with the lanes acting as (record, AXIS) pairs instead of records: lane 4 r + a looks at axis a
+// pruneAlive and planeAlive of the eight slots of one wide node, with the lanes acting as (record, AXIS) pairs: lane 4 r + a looks at axis a
 // of record r (r < 8: slot r's PruneRec, r >= 8: slot r - 8's PlaneRec; a = 3: the record's fourth words -- P / Pgen, wlo / whi -- which it hands to its quad), so
 // that the per-axis arithmetic of both tests is one instruction for all three axes and what joins the axes (the largest |orig - vertex|, entry / exit, the three
 // dot products) is two DPP steps inside the quad: rotations among lanes 0-2 (lane 3 is never read).  ~70 VALU instructions per node visit against ~110 with one
-// record per lane on 16 lanes ("the prune / plane record evaluation runs on 16 of 64 lanes").  Same inequalities, same margins as pruneAlive /
-// planeAlive above -- only the order in which a dot product's three terms are added differs per lane, which the margins (kd doubled, eB: see planeAlive) cover
-// whatever the order; lane 4 r's verdict is the record's.  Returns bit 4 k set when slot k may contribute.
+// record per lane on 16 lanes ("the prune / plane record evaluation runs on 16 of 64 lanes").  The order in which a dot product's three terms
+// are added differs per lane, which the margins (kd doubled, eB: see planeAlive) cover whatever the order; lane 4 r's verdict is the record's.  Returns bit 4 k set when slot k may contribute.
 // pu = the wave's six axis records (pruneUni); blk = the node's PruneBlock (wave-uniform).
 // CULL = false (options::useBackfaceCulling off, objects.cpp:75-79: a pair is rejected iff |det_c| < 1e-8): the plane test cannot drop back faces, and
 // which sign of Nt means "behind the origin" depends on the sign of det.  With min and max of dir . q over the bundle and the slot:
@@ -812,7 +717,6 @@ __device__ __forceinline__ bool planeAlive(const f4v& r0, const f4v& r1, const B
 //     sign uncertain -> alive.
 // The box test rests on |det_c| >= 1e-8 and magnitudes only (pruneAlive; the source certificates likewise: rtx_source.hip works with |a . m|, and its
 // error terms are symmetric in e1, e2 -- a back face is the front face (e2, e1) with u and v exchanged), so it is the same with and without culling.
-#if RTX_PRUNE_LANEK
 // What a lane of pruneEval8 reads, as ONE register kept across the walk: bits 0-15 the byte offset of its two words in a node's PruneBlock, bits 16-31 the LDS
 // address of its axis record.  Deriving both from the lane index on every visit took 12 VALU instructions; kept as two or three separate registers they spilled.
 __device__ __forceinline__ uint32_t pruneLaneK(const float* pu)
@@ -824,26 +728,14 @@ __device__ __forceinline__ uint32_t pruneLaneK(const float* pu)
 	const uint32_t lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)(pu + ui * 8u);
 	return lds << 16 | word * 4u;
 }
-#endif
 template <bool BOXES, bool CULL = true>
 __device__ __forceinline__ uint32_t pruneEval8(const RTX_AS1 char* blk, const float* pu, float tmaxB, uint32_t laneK = 0)
 {
 	static_assert(kWideSlots == 8, "pruneEval8: lanes = 16 records x 4");
-#if RTX_PRUNE_LANEK
 	const uint32_t off = laneK & 0xffffu;
 	const float f0 = *(const RTX_AS1 float*)(blk + off), f1 = *(const RTX_AS1 float*)(blk + off + 16u);      // (uniform base + a 32-bit lane offset)
 	const __attribute__((address_space(3))) f4v* ur = (const __attribute__((address_space(3))) f4v*)(uintptr_t)(laneK >> 16);
 	const f4v ua = ur[0], ub = ur[1];
-#else
-	const uint32_t lane = laneNow();      // (recomputed here: the addresses derived from it are otherwise hoisted out of the node loop and live -- spilled -- across the walk)
-	const uint32_t axis = lane & 3u;
-	const RTX_AS1 float* pf = (const RTX_AS1 float*)blk;      // (uniform base + a 32-bit lane offset: one scalar-base load, no 64-bit address arithmetic per lane)
-	const uint32_t word = 2u * lane - axis;                   // record lane >> 2 (eight words each), word lane & 3
-	const float f0 = pf[word], f1 = pf[word + 4u];            // box: c_a, h_a (lane 3: P, Pgen); plane: qc_a, qr_a (lane 3: wlo, whi)
-	uint32_t ui = (lane >> 5) * 3u + axis;
-	ui = ui < 5u ? ui : 5u;                      // (the fourth lane of a plane quad reads a record that exists; what it computes is never used)
-	const f4v ua = *(const f4v*)(pu + ui * 8u), ub = *(const f4v*)(pu + ui * 8u + 4u);
-#endif
 	// ---- per axis, both tests (each meaningful on its own half of the wave)
 	// box (pruneAlive): centre mirrored, the largest |orig - vertex| along this axis
 	const float c = __uint_as_float(__float_as_uint(f0) ^ __float_as_uint(ub.x));
@@ -892,10 +784,13 @@ __device__ __forceinline__ uint32_t pruneEval8(const RTX_AS1 char* blk, const fl
 	uint32_t deadBits = (uint32_t)(deadPlane >> 32);      // slot k: lane 32 + 4 k
 	if (BOXES) {
 		// ---- box: the slot's true box inflated by rho against the bundle's segment [0, tmaxB] (pruneAlive)
+		// P of the walk's source copy (rtxd::PruneRec: the camera's, a point light's) holds for origins within kSrcAinfMax of the box; beyond, and in copy 0
+		// (P == Pgen), the unconditional Pgen
 		const float Pn = ainf <= kSrcAinfMax ? w0 : w1;
 		const float rho = __builtin_fmaf(ub.z * ainf, Pn, 0x1p-17f * (ainf + ub.w)) * (1.0f + 0x1p-20f) + 1e-30f;
 		const float hh = f1 + rho;
 		const float a = (c - hh) - ua.w, b = (c + hh) - ua.z;
+		// (an axis that is not usable -- 1 / dir changes sign over the bundle -- drops out through the cap ub.y = -inf: entry -inf, exit +inf, NaN products included)
 		const float e = fminf(fminf(a * ua.x, a * ua.y), ub.y), f = fmaxf(fmaxf(b * ua.x, b * ua.y), -ub.y);
 		float ent, ext;
 		asm volatile("s_nop 1\n\t"
@@ -910,7 +805,6 @@ __device__ __forceinline__ uint32_t pruneEval8(const RTX_AS1 char* blk, const fl
 	}
 	return ~deadBits & 0x11111111u;
 }
-#endif
 
 template <bool STATS, bool CULL, bool REGULAR, bool WIDE = false, bool FEWRAYS = false, bool BOXES = true>
 __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool consider, bool shadow, const V3& o, const V3& d,
@@ -966,7 +860,6 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 			if (laneNow() == 0) {
 				const bool nx = hx < 0, ny = hy < 0, nz = hz < 0;
 				const bool okx = usx && (lx > 0 || nx), oky = usy && (ly > 0 || ny), okz = usz && (lz > 0 || nz);
-#if RTX_PRUNE_AXIS
 				// (plain scalars, each record built in one go: assembled from the components of other vectors, the records went through 32 bytes of scratch per lane --
 				// the kernel's only scratch)
 				const float ilx = nx ? -hx : lx, ihx = nx ? -lx : hx, ily = ny ? -hy : ly, ihy = ny ? -ly : hy, ilz = nz ? -hz : lz, ihz = nz ? -lz : hz;
@@ -984,35 +877,13 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 				*(f4v*)(pu + 24) = f4v{ dcx, rdx, B.ocx, B.rox }; *(f4v*)(pu + 28) = f4v{ kd2, eB, 0.0f, 0.0f };
 				*(f4v*)(pu + 32) = f4v{ dcy, rdy, B.ocy, B.roy }; *(f4v*)(pu + 36) = f4v{ kd2, eB, 0.0f, 0.0f };
 				*(f4v*)(pu + 40) = f4v{ dcz, rdz, B.ocz, B.roz }; *(f4v*)(pu + 44) = f4v{ kd2, eB, 0.0f, 0.0f };
-#else
-				f4v a, b, c, e;
-				a.x = nx ? -hx : lx; a.y = nx ? -lx : hx; a.z = ny ? -hy : ly; a.w = ny ? -ly : hy;
-				b.x = nz ? -hz : lz; b.y = nz ? -lz : hz;
-				const float ocx = nx ? -B.ocx : B.ocx, ocy = ny ? -B.ocy : B.ocy, ocz = nz ? -B.ocz : B.ocz;
-				b.z = ocx - B.rox; b.w = ocx + B.rox;
-				c.x = ocy - B.roy; c.y = ocy + B.roy; c.z = ocz - B.roz; c.w = ocz + B.roz;
-				e.x = B.kd * (kPruneC / kFilterK);      // 216 dmax (kd = K dmax, rounded up)
-				e.y = fmaxf(fmaxf(fabsf(B.ocx) + B.rox, fabsf(B.ocy) + B.roy), fabsf(B.ocz) + B.roz);
-				e.z = __uint_as_float((nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u) | (okx ? 8u : 0u) | (oky ? 16u : 0u) | (okz ? 32u : 0u));
-				e.w = kFilterK * (e.y + F(mp[13])) * (1.0f + 0x1p-20f) + 1e-30f;      // K (|orig| + |vertex|): see planeAlive
-				f4v f, g;
-				f.x = __uint_as_float(nx ? 0x80000000u : 0u); f.y = __uint_as_float(ny ? 0x80000000u : 0u); f.z = __uint_as_float(nz ? 0x80000000u : 0u);
-				f.w = okx ? __builtin_inff() : -__builtin_inff();
-				g.x = oky ? __builtin_inff() : -__builtin_inff(); g.y = okz ? __builtin_inff() : -__builtin_inff(); g.z = 0; g.w = 0;
-				*(f4v*)(pu + 0) = a; *(f4v*)(pu + 4) = b; *(f4v*)(pu + 8) = c; *(f4v*)(pu + 12) = e;
-				*(f4v*)(pu + 16) = f; *(f4v*)(pu + 20) = g;
-#endif
 			}
 			if (!B.sane) pruneRecs = nullptr;      // NaN / inf / huge coordinates somewhere in the bundle: nothing is pruned
 		}
 	}
 	if (WIDE && RTX_DBG) { cnt.aWalks++; if (shadow) cnt.sWalks++; }
-#if RTX_PRUNE_LANEK
 	uint32_t laneK = WIDE ? pruneLaneK(pu) : 0u;
 	asm volatile("" : "+v"(laneK));      // (one register, computed once per walk: not re-derived inside the node loop)
-#else
-	const uint32_t laneK = 0;
-#endif
 	if (WIDE) {
 		// (the rays in `consider` have passed the root box: traceWave)
 		const uint64_t m0 = ballot(consider);
@@ -1068,33 +939,15 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 				const WideNode* w = wideNodes + (uint32_t)(link - 1);
 				// slots 3..0 are requested at once (their fetch runs while the prune records are evaluated); the SGPR file does not hold eight slots: see below
 				u32x16 wa = sload16(w), wb = sload16((const char*)w + 64);
-				// Which slots can contribute at all: of the first 2 kWideSlots lanes, lane k looks at record k (boxes, then planes: rtxd::PruneBlock).
-				uint32_t aliveM = (1u << kWideSlots) - 1u;
-				// (four slots: not at the root, where they are as good as never pruned -- 7 of 259 in tools/research/pruned_walk_sim.py; eight: everywhere)
-				const bool evalPrune = pruneRecs != nullptr && (kPruneRoot || link != 1);
-#if RTX_PRUNE_AXIS
-				// (aliveM in the form pruneEval8 returns: slot k = bit 4 k)
-				aliveM = 0x11111111u;
+				// Which slots can contribute at all (the root's too: -1.6 %), in the form pruneEval8 returns: slot k = bit 4 k.
+				uint32_t aliveM = 0x11111111u;
+				const bool evalPrune = pruneRecs != nullptr;
 				if (evalPrune) {
 					aliveM = pruneEval8<BOXES, CULL>(pruneRecs + ((size_t)(uint32_t)(link - 1) << 9), pu, tmaxB, laneK);
 					if (RTX_DBG) { cnt.wS4++; cnt.wLeafSkips += (uint32_t)kWideSlots - (uint32_t)__popc(aliveM); }
 				}
 #define RTX_ALIVE(k) ((aliveM >> (4 * (k))) & 1u)
 #define RTX_ALIVE4(q) ((aliveM >> (16 * (q))) & 0x1111u)
-#else
-#define RTX_ALIVE(k) ((aliveM >> (k)) & 1u)
-#define RTX_ALIVE4(q) ((aliveM >> (4 * (q))) & 0xfu)
-				if (evalPrune) {
-					// lanes [0, kWideSlots): the slots' boxes (PruneRec), [kWideSlots, 2 kWideSlots): their planes (PlaneRec); both tests run on every lane's record
-					const RTX_AS1 f4v* pr = (const RTX_AS1 f4v*)(pruneRecs + (((uint32_t)(link - 1) * (2u * kWideSlots) + (lane & (2u * kWideSlots - 1u))) << 5));
-					const f4v r0 = pr[0], r1 = pr[1];
-					const bool aliveBox = !BOXES || pruneAlive(r0, r1, pu, tmaxB);      // (BOXES: see the kernels' template parameter)
-					const bool alivePlane = !CULL || planeAlive(r0, r1, B, pu[15], tmaxB);      // (planeAlive's rejections assume culling; pruneEval8 has the other form)
-					const uint32_t bal = (uint32_t)ballot((lane & (uint32_t)kWideSlots) ? alivePlane : aliveBox);
-					aliveM = bal & (bal >> kWideSlots) & ((1u << kWideSlots) - 1u);
-					if (RTX_DBG) { cnt.wS4++; cnt.wLeafSkips += (uint32_t)kWideSlots - (uint32_t)__popc(aliveM); }
-				}
-#endif
 				// The node's slots four at a time (two s_load_dwordx16: the SGPR file holds no more), the last four first, slots 3..0 of every four in
 				// that order, so that slot 0 ends up on top of the stack; four slots none of which is alive are not fetched.
 #define RTX_SLOT(rec, base, k)                                                                                                     \
@@ -1104,7 +957,7 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 					if (RTX_DBG) cnt.wS3++;                                                                                         \
 					if (mk_ != 0) RTX_PUSH(rec[base + 6], rec[base + 7], mk_)                                                       \
 				}
-				if (kWideSlots > 4 && RTX_ALIVE4(1) != 0) {
+				if (RTX_ALIVE4(1) != 0) {
 					// the upper slots first, four at a time from the top (they are pushed first): the registers of slots 3..0 are given up for them and loaded
 					// again afterwards (a hit in the scalar cache; touching the lines of the upper slots when the node is popped made no difference: profiles/r04_wide8.txt)
 #pragma unroll
@@ -1240,18 +1093,10 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 			rb.e1x = vb.x; rb.e1y = vb.y; rb.e1z = vb.z; rb.e2x = vb.w; rc.e2y = vc.x; rc.e2z = vc.y;
 			FilterState fs;
 			const bool valid = p0 + lane < total;
-#if RTX_FILTER_MASKS
 			const uint64_t open1 = ballot(valid) & ~bundleRejects1<CULL>(B, tmaxB, ra, rb, rc, fs);
 			if (RTX_DBG) { cnt.wChunks++; if (shadow) cnt.sPasses++; }
 			if (open1 == 0) { if (RTX_DBG) cnt.wChunkSkips++; return false; }
 			uint64_t cand = open1 & ~bundleRejects2<CULL>(B, ra, rb, rc, fs, open1);
-#else
-			const bool rej1 = bundleRejects1<CULL>(B, tmaxB, ra, rb, rc, fs);
-			if (RTX_DBG) { cnt.wChunks++; if (shadow) cnt.sPasses++; }
-			if (ballot(valid && !rej1) == 0) { if (RTX_DBG) cnt.wChunkSkips++; return false; }
-			const bool rej2 = bundleRejects2<CULL>(B, ra, rb, rc, fs);
-			uint64_t cand = ballot(valid && !rej1 && !rej2);
-#endif
 			if (RTX_DBG) { cnt.wTri += __popcll(cand); if (shadow) cnt.sExact += __popcll(cand); if (cand == 0) cnt.wS2++; }
 			if (cand == 0) return false;
 			bool improved = false;
@@ -1288,9 +1133,7 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 				}
 				cand = 0;
 			}
-#if RTX_EXACT_HOIST
 			const float btBefore = bt;      // (bt only falls: one compare after the survivors instead of one per survivor, and no copy of bt carried round the loop)
-#endif
 			while (cand != 0) {
 				const int c = __builtin_ctzll(cand);
 				cand &= cand - 1;
@@ -1307,17 +1150,9 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 				// the rays that reached the survivor's leaf
 				const uint32_t ent = (kLeafBatch == 1 && !FEWRAYS) ? 0u : (uint32_t)__builtin_amdgcn_ds_bpermute(c << 2, (int)myEnt);
 				const bool pass = ((myReach >> ent) & 1u) != 0;      // (no dependent LDS read of the table's mask per survivor)
-#if !RTX_EXACT_HOIST
-				const float before = bt;
-#endif
 				if (pass) triTestOne<CULL, STATS>(v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z, tri, o, d, bt, bu, bv, btri);
-#if !RTX_EXACT_HOIST
-				improved = improved || bt < before;
-#endif
 			}
-#if RTX_EXACT_HOIST
 			improved = improved || bt < btBefore;
-#endif
 			RTX_DBG_ONLY(dbgExact += __builtin_readcyclecounter() - dbgE0;)
 			if (ballot(improved) != 0) {
 				// any-hit: a shadow ray only asks "is some t < light distance" (scene.cpp:787); once that is true
@@ -1393,10 +1228,6 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 			// filter to reject much (rays of a silhouette tile that hit different objects, a grazing strip of shadow-ray
 			// origins, coarse frames): then the lanes on one side of the middle of the widest axis go first, the others
 			// later, halving until the bundle is narrow.  Which lanes walk together changes the amount of work only.
-#if !RTX_REC2_RELOAD
-			const float fat = F(rec2[8]), mrad = F(rec2[12]);
-			const float mcx = F(rec2[9]), mcy = F(rec2[10]), mcz = F(rec2[11]);
-#endif
 			const uint32_t mflags = rec2[13];
 			// Rays that fail the root box (objects.cpp:590) take no further part: the bundles are formed by the others.
 			bool pending = consider;
@@ -1422,7 +1253,7 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 				pending = consider && !fail;
 			}
 			// (src == 1: the ray starts at the camera, o == view.camPos bit for bit -- castRayWave)
-			const bool oneOrigin = RTX_SAME_ORIGIN && !STATS && ballot(pending && src != 1u) == 0;
+			const bool oneOrigin = !STATS && ballot(pending && src != 1u) == 0;
 			while (ballot(pending) != 0) {
 				bool cl = pending;
 				// the regular rays first, as one bundle (or more: the split below); what is left afterwards are the irregular ones
@@ -1431,14 +1262,12 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 					const uint64_t regM = ballot(pending && laneRegular);
 					if (regM != 0) { cl = pending && laneRegular; regular = true; }
 				}
-#if RTX_REC2_RELOAD
 				// what the split rule needs of the object's second line, fetched again per bundle (a hit in the scalar cache, requested ahead of the reductions below)
 				// instead of being kept in -- i.e. spilled from -- sixteen SGPRs across the walk of the previous bundle
 				const char* ob2 = (const char*)ob + 96;
 				asm volatile("" : "+s"(ob2));
 				const u32x8 geo = sload8(ob2);      // fatRadius, centre[3], radius, meshFlags, pad[2]
 				const float fat = F(geo[0]), mcx = F(geo[1]), mcy = F(geo[2]), mcz = F(geo[3]), mrad = F(geo[4]);
-#endif
 				Bundle B = makeBundle(cl, o, d, oneOrigin);
 				for (int split = 0; split < RTX_MAX_SPLITS; ++split) {
 					// width of the bundle where it can meet the mesh: origin box, and direction box times the distance to the far side
@@ -1464,11 +1293,9 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 					}
 				}
 				if (!STATS && cull && regular && wideOk) meshWalk<STATS, true, true, true, FEWRAYS, BOXES>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt, srcSel);
-#if RTX_WIDE_NOCULL
 				// culling off (options.h:27, objects.cpp:75-79): the same wide walk; its filter mirrors by the sign of det (bundleRejects1), its plane records
 				// keep what may show either face (pruneEval8<.., false>)
 				else if (!STATS && regular && wideOk) meshWalk<STATS, false, true, true, FEWRAYS, BOXES>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt, srcSel);
-#endif
 				else if (cull && regular) meshWalk<STATS, true, true, false, FEWRAYS>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
 				else if (cull) meshWalk<STATS, true, false, false, FEWRAYS>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
 				else meshWalk<STATS, false, false, false, FEWRAYS>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
@@ -1607,7 +1434,6 @@ struct LightRec { int type; V3 color; float intensity; V3 dir, pos; uint32_t nPo
 // PLAIN (round 6): the kernel was chosen for a scene whose objects are all Diffuse and whose lights are all point / distant lights (rtx_scene_create checks; nothing can change
 // either afterwards) -- the mirror / glass recursion with its frame stack, Phong's powf (a real call) and the area-light sums cannot be reached, and are not compiled in: a third of
 // the state machine's code and half of the kernel's scratch go with them (pass 1 of the headline -2.7 %: profiles/r06_ab_plain.txt).
-#if RTX_ADVANCE_UNIFORM
 template <bool PLAIN = false>
 __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 {
@@ -1615,7 +1441,7 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 	const float bias = P.view.bias;
 	// One loop for the whole wave with a UNIFORM exit: a lane that has reached a waiting state (or ST_DONE) sits out the remaining steps (run = false) instead
 	// of leaving the loop.  With per-lane `return`s the compiler kept every field of the lane state twice -- the value a lane left with and the value the others go on
-	// changing -- and copied 16-20 registers at the head of every step and at every exit (RTX_ADVANCE_UNIFORM = 0: that form).
+	// changing -- and copied 16-20 registers at the head of every step and at every exit (pass 1 -2.7 %: profiles/r06_ab_control_flow.txt).
 	bool run = true;
 	do {
 		if (!run) continue;
@@ -1764,162 +1590,6 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 		run = false;   // ST_DONE / waiting states
 	} while (ballot(run) != 0);
 }
-#else
-template <bool PLAIN = false>
-__device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
-{
-	const int maxDepth = P.view.maxDepth;
-	const float bias = P.view.bias;
-	for (;;) {
-		if (s.state == ST_NEWRAY) {
-			RTX_T0
-			if (s.sp > maxDepth) { s.col = skyColor(P, s.rd); s.state = ST_RETURN; RTX_ACC(0) continue; }   // scene.cpp:760
-			s.qtmax = kFltMax;
-			s.state = ST_WAIT_PRIMARY;
-			return;
-		}
-		if (s.state == ST_NEXT_LIGHT) {
-			RTX_T0
-			if (s.li >= P.nLights) { s.state = ST_LIGHTS_DONE; continue; }
-			// The light's record: the lanes that are here are nearly always at the same light -- then it comes through the scalar
-			// unit in one load (the per-lane form is a chain of dependent vector loads: type, then the fields of that type).
-			LightRec lr;
-			const uint32_t li0 = __builtin_amdgcn_readfirstlane(s.li);
-			if (ballot(s.li != li0) == 0) {
-				const u32x16 w = sload16(P.lights + li0);
-				lr.type = (int)w[0]; lr.color = mk(F(w[1]), F(w[2]), F(w[3])); lr.intensity = F(w[4]);
-				lr.dir = mk(F(w[5]), F(w[6]), F(w[7])); lr.pos = mk(F(w[8]), F(w[9]), F(w[10])); lr.nPoints = w[11];
-				lr.points = (const float*)(((uint64_t)w[13] << 32) | w[12]);
-			}
-			else {
-				const Light* lp = P.lights + s.li;
-				lr.type = lp->type; lr.color = mk(lp->color[0], lp->color[1], lp->color[2]); lr.intensity = lp->intensity;
-				lr.dir = mk(lp->dir[0], lp->dir[1], lp->dir[2]); lr.pos = mk(lp->pos[0], lp->pos[1], lp->pos[2]); lr.nPoints = lp->nPoints; lr.points = lp->points;
-			}
-			const LightRec* l = &lr;
-			const int lt = l->type;
-			if (PLAIN && lt == 3) __builtin_unreachable();
-			float dist;
-			if (lt == 1) {                 // DistantLight::illuminate, lights.cpp:18-23
-				s.L = l->dir;
-				s.I = l->color * l->intensity;
-				dist = kFltMax;
-			}
-			else if (lt == 2) {            // PointLight::illuminate, lights.cpp:32-38
-				const V3 lp = l->pos;
-				V3 L = s.P - lp;
-				s.I = l->color * attenuation(l->intensity, len2(L));
-				s.L = normalized(L);
-				dist = length(s.P - lp);
-			}
-			else {                         // area light sample loop, scene.cpp:790-806 etc.
-				const uint32_t np = l->nPoints;
-				if (s.si == 0) {
-					const V3 lp = l->pos;
-					s.I = l->color * attenuation(l->intensity, len2(s.P - lp));
-					s.dsum = 0; s.ssum = 0;
-				}
-				if (s.si >= np) {
-					const float fn = (float)np;
-					if (s.mat == 0) s.diff = s.diff + s.I * (s.dsum / fn);                       // scene.cpp:805
-					else if (s.mat == 3) {                                                      // scene.cpp:845-846
-						s.diff = s.diff + s.I * (s.dsum / fn);
-						s.spec = s.spec + s.I * powfRef(s.ssum / fn, s.nSpec);
-					}
-					else s.spec = s.spec + s.I * powfRef(s.ssum / fn, s.nSpec);                  // scene.cpp:887, 937
-					s.li++; s.si = 0;
-					continue;
-				}
-				V3 L = s.P - load3(inGlobal(l->points) + (size_t)s.si * 3);
-				dist = length(L);
-				s.L = normalized(L);
-			}
-			// Diffuse (scene.cpp:780-809): the only use of the shadow ray is  vis * max(0, N . -L)  with vis in {0, 1}.  When
-			// the max is +0 (surface turned away from the light, or NaN) the product is the same +0 for either answer: the
-			// ray cannot influence the pixel ("moot"), and the product kernels do not walk it (castRayWave).
-			s.qmoot = s.mat == 0 && fmaxRef(0.f, dot(s.N, -s.L)) == 0.f;
-			s.qarea = lt == 3;
-			// (a light's source copy was derived for shadow-ray origins within srcNmax |bias| of the surface: a shading normal longer than the host
-			// looked at -- a caller's un-normalised tri_nrm, a future object type -- or NaN falls back to copy 0 instead of pruning with too small a sigma)
-			s.qsrc = (lt == 2 && s.li < P.nSrcLights && len2(s.N) <= P.srcNmax2) ? 2u + s.li : 0u;
-			s.qtmax = dist;               // the ray itself: Ray{P + N*bias, -L, ShadowRay} (scene.cpp:787), built in castRayWave
-			s.state = ST_WAIT_SHADOW;
-			RTX_ACC(1)
-			return;
-		}
-		if (s.state == ST_LIGHTS_DONE) {
-			RTX_T0
-			const Object* ob = P.objects + s.obj;
-			if (PLAIN && s.mat != 0) __builtin_unreachable();
-			if (s.mat == 0) { s.col = s.objColor * s.diff; s.state = ST_RETURN; continue; }       // scene.cpp:808
-			if (s.mat == 3) {                                                                   // scene.cpp:852
-				s.col = s.objColor * ob->ambient + s.diff * ob->diffuse + s.spec * s.specCoef;
-				s.state = ST_RETURN; continue;
-			}
-			if (s.mat == 1) {                                                                   // scene.cpp:856-858, 890
-				frameAt(P, gl, s.sp, 0) = __int_as_float(FR_REFL);
-				frameAt(P, gl, s.sp, 2) = s.spec.x; frameAt(P, gl, s.sp, 3) = s.spec.y; frameAt(P, gl, s.sp, 4) = s.spec.z;
-				const V3 nd = s.rd - s.N * (2 * dot(s.rd, s.N));
-				s.ro = s.P + s.N * bias; s.rd = nd;
-				s.sp++; s.state = ST_NEWRAY; RTX_ACC(2) continue;
-			}
-			// Transparent, scene.cpp:893-907
-			const float ior = ob->ior;
-			const float kr = fresnelKr(s.rd, s.N, ior);
-			const bool outside = dot(s.rd, s.N) < 0;
-			const V3 biasVec = s.N * bias;
-			const V3 fd = normalized(reflectDir(s.rd, s.N));
-			const V3 fo = outside ? s.P + biasVec : s.P - biasVec;
-			frameAt(P, gl, s.sp, 1) = kr;
-			frameAt(P, gl, s.sp, 2) = s.spec.x; frameAt(P, gl, s.sp, 3) = s.spec.y; frameAt(P, gl, s.sp, 4) = s.spec.z;
-			if (kr < 1) {
-				const V3 rd = normalized(refractDir(s.rd, s.N, ior));
-				const V3 ro = outside ? s.P - biasVec : s.P + biasVec;
-				frameAt(P, gl, s.sp, 0) = __int_as_float(FR_TRANS1);
-				frameAt(P, gl, s.sp, 8) = fo.x; frameAt(P, gl, s.sp, 9) = fo.y; frameAt(P, gl, s.sp, 10) = fo.z;
-				frameAt(P, gl, s.sp, 11) = fd.x; frameAt(P, gl, s.sp, 12) = fd.y; frameAt(P, gl, s.sp, 13) = fd.z;
-				s.ro = ro; s.rd = rd;
-			}
-			else {
-				frameAt(P, gl, s.sp, 0) = __int_as_float(FR_TRANS2);
-				frameAt(P, gl, s.sp, 5) = 0.f; frameAt(P, gl, s.sp, 6) = 0.f; frameAt(P, gl, s.sp, 7) = 0.f;
-				s.ro = fo; s.rd = fd;
-			}
-			s.sp++; s.state = ST_NEWRAY; RTX_ACC(3) continue;
-		}
-		if (s.state == ST_RETURN) {
-			RTX_T0
-			if (s.sp == 0) { s.state = ST_DONE; return; }
-			if (PLAIN) __builtin_unreachable();      // (nothing ever pushed a frame)
-			s.sp--;
-			// The whole frame is requested at once (14 coalesced loads, one round trip) instead of the kind first and then the fields of
-			// that kind: a deep reflect / refract tree is a chain of these, and a small frame lasts as long as its deepest pixel.
-			float fr[kFrameFields];
-			for (int k = 0; k < kFrameFields; ++k) fr[k] = frameAt(P, gl, s.sp, k);
-			asm volatile("" : "+v"(fr[0]), "+v"(fr[1]), "+v"(fr[2]), "+v"(fr[3]), "+v"(fr[4]), "+v"(fr[5]), "+v"(fr[6]));
-			asm volatile("" : "+v"(fr[7]), "+v"(fr[8]), "+v"(fr[9]), "+v"(fr[10]), "+v"(fr[11]), "+v"(fr[12]), "+v"(fr[13]));
-			const int kind = __float_as_int(fr[0]);
-			const V3 spec = mk(fr[2], fr[3], fr[4]);
-			if (kind == FR_REFL) { s.col = s.col * 0.8f + spec; RTX_ACC(4) continue; }                      // scene.cpp:858, 890
-			const float kr = fr[1];
-			if (kind == FR_TRANS1) {                                                             // scene.cpp:896-902
-				const V3 acc = mk(0, 0, 0) + s.col * (1 - kr);
-				frameAt(P, gl, s.sp, 0) = __int_as_float(FR_TRANS2);
-				frameAt(P, gl, s.sp, 5) = acc.x; frameAt(P, gl, s.sp, 6) = acc.y; frameAt(P, gl, s.sp, 7) = acc.z;
-				s.ro = mk(fr[8], fr[9], fr[10]);
-				s.rd = mk(fr[11], fr[12], fr[13]);
-				s.sp++; s.state = ST_NEWRAY; RTX_ACC(5) continue;
-			}
-			V3 acc = mk(fr[5], fr[6], fr[7]);
-			acc = acc + s.col * kr;                                                              // scene.cpp:908
-			s.col = acc + spec * kr;                                                             // scene.cpp:940
-			RTX_ACC(6)
-			continue;
-		}
-		return;   // ST_DONE / waiting states
-	}
-}
-#endif
 
 // Consumes a finished Render::trace for this lane.
 template <bool PLAIN = false>
@@ -1985,9 +1655,7 @@ __device__ __forceinline__ void primaryRay(const Params& P, float x, float y, V3
 // parked in LDS around every trace so that the walk has the registers.  Left to the compiler it goes to scratch, i.e.
 // through L2 into HBM and back (round 1 / 2: 5.9 GB of writes per launch for a 0.2-GB framebuffer); the kernels use
 // 5-10 KB of the 32-40 KB of LDS their occupancy leaves a block.
-constexpr bool kParkColor = kWideSlots < 16;      // (sixteen-slot nodes: the stack takes the 3 KB of objColor's three fields)
-constexpr int kParkFields = 25 - (kParkColor ? 0 : 3);
-constexpr int kPk = kParkColor ? 0 : -3;          // index shift of the fields behind objColor      // (26 with nSpec until the eight-slot walk's stack needed the kilobyte: five blocks per CU hold 31 744 B each)
+constexpr int kParkFields = 25;      // (26 with nSpec until the eight-slot walk's stack needed the kilobyte: five blocks per CU hold 31 744 B each)
 // (PLAIN kernels: no specular sum and no specular coefficient to park -- four kilobytes less, which with the pow table they do not touch is what a SIXTH block per CU needs)
 template <bool PLAIN> struct ParkLayout { static constexpr int kFields = kParkFields - (PLAIN ? 4 : 0), kSp = PLAIN ? -3 : 0; };
 template <bool PLAIN>
@@ -2028,15 +1696,10 @@ __device__ __forceinline__ V3 castRayWave(const Params& P0, bool valid, V3 o, V3
 	s.specCoef = s.nSpec = s.dsum = s.ssum = 0;
 	s.qtmax = kFltMax; s.qmoot = false; s.qarea = false; s.qsrc = 0;
 	RTX_DBG_ONLY(unsigned long long dbgRounds = 0, dbgTrace = 0, dbgState = 0;)
-#if RTX_ONE_ADVANCE
 	// (one copy of advance() in the kernel: at the head of the round instead of before the loop and at its end -- the same sequence of steps)
 	for (;;) {
 		advance<PLAIN>(freshParams(P0), s, gl);
 		if (ballot(s.state != ST_DONE) == 0) break;
-#else
-	advance<PLAIN>(P, s, gl);
-	while (ballot(s.state != ST_DONE) != 0) {
-#endif
 		Hit h;
 		RTX_DBG_ONLY(const unsigned long long dbgT0 = __builtin_readcyclecounter();)
 		// moot shadow rays (see advance): only the instrumented variant walks them -- the reference's statistics count
@@ -2056,13 +1719,13 @@ __device__ __forceinline__ V3 castRayWave(const Params& P0, bool valid, V3 o, V3
 			constexpr int kSp = ParkLayout<PLAIN>::kSp;
 			parkedState[0][t] = s.P.x; parkedState[1][t] = s.P.y; parkedState[2][t] = s.P.z;
 			parkedState[3][t] = s.N.x; parkedState[4][t] = s.N.y; parkedState[5][t] = s.N.z;
-			if (kParkColor) { parkedState[6][t] = s.objColor.x; parkedState[7][t] = s.objColor.y; parkedState[8][t] = s.objColor.z; }
-			parkedState[9 + kPk][t] = s.diff.x; parkedState[10 + kPk][t] = s.diff.y; parkedState[11 + kPk][t] = s.diff.z;
-			if (!PLAIN) { parkedState[12 + kPk][t] = s.spec.x; parkedState[13 + kPk][t] = s.spec.y; parkedState[14 + kPk][t] = s.spec.z; }
-			parkedState[15 + kPk + kSp][t] = s.L.x; parkedState[16 + kPk + kSp][t] = s.L.y; parkedState[17 + kPk + kSp][t] = s.L.z;
-			parkedState[18 + kPk + kSp][t] = s.I.x; parkedState[19 + kPk + kSp][t] = s.I.y; parkedState[20 + kPk + kSp][t] = s.I.z;
-			parkedState[21 + kPk + kSp][t] = s.rd.x; parkedState[22 + kPk + kSp][t] = s.rd.y; parkedState[23 + kPk + kSp][t] = s.rd.z;
-			if (!PLAIN) parkedState[24 + kPk][t] = s.specCoef;
+			parkedState[6][t] = s.objColor.x; parkedState[7][t] = s.objColor.y; parkedState[8][t] = s.objColor.z;
+			parkedState[9][t] = s.diff.x; parkedState[10][t] = s.diff.y; parkedState[11][t] = s.diff.z;
+			if (!PLAIN) { parkedState[12][t] = s.spec.x; parkedState[13][t] = s.spec.y; parkedState[14][t] = s.spec.z; }
+			parkedState[15 + kSp][t] = s.L.x; parkedState[16 + kSp][t] = s.L.y; parkedState[17 + kSp][t] = s.L.z;
+			parkedState[18 + kSp][t] = s.I.x; parkedState[19 + kSp][t] = s.I.y; parkedState[20 + kSp][t] = s.I.z;
+			parkedState[21 + kSp][t] = s.rd.x; parkedState[22 + kSp][t] = s.rd.y; parkedState[23 + kSp][t] = s.rd.z;
+			if (!PLAIN) parkedState[24][t] = s.specCoef;
 			asm volatile("" ::: "memory");
 		}
 		traceWave<STATS, MESH, FEWRAYS, BOXES, CULLK>(freshParams(P0), qactive, qshadow, qo, qd, qtmax, h, cnt, qsrc);
@@ -2073,21 +1736,18 @@ __device__ __forceinline__ V3 castRayWave(const Params& P0, bool valid, V3 o, V3
 			constexpr int kSp = ParkLayout<PLAIN>::kSp;
 			s.P = mk(parkedState[0][t], parkedState[1][t], parkedState[2][t]);
 			s.N = mk(parkedState[3][t], parkedState[4][t], parkedState[5][t]);
-			if (kParkColor) s.objColor = mk(parkedState[6][t], parkedState[7][t], parkedState[8][t]);
-			s.diff = mk(parkedState[9 + kPk][t], parkedState[10 + kPk][t], parkedState[11 + kPk][t]);
-			if (!PLAIN) s.spec = mk(parkedState[12 + kPk][t], parkedState[13 + kPk][t], parkedState[14 + kPk][t]);
-			s.L = mk(parkedState[15 + kPk + kSp][t], parkedState[16 + kPk + kSp][t], parkedState[17 + kPk + kSp][t]);
-			s.I = mk(parkedState[18 + kPk + kSp][t], parkedState[19 + kPk + kSp][t], parkedState[20 + kPk + kSp][t]);
-			s.rd = mk(parkedState[21 + kPk + kSp][t], parkedState[22 + kPk + kSp][t], parkedState[23 + kPk + kSp][t]);
-			if (!PLAIN) s.specCoef = parkedState[24 + kPk][t];
+			s.objColor = mk(parkedState[6][t], parkedState[7][t], parkedState[8][t]);
+			s.diff = mk(parkedState[9][t], parkedState[10][t], parkedState[11][t]);
+			if (!PLAIN) s.spec = mk(parkedState[12][t], parkedState[13][t], parkedState[14][t]);
+			s.L = mk(parkedState[15 + kSp][t], parkedState[16 + kSp][t], parkedState[17 + kSp][t]);
+			s.I = mk(parkedState[18 + kSp][t], parkedState[19 + kSp][t], parkedState[20 + kSp][t]);
+			s.rd = mk(parkedState[21 + kSp][t], parkedState[22 + kSp][t], parkedState[23 + kSp][t]);
+			if (!PLAIN) s.specCoef = parkedState[24][t];
 		}
 		RTX_DBG_ONLY(const unsigned long long dbgT1 = __builtin_readcyclecounter();)
 		if (s.state != ST_DONE) {
 			const Params& Pa = freshParams(P0);
 			consume<PLAIN>(Pa, s, h);
-#if !RTX_ONE_ADVANCE
-			advance<PLAIN>(Pa, s, gl);
-#endif
 		}
 		RTX_DBG_ONLY(dbgRounds++; dbgTrace += dbgT1 - dbgT0; dbgState += __builtin_readcyclecounter() - dbgT1;)
 	}
@@ -2187,7 +1847,6 @@ __global__ void __launch_bounds__(256, MESH ? (PLAIN ? RTX_WAVES_PLAIN : RTX_WAV
 			RTX_DBG_ONLY(if (P.pad3 != 0 && tile != P.pad3 - 1) continue;)   // RTX_DBG_TILE=tx,ty: only this tile (counters of one work item)
 			// a tile (ty << 16 | tx), or a 64 x 1 strip of a halo row (0x10000000 | strip << 16 | y: rtx_api.hip, buildTileList),
 			// which is accounted to the first of the eight tiles it runs through
-#if RTX_TILE_RECOMPUTE
 			// What the tile's pixels are is derived from the list entry twice -- before the rays are cast and again afterwards, from fresh copies of the parameters --
 			// instead of being kept (x, y and a dozen scalars: spilled) across castRayWave.
 			uint32_t tx, ty, x, y; bool strip, valid;
@@ -2232,37 +1891,6 @@ __global__ void __launch_bounds__(256, MESH ? (PLAIN ? RTX_WAVES_PLAIN : RTX_WAV
 			}
 		}
 	}
-#else
-			const bool strip = (tile & P.stripBit) != 0;      // (stripBit = 0 when the list holds no strips: tile rows from 4096 on use bit 28 themselves)
-			const uint32_t tx = strip ? ((tile >> 16) & 0xfffu) * 8 : tile & 0xffffu, ty = strip ? (tile & 0x7fffu) >> 3 : tile >> 16;
-			const uint32_t x = strip ? tx * 8 + lane : tx * 8 + (lane & 7), y = strip ? tile & 0x7fffu : ty * 8 + (lane >> 3);
-			// x1/y1 are clamped to W-1/H-1: the last column and row are never rendered (scene.cpp:369-372)
-			const bool valid = x < W - 1 && y < H - 1 && y >= P.rowBegin && y < P.rowEnd && rowRendered(P, y);
-			if (ballot(valid) == 0) continue;
-			V3 o, d;
-			primaryRay(P, (float)x + 0.5f, (float)y + 0.5f, o, d);
-			// a tile that was slow in the previous launch of this view (a pole, a silhouette) runs at raised priority: the
-			// launch ends when its slowest wave does, and such a wave otherwise gets one issue slot in RTX_WAVES
-			if (take > 1) __builtin_amdgcn_s_setprio(0);      // (the cheap part of the queue: no look at the tile's cost)
-			else
-			if (sload1(P.tileCost + ty * P.tilesXFull + tx) > RTX_PRIO_TICKS) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-			const unsigned long long t0 = wall_clock64();
-			const V3 c = castRayWave<STATS, MESH, false, BOXES, true, CULLK, PLAIN>(P, valid, o, d, gl, cnt);
-			const unsigned long long dt = wall_clock64() - t0;
-			RTX_TRACE_ONLY(dbgEnd = t0 + dt; dbgBusy += dt;)
-			if (lane == 0) {
-				// remembered per tile: the SSAA pass starts with the tiles that were expensive here (longest job first)
-				if (!strip) P.tileCost[ty * P.tilesXFull + tx] = dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
-				if (STATS) { atomicMax(P.counters + 3, dt); atomicAdd(P.counters + 4, dt); }
-			}
-			if (strip && lane < 8 && tx + lane < P.tilesX) P.tileCost[ty * P.tilesXFull + tx + lane] = (uint32_t)((dt > 0xffffffffull ? 0xffffffffull : dt) / 8);
-			if (valid) {
-				float* px = P.fb + ((size_t)y * W + x) * 3;
-				px[0] = c.x; px[1] = c.y; px[2] = c.z;
-			}
-		}
-	}
-#endif
 	RTX_TRACE_ONLY(if (lane == 0 && (gl >> 6) < 16384) { gDbgWave[3 * (gl >> 6)] = dbgStart; gDbgWave[3 * (gl >> 6) + 1] = dbgEnd; gDbgWave[3 * (gl >> 6) + 2] = dbgBusy; })
 	if (STATS || RTX_DBG) flushCounts(P, cnt);
 }

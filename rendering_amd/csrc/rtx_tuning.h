@@ -1,7 +1,8 @@
 // Compile-time tunables of the ray kernels (rtx_kernels.hip), all in one place.  Each can be overridden on the hipcc command
 // line (-DRTX_WAVES=6: tools/build_variants.sh builds such variants for A/B runs); the defaults are what the product ships.
-// Everything that used to be an experiment SWITCH (alternative walks, filters, stores ...) has been retired: the losing
-// branches are kept as a patch (tools/research/r04_experiment_branches.patch, DESIGN_HISTORY.md).
+// What is here is numeric (waves per SIMD, queue helpings, priorities, splits, leaf batches, SSAA spreads) or a diagnostic
+// (RTX_DBG, RTX_WAVE_TRACE).  Every experiment SWITCH (alternative walks, filters, stores ...) has been retired at its winning
+// value: rounds 2-4's losing branches are tools/research/r04_experiment_branches.patch, round 6's are in git history.
 #pragma once
 
 #ifndef RTX_DBG
@@ -45,40 +46,4 @@
 #endif
 #ifndef RTX_SSAA_SPREAD_PX
 #define RTX_SSAA_SPREAD_PX 4u   // pixels per wave for the tiles that were very slow in pass 1 (rtxSsaaCountKernel)
-#endif
-#ifndef RTX_BUNDLE_PAIRS
-#define RTX_BUNDLE_PAIRS 1      // makeBundle: 1 = waveMaxMin (two interleaved DPP chains per coordinate).  Rounds 2-4 shipped 0 without meaning to: the switch was
-#endif                          // tested (line 477) before it was defined (line 671) -- found when the switches were retired in round 5; A/B in profiles/r05_ab_*.txt
-#ifndef RTX_FAST_INVLEN
-#define RTX_FAST_INVLEN 1       // Vec3::normalize's (float)(1 / sqrt((double)len2)) through the exact fp32 fast path (rtx_kernels.hip, invLenD); 0 = always the fp64 expression
-#endif
-#ifndef RTX_SAME_ORIGIN
-#define RTX_SAME_ORIGIN 1       // makeBundle: bundles whose rays all start at the camera take their origin box as that point (no reductions over the origins)
-#endif
-#ifndef RTX_REC2_RELOAD
-#define RTX_REC2_RELOAD 1       // traceWave: the mesh's bundle-split constants are fetched again per bundle instead of living in SGPRs across the walk
-#endif
-#ifndef RTX_PRUNE_AXIS
-#define RTX_PRUNE_AXIS 1        // node visit: the prune / plane records of a wide node are evaluated with lanes = (record, axis) -- pruneEval8 -- instead of lanes = records (16 of 64 lanes)
-#endif
-#ifndef RTX_WIDE_NOCULL
-#define RTX_WIDE_NOCULL 1       // options::useBackfaceCulling = 0 takes the wide walk with prune records too (0: the stackless binary walk, as until round 5)
-#endif
-#ifndef RTX_FILTER_MASKS
-#define RTX_FILTER_MASKS 1      // bundle filter: verdicts as wave masks (a ballot per compare, combined on the scalar side) instead of bools (whose ballots compiled to v_cndmask + v_cmp)
-#endif
-#ifndef RTX_EXACT_HOIST
-#define RTX_EXACT_HOIST 1       // exact tests of a pass: "did a lane's t improve" is one compare after the survivors, not one per survivor (0: the per-survivor form, with its copies of t)
-#endif
-#ifndef RTX_ADVANCE_UNIFORM
-#define RTX_ADVANCE_UNIFORM 1   // castRay state machine: advance() steps all lanes in one loop with a uniform exit (finished lanes sit out) instead of per-lane returns
-#endif
-#ifndef RTX_ONE_ADVANCE
-#define RTX_ONE_ADVANCE 1       // castRayWave: advance() once per round, at its head (0: before the loop and at the end of every round -- two copies of its code)
-#endif
-#ifndef RTX_PRUNE_LANEK
-#define RTX_PRUNE_LANEK 1       // pruneEval8: a lane's two addresses (PruneBlock words, LDS axis record) packed in one register per walk instead of 12 VALU instructions per visit
-#endif
-#ifndef RTX_TILE_RECOMPUTE
-#define RTX_TILE_RECOMPUTE 1    // rtxPass1Kernel: a tile's pixel coordinates are derived from the list entry again after castRayWave (fresh parameters) instead of being kept across it
 #endif

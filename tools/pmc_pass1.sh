@@ -9,7 +9,9 @@ export RTX_ALLOW_ENV_KNOBS=1      # the product ignores RTX_* environment knobs 
 #     python bench.py --config <cfg> --steps 2 --warmup 1 --no-cpu-baseline
 # FETCH_SIZE and WRITE_SIZE cannot share a pass (TCC slots); the SQ counters fill two passes (the split of the wave-cycles --
 # SQ_WAIT_ANY = parked on s_waitcnt, SQ_WAIT_INST_ANY = ready but not issued, SQ_ACTIVE_INST_ANY = issuing -- and SQ_THREAD_CYCLES_VALU).
+# Every GPU run has a time limit of its own; the first that fails ends the script (nothing more is started on the card).
 # Usage: tools/pmc_pass1.sh <round tag, e.g. r05> [workloads, default: all]
+set -o pipefail
 TAG=${1:-r06}
 WLS=${2:-"headline cfg1 cfg2 cfg3 cfg4 cfg5 area"}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -17,11 +19,12 @@ OUT=$R/gpurun_out/pmc_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for cfg in $WLS; do
-  mode=$(python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "import json,sys; print('fused' if json.loads(sys.stdin.read())['config']['frame'].startswith('one') else 'split')")
+  mode=$(timeout -k 10 300 python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "import json,sys; print('fused' if json.loads(sys.stdin.read())['config']['frame'].startswith('one') else 'split')") || { echo "$cfg: bench run failed"; exit 1; }
   echo "$cfg $mode" >> $OUT/modes.txt
   for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "sq:SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY" "sq2:SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_THREAD_CYCLES_VALU SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_VMEM_WR" "tcc:TCC_HIT_sum TCC_MISS_sum"; do
     name=${pass%%:*}; cnt=${pass#*:}
-    RTX_FRAME_MODE=$mode rocprofv3 --pmc $cnt --output-format csv -d $OUT/$cfg/$name -o $name -- python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > $OUT/$cfg.$name.log 2>&1
+    RTX_FRAME_MODE=$mode timeout -k 10 300 rocprofv3 --pmc $cnt --output-format csv -d $OUT/$cfg/$name -o $name -- python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > $OUT/$cfg.$name.log 2>&1 \
+      || { echo "$cfg $name: rocprofv3 run failed (exit $?)"; tail -5 $OUT/$cfg.$name.log; exit 1; }
   done
 done
 cd $R
