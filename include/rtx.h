@@ -44,6 +44,11 @@ enum { RTX_LIGHT_DISTANT = 1, RTX_LIGHT_POINT = 2, RTX_LIGHT_AREA = 3 };
 
 #define RTX_FLAG_BACKFACE_CULL 1u /* options::useBackfaceCulling (options.h:27) */
 #define RTX_FLAG_SKYBOX 2u        /* options::useSkybox (options.h:32)          */
+/* options::showNormals (options.h:35), the normals debug view: castRay returns hitNormal / 2 + 0.5 at the first hit
+ * (scene.cpp:771-772) -- no light, material or recursion is evaluated; a miss still returns the skybox / background.  It applies
+ * to rtx_render_pass1, rtx_render_ssaa, rtx_render_frame (always in three launches), rtx_render_frame_host and
+ * rtx_cast_rays.  Counters are not collected in this view: with rtx_counters_enable on, the render calls fail. */
+#define RTX_FLAG_SHOW_NORMALS 4u
 
 /* Options + Camera, everything the workers read (options.h:9-20; scene.h:52-66; scene.cpp:447-457). */
 typedef struct rtx_view {
@@ -175,6 +180,18 @@ int rtx_render_ssaa(rtx_scene* scene, const uint8_t* mask_dev, uint32_t row_begi
  * bgr_dev: H*W*3 bytes (W % 4 == 0), 4-byte aligned; fb_dev 16-byte aligned.  Under rtx_set_row_ownership only the rows this
  * device owns are converted; the others are not touched (rtx_gather fills them on the root). */
 int rtx_quantize_bgr8(rtx_scene* scene, const float* fb_dev, uint8_t* bgr_dev, void* stream);
+
+/* The showAC heat map of Scene::render (scene.cpp:601-634): no pass 1 and no 4-ray pass; for EVERY pixel of the frame (the last row
+ * and column included) count = Scene::countAC(ray) (scene.cpp:659-669) = the sum over the meshes, in scene order, of
+ * AccelerationStructure::recCountAC (objects.cpp:572-585): the number of nodes whose box the ray passes (intersectBox,
+ * objects.cpp:536-570), a node being tested only when its parent's box passed.  The pixel's ray is
+ * camera.getRay((2 (x + 0.5) / W - 1) scale aspect, -(2 (y + 0.5) / H - 1) scale) -- 0.5 added once, not twice as in pass 1.
+ * fb_dev[x + y*W] = Vec3f{(float)count / (float)acMax}, acMax = the largest count of the frame: without a mesh, or when no ray
+ * meets one, every pixel is 0/0 = NaN as in the reference (rtx_quantize_bgr8 writes it as 255).
+ * counts_dev: H*W uint32 per-pixel counts, or NULL (a buffer of the scene is used); the maximum is theirs (the caller
+ * reads it from the counts).  Refused (RTX_ERR_ARG) under rtx_set_row_ownership with more than one part -- the normalisation
+ * needs the maximum of the whole frame -- and with counters enabled; the buffers are then not touched.  Asynchronous on `stream`. */
+int rtx_render_ac(rtx_scene* scene, float* fb_dev, uint32_t* counts_dev, void* stream);
 
 /* Convenience for hosts that hold a plain `Vec3f*`: pass 1 (+ optional Sobel/SSAA) into a host buffer;
  * allocates a device framebuffer internally and copies back (PCIe-inclusive). */

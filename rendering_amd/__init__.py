@@ -34,7 +34,7 @@ _host = None
 # every entry point declared in include/rtx.h (the boundary) and include/rtx_debug.h (probes, diagnostics, tuning hooks)
 RTX_SYMBOLS = [
     "rtx_last_error", "rtx_device_count", "rtx_scene_create", "rtx_scene_destroy", "rtx_scene_set_view", "rtx_scene_bytes",
-    "rtx_render_pass1", "rtx_sobel", "rtx_render_ssaa", "rtx_render_frame", "rtx_frame_status", "rtx_frame_mode", "rtx_set_frame_mode", "rtx_set_knob", "rtx_cost_grid_read", "rtx_mesh_flatten_probe", "rtx_wide_node_slots", "rtx_source_p_probe", "rtx_quantize_bgr8", "rtx_render_frame_host",
+    "rtx_render_pass1", "rtx_sobel", "rtx_render_ssaa", "rtx_render_frame", "rtx_render_ac", "rtx_frame_status", "rtx_frame_mode", "rtx_set_frame_mode", "rtx_set_knob", "rtx_cost_grid_read", "rtx_mesh_flatten_probe", "rtx_wide_node_slots", "rtx_source_p_probe", "rtx_quantize_bgr8", "rtx_render_frame_host",
     "rtx_counters_enable", "rtx_counters_reset", "rtx_counters_read", "rtx_last_kernel_ms", "rtx_math_probe",
     "rtx_cast_rays", "rtx_kernel_time_reset", "rtx_kernel_time_stats", "rtx_tile_cost_read", "rtx_set_row_ownership",
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
@@ -65,6 +65,7 @@ def load():
     rtx.rtx_sobel.argtypes = [vp, vp, u32, u32, vp, vp]
     rtx.rtx_render_ssaa.argtypes = [vp, vp, u32, u32, vp, vp]
     rtx.rtx_render_frame.argtypes = [vp, u32, u32, vp, vp, vp]
+    rtx.rtx_render_ac.argtypes = [vp, vp, vp, vp]
     rtx.rtx_frame_status.argtypes = [vp, C.POINTER(C.c_uint32)]
     rtx.rtx_set_frame_mode.argtypes = [vp, C.c_int]
     rtx.rtx_set_knob.argtypes = [vp, C.c_char_p, C.c_double]
@@ -377,6 +378,8 @@ class Scene:
         self.host.rah_camera_set(self.h, _np_ptr(pos), _np_ptr(rot))
 
     def set_flag(self, name, value):
+        """Pins one of the switches the render reads on this scene only: useBackfaceCulling, useSkybox, collectStatistics,
+        showNormals (the normals view) or showAC (the heat map of Scene::render; see render_ac)."""
         self.host.rah_set_flag(self.h, name.encode(), int(value))
 
     # ---- host-side structures (no GPU needed) -------------------------------------------------
@@ -388,7 +391,7 @@ class Scene:
         return np.float32(scale.value), np.float32(aspect.value), m, pos
 
     def view_flags(self):
-        """rtx_view::flags this scene uploads (bit 0 back-face culling, bit 1 skybox)."""
+        """rtx_view::flags this scene uploads (bit 0 back-face culling, bit 1 skybox, bit 2 the showNormals view)."""
         return self.host.rah_view_flags(self.h)
 
     def digest(self):
@@ -463,6 +466,13 @@ class Scene:
         r0, r1 = rows if rows is not None else (0, self.height)
         _check(self.rtx.rtx_render_frame(self.gpu(), r0, r1, C.c_void_p(fb.data_ptr()), C.c_void_p(mask.data_ptr()),
                                          self._stream_ptr(stream)), "rtx_render_frame")
+
+    def render_ac(self, fb, counts=None, stream=None):
+        """The showAC heat map (rtx_render_ac, Scene::render scene.cpp:601-634) into the device tensor fb (H,W,3 float32): every pixel
+        = its count of passed acceleration-structure boxes / the frame's largest count.  counts: optional device tensor of H*W
+        int32 / uint32 that receives the raw per-pixel counts (their max is the normaliser)."""
+        cp = C.c_void_p(counts.data_ptr()) if counts is not None else None
+        _check(self.rtx.rtx_render_ac(self.gpu(), C.c_void_p(fb.data_ptr()), cp, self._stream_ptr(stream)), "rtx_render_ac")
 
     def set_knob(self, name, value):
         """Experiment / test knob of this scene (include/rtx.h, rtx_set_knob); no knob changes a pixel."""

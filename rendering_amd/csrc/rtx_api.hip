@@ -171,6 +171,9 @@ struct rtx_scene {
 	                   uint64_t viewSerial = 0; uint32_t bandH = 0, nParts = 0, part = 0, halo = 0; };
 	LastFused lastFused;
 	uint32_t framesRecovered = 0;
+	// rtx_render_ac: per-pixel counts when the caller passes none, and the frame's maximum
+	uint32_t* acCounts = nullptr; size_t acCap = 0;
+	uint32_t* acMax = nullptr;
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
 	struct MeshLeaves { const float* boxes; uint32_t n; };      // 8 floats per non-empty leaf: true box lo, hi, reference count, -
@@ -958,6 +961,8 @@ void rtx_scene_destroy(rtx_scene* s)
 	if (s->orderedList) (void)hipFree(s->orderedList);
 	if (s->frameCtl) (void)hipFree(s->frameCtl);
 	if (s->ssaaPixels) (void)hipFree(s->ssaaPixels);
+	if (s->acCounts) (void)hipFree(s->acCounts);
+	if (s->acMax) (void)hipFree(s->acMax);
 	if (s->work) {
 		(void)hipFree(s->work); (void)hipFree(s->counters); (void)hipFree(s->orderWork);
 		for (int i = 0; i < 5; i++) for (hipEvent_t e : s->evPool[i]) (void)hipEventDestroy(e);
@@ -1265,6 +1270,52 @@ int prepareView(rtx_scene* s)
 	} while (0)
 #define RTX_COMMA ,
 
+namespace {
+
+// RTX_FLAG_SHOW_NORMALS: the view's pass 1 / 4-sample pass through rtxNormalsKernel.  Plain grids over the pixels: the tile lists, the
+// tile costs and the frame-mode measurements of the ordinary frames are neither used nor touched.
+bool showNormals(const rtx_scene* s) { return (s->params.view.flags & RTX_FLAG_SHOW_NORMALS) != 0; }
+
+int normalsPass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, hipStream_t st)
+{
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "the debug views collect no statistics (rtx_counters_enable)");
+	const uint32_t W = s->params.view.width, H = s->params.view.height;
+	Params p = s->params;
+	p.fb = fb_dev;
+	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
+	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
+	if (lastRow <= rowBegin) return RTX_OK;
+	p.tilesX = (W - 1 + 7) / 8;
+	p.tileRow0 = rowBegin / 8;
+	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
+	if (tiles >= (1u << 30)) return fail(RTX_ERR_ARG, "frame too large");
+	p.nTiles = (uint32_t)tiles;
+	int rc = stamp(s, 0, st);
+	if (rc) return rc;
+	hipLaunchKernelGGL(rtxNormalsKernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, 0);
+	HIPCHK(hipGetLastError());
+	return stamp(s, 0, st);
+}
+
+int normalsSsaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, hipStream_t st)
+{
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "the debug views collect no statistics (rtx_counters_enable)");
+	const uint32_t W = s->params.view.width;
+	Params p = s->params;
+	p.fb = fb_dev;
+	p.ssaaMask = mask_dev;
+	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
+	const size_t waves = ((size_t)(rowEnd - rowBegin) * W + 15) / 16;
+	if (waves >= (1ull << 32)) return fail(RTX_ERR_ARG, "frame too large");
+	int rc = stamp(s, 2, st);
+	if (rc) return rc;
+	hipLaunchKernelGGL(rtxNormalsKernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, p, 1);
+	HIPCHK(hipGetLastError());
+	return stamp(s, 2, st);
+}
+
+} // namespace
+
 int rtx_render_pass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, void* stream)
 {
 	RoctxRange range("Render scene (rtx_render_pass1)");
@@ -1276,6 +1327,7 @@ int rtx_render_pass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (int ro = renderOn(s, st)) return ro;
+	if (showNormals(s)) return normalsPass1(s, rowBegin, rowEnd, fb_dev, st);
 	Params p = s->params;
 	p.fb = fb_dev;
 	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
@@ -1451,6 +1503,15 @@ int rtx_render_frame(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (int ro = renderOn(s, st)) return ro;
+	if (showNormals(s)) {
+		// the debug view in three launches, outside the measurements and tile lists of the ordinary frames
+		s->lastFused.valid = false;
+		if ((rc = stamp(s, 3, st))) return rc;
+		if ((rc = renderFrameSplit(s, rowBegin, rowEnd, fb_dev, mask_dev, stream))) { if (s->evUsed[3] & 1) s->evUsed[3]--; return rc; }
+		if ((rc = stamp(s, 3, st))) return rc;
+		s->lastFrameMode = 0;
+		return RTX_OK;
+	}
 	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);
 	rtx_scene::TileQueues* tq = nullptr;
 	if (lastRow > rowBegin) {
@@ -1645,6 +1706,7 @@ int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, ui
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (int ro = renderOn(s, st)) return ro;
+	if (showNormals(s)) return normalsSsaa(s, mask_dev, rowBegin, rowEnd, fb_dev, st);
 	// (work[1], the queue head, and work[10], the slot budget used, are zeroed by rtxSsaaScatterKernel; [8], [9]: the layout
 	// decision and its count, see below)
 	if ((uint32_t)s->tileCap < s->params.tilesXFull * ((H + 7) / 8) || W > 0xffffu || H > 0xffffu) return fail(RTX_ERR_ARG, "frame too large for the SSAA pixel list");
@@ -1727,6 +1789,40 @@ int rtx_render_frame_host(rtx_scene* s, int with_ssaa, float* fb_host)
 		if ((rc = rtx_render_ssaa(s, (const uint8_t*)mask.p, 0, H, (float*)fb.p, nullptr))) return rc;
 	}
 	HIPCHK(hipMemcpy(fb_host, fb.p, bytes, hipMemcpyDeviceToHost));
+	return RTX_OK;
+}
+
+int rtx_render_ac(rtx_scene* s, float* fb_dev, uint32_t* counts_dev, void* stream)
+{
+	RoctxRange range("Render AC heat map (rtx_render_ac)");
+	if (!s || !fb_dev) return fail(RTX_ERR_ARG, "scene/fb is NULL");
+	if (s->params.bandH != 0 && s->params.nParts > 1) return fail(RTX_ERR_ARG, "rtx_render_ac: the heat map is normalised by the maximum of the whole frame -- not under row ownership with more than one part");
+	if (s->stats) return fail(RTX_ERR_ARG, "rtx_render_ac: the debug views collect no statistics (rtx_counters_enable)");
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	const uint32_t W = s->params.view.width, H = s->params.view.height;
+	const size_t px = (size_t)W * H;
+	const size_t waves = (size_t)((W + 7) / 8) * ((H + 7) / 8);
+	if (waves >= (1ull << 32)) return fail(RTX_ERR_ARG, "frame too large");
+	if (!s->acMax) HIPCHK(hipMalloc((void**)&s->acMax, sizeof(uint32_t)));
+	uint32_t* counts = counts_dev;
+	if (!counts) {
+		if (s->acCap < px) {
+			HIPCHK(hipDeviceSynchronize());
+			if (s->acCounts) HIPCHK(hipFree(s->acCounts));
+			s->acCounts = nullptr; s->acCap = 0;
+			HIPCHK(hipMalloc((void**)&s->acCounts, px * sizeof(uint32_t)));
+			s->acCap = px;
+		}
+		counts = s->acCounts;
+	}
+	hipStream_t st = (hipStream_t)stream;
+	if (int ro = renderOn(s, st)) return ro;
+	HIPCHK(hipMemsetAsync(s->acMax, 0, sizeof(uint32_t), st));
+	hipLaunchKernelGGL(rtxAcCountKernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, s->params, counts, s->acMax);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(rtxAcNormalizeKernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, (const uint32_t*)counts, (const uint32_t*)s->acMax, fb_dev, px);
+	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
 
@@ -1977,7 +2073,8 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 	uint32_t blocks = (uint32_t)s->blocksPass1;
 	const uint32_t need = ((n + 63) / 64 + 3) / 4;
 	if (blocks > need) blocks = need;
-	hipLaunchKernelGGL(rtxProbeKernel, dim3(blocks), dim3(256), 0, nullptr, p);
+	if (showNormals(s)) hipLaunchKernelGGL(rtxNormalsKernel, dim3(need), dim3(256), 0, nullptr, p, 2);
+	else hipLaunchKernelGGL(rtxProbeKernel, dim3(blocks), dim3(256), 0, nullptr, p);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 32, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(colours, dc.p, (size_t)n * 12, hipMemcpyDeviceToHost));

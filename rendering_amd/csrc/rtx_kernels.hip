@@ -2873,3 +2873,182 @@ template __global__ void rtxSsaaKernel<false, true, B, C, true>(const Params);  
 template __global__ void rtxFrameKernel<true, B, C, true>(const Params);
 RTX_PLAIN_INSTANCES(true, 1) RTX_PLAIN_INSTANCES(false, 1) RTX_PLAIN_INSTANCES(true, 0) RTX_PLAIN_INSTANCES(false, 0)
 #undef RTX_PLAIN_INSTANCES
+
+// ------------------------------------------------------------------------------------------------
+// The reference's two debug views (options::showNormals, options::showAC).  Kernels of their own: none of the kernels above
+// carries a branch for them.
+// ------------------------------------------------------------------------------------------------
+// showNormals (scene.cpp:758-775): castRay stops after getSurfaceData at the first hit and returns hitNormal / 2 + 0.5 -- no
+// light, no material, no recursion.  A miss returns getSkybox(dir), and so does depth 0 > maxRayDepth (scene.cpp:760).
+__device__ __forceinline__ V3 normalsCast(const Params& P, bool valid, V3 o, V3 d, uint32_t src, Hit& h)
+{
+	Counts cnt = {};
+	traceWave<false, true, false, true, -1>(P, valid, false, o, d, kFltMax, h, cnt, src);
+	V3 c = mk(0, 0, 0);
+	if (!valid) return c;
+	if (P.view.maxDepth < 0 || h.obj < 0) return skyColor(P, d);
+	Lane s;
+	s.ro = o; s.rd = d;
+	shadePrimary(P, s, h);        // (only the lanes that hit are here: its loop is over their objects)
+	return s.N / 2.0f + mk(0.5f, 0.5f, 0.5f);
+}
+
+// mode 0: pass 1 of the view (renderWorker, scene.cpp:444-468): one 8x8 tile per wave, the pixels x < W-1, y < H-1 of rows [rowBegin, rowEnd)
+//         that this part renders; tiles [tileRow0 * tilesX, +nTiles).
+// mode 1: the 4-sample pass (SSAAworker, scene.cpp:508-540): 16 pixels per wave (4 lanes = the 4 sub-samples), every pixel of rows
+//         [rowBegin, rowEnd) owned by this part with a mask entry != 0, replaced by the mean of its samples.
+// mode 2: probe rays (rtx_cast_rays): hits and colours.
+__global__ void __launch_bounds__(256) rtxNormalsKernel(const Params P, int mode)
+{
+	const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
+	const uint32_t W = P.view.width, H = P.view.height;
+	Hit h;
+	if (mode == 0) {
+		if (wave >= P.nTiles) return;
+		const uint32_t tx = wave % P.tilesX, ty = P.tileRow0 + wave / P.tilesX;
+		const uint32_t x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+		const bool valid = x < W - 1 && y < H - 1 && y >= P.rowBegin && y < P.rowEnd && rowRendered(P, y);
+		if (ballot(valid) == 0) return;
+		V3 o, d;
+		primaryRay(P, (float)x + 0.5f, (float)y + 0.5f, o, d);
+		const V3 c = normalsCast(P, valid, o, d, 1u, h);
+		if (valid) { float* px = P.fb + ((size_t)y * W + x) * 3; px[0] = c.x; px[1] = c.y; px[2] = c.z; }
+	}
+	else if (mode == 1) {
+		const size_t first = (size_t)P.rowBegin * W + (size_t)wave * 16, end = (size_t)P.rowEnd * W;
+		if (first >= end) return;
+		const size_t i = first + (lane >> 2);
+		const uint32_t sub = lane & 3;
+		const uint32_t y = (uint32_t)(i / W), x = (uint32_t)(i - (size_t)y * W);
+		const bool valid = i < end && x < W - 1 && y < H - 1 && rowOwned(P.bandH, P.nParts, P.part, y) && P.ssaaMask[i] != 0;
+		if (ballot(valid) == 0) return;
+		// offsets in the reference's order: (.25,.25) (.25,.75) (.75,.25) (.75,.75)  (scene.cpp:527-534)
+		const float fx = (float)x + ((sub & 2) ? 0.75f : 0.25f), fy = (float)y + ((sub & 1) ? 0.75f : 0.25f);
+		V3 o, d;
+		primaryRay(P, fx, fy, o, d);
+		const V3 c = normalsCast(P, valid, o, d, 1u, h);
+		// color = 0; color += c0; += c1; += c2; += c3; fb = color / 4
+		const int base = (int)(lane & ~3u);
+		V3 sum = mk(0, 0, 0);
+		for (int k = 0; k < 4; ++k)
+			sum = sum + mk(__shfl(c.x, base + k), __shfl(c.y, base + k), __shfl(c.z, base + k));
+		if (valid && sub == 0) { float* px = P.fb + i * 3; px[0] = sum.x / 4; px[1] = sum.y / 4; px[2] = sum.z / 4; }
+	}
+	else {
+		const uint32_t i = wave * 64 + lane;
+		if (wave * 64 >= P.nProbe) return;
+		const bool valid = i < P.nProbe;
+		V3 o = mk(0, 0, 0), d = mk(0, 0, -1);
+		if (valid) { o = load3(P.probeRays + (size_t)i * 6); d = load3(P.probeRays + (size_t)i * 6 + 3); }
+		const V3 c = normalsCast(P, valid, o, d, 0u, h);
+		if (valid) {
+			float* out = P.probeHits + (size_t)i * 8;
+			const bool hit = h.obj >= 0;      // (the hit record of rtxProbeKernel)
+			const bool mesh = hit && P.objects[hit ? h.obj : 0].type == 3;
+			out[0] = hit ? 1.f : 0.f; out[1] = hit ? (float)h.obj : -1.f; out[2] = mesh ? (float)h.tri : -1.f;
+			out[3] = h.t; out[4] = hit ? h.u : -1.f; out[5] = hit ? h.v : -1.f; out[6] = 0; out[7] = 0;
+			float* pc = P.probeColours + (size_t)i * 3; pc[0] = c.x; pc[1] = c.y; pc[2] = c.z;
+		}
+	}
+}
+
+// showAC (Scene::render, scene.cpp:601-634): per pixel, sum over the meshes in scene order of recCountAC(root) (objects.cpp:572-585) =
+// the number of nodes whose box the pixel's ray passes, a node being tested only when its parent passed.  The ray is
+// camera.getRay((2 (x + 0.5) / W - 1) scale aspect, -(2 (y + 0.5) / H - 1) scale): 0.5 added ONCE (renderWorker adds it twice).
+// One 8x8 tile per wave over the binary pre-order nodes (the wide nodes skip the levels in between: they cannot count them).
+// The node index is wave-uniform; a lane takes part at node i iff i >= resume, where resume is the skip of the last node whose
+// box it failed.  A lane that fails node i sets resume = skip(i); the wave goes on at i + 1 when a taking-part lane passed an inner
+// node, else at skip(i) -- exact, because a lane sitting out has resume = the skip of an ancestor of i, which is >= skip(i).
+// The box test is the reference's intersectBox (objects.cpp:536-570): the sequential form, or the min / max form where that is
+// exact (rtxd::Mesh::boxesRegular and a finite 1 / dir and origin for every ray of the wave: see traceWave).
+template <bool REGULAR>
+__device__ __forceinline__ uint32_t countWalk(const Node* nodes, uint32_t n, bool valid, const V3& o, float ix, float iy, float iz)
+{
+	const bool sx = ix < 0, sy = iy < 0, sz = iz < 0;
+	uint32_t count = 0, resume = valid ? 0u : n;
+	for (uint32_t i = 0; i < n;) {
+		const u32x8 nd = sload8(nodes + i);
+		const bool on = i >= resume;
+		bool fail;
+		if (REGULAR) fail = boxFailsRegular(F(nd[0]), F(nd[1]), F(nd[2]), F(nd[3]), F(nd[4]), F(nd[5]), o, ix, iy, iz);
+		else {
+			const float xlo = (F(nd[0]) - o.x) * ix, xhi = (F(nd[1]) - o.x) * ix, ylo = (F(nd[2]) - o.y) * iy, yhi = (F(nd[3]) - o.y) * iy;
+			float tmin = sx ? xhi : xlo, tmx = sx ? xlo : xhi;
+			const float tymin = sy ? yhi : ylo, tymax = sy ? ylo : yhi;
+			fail = (tmin > tymax) || (tymin > tmx);
+			if (tymin > tmin) tmin = tymin;
+			if (tymax < tmx) tmx = tymax;
+			const float zlo = (F(nd[4]) - o.z) * iz, zhi = (F(nd[5]) - o.z) * iz;
+			const float tzmin = sz ? zhi : zlo, tzmax = sz ? zlo : zhi;
+			fail = fail || (tmin > tzmax) || (tzmin > tmx);
+		}
+		const int32_t link = (int32_t)nd[6];
+		const bool inner = link > 0;
+		if (on && !fail) count++;
+		if (on && fail && inner) resume = (uint32_t)link;
+		i = (inner && ballot(on && !fail) == 0) ? (uint32_t)link : i + 1;
+		i = uni(i);
+	}
+	return count;
+}
+
+__device__ __forceinline__ void acRay(const Params& P, uint32_t x, uint32_t y, V3& o, V3& d)
+{
+	// scene.cpp:616-619 (0.5 added once) and Camera::getRay, scene.cpp:52-53 -- the same getRay as primaryRay's
+	const float w = (float)P.view.width, hgt = (float)P.view.height;
+	const float xp = (2 * ((float)x + 0.5f) / w - 1) * P.view.scale * P.view.aspect;
+	const float yp = -(2 * ((float)y + 0.5f) / hgt - 1) * P.view.scale;
+	const V3 s = normalized(mk(xp, yp, -1));
+	const float* M = P.view.camM;
+	V3 r;
+	r.x = s.x * M[0] + s.y * M[4] + s.z * M[8] + M[12];
+	r.y = s.x * M[1] + s.y * M[5] + s.z * M[9] + M[13];
+	r.z = s.x * M[2] + s.y * M[6] + s.z * M[10] + M[14];
+	const float ww = s.x * M[3] + s.y * M[7] + s.z * M[11] + M[15];
+	if (ww != 0.0f && ww != 1.0f) { const float wi = 1.0f / ww; r.x *= wi; r.y *= wi; r.z *= wi; }   // geometry.h:300-305
+	o = mk(P.view.camPos[0], P.view.camPos[1], P.view.camPos[2]);
+	d = r;
+}
+
+// Counts of every pixel of the frame (the last row and column included) into counts[x + y W], and their maximum into *acMax
+// (one atomicMax per wave; *acMax is zeroed before the launch).
+__global__ void __launch_bounds__(256) rtxAcCountKernel(const Params P, uint32_t* __restrict__ counts, uint32_t* __restrict__ acMax)
+{
+	const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
+	const uint32_t W = P.view.width, H = P.view.height;
+	const uint32_t tilesX = (W + 7) / 8;
+	if (wave >= tilesX * ((H + 7) / 8)) return;
+	const uint32_t x = (wave % tilesX) * 8 + (lane & 7), y = (wave / tilesX) * 8 + (lane >> 3);
+	const bool valid = x < W && y < H;
+	V3 o, d;
+	acRay(P, x, y, o, d);
+	const float ix = 1 / d.x, iy = 1 / d.y, iz = 1 / d.z;      // (objects.cpp:543)
+	const bool laneRegular = fabsf(ix) < __builtin_inff() && fabsf(iy) < __builtin_inff() && fabsf(iz) < __builtin_inff() &&
+	                         fabsf(o.x) < 0x1p100f && fabsf(o.y) < 0x1p100f && fabsf(o.z) < 0x1p100f;
+	const bool waveRegular = ballot(valid && !laneRegular) == 0;
+	uint32_t count = 0;
+	const uint32_t nObj = uni(P.nObjects);
+	for (uint32_t oi = 0; oi < nObj; oi = uni(oi + 1)) {      // Scene::countAC: the meshes in scene order (scene.cpp:659-669)
+		const Object* ob = uni(P.objects + oi);
+		if ((int)sload1(&ob->type) != 3) continue;
+		const Node* nodes = (const Node*)sloadp(&ob->nodes);
+		const uint32_t n = sload1(&ob->nNodes);
+		if (n == 0 || nodes == nullptr) continue;
+		const bool regular = (sload1(&ob->meshFlags) & 2u) != 0;
+		if (regular && waveRegular) count += countWalk<true>(nodes, n, valid, o, ix, iy, iz);
+		else count += countWalk<false>(nodes, n, valid, o, ix, iy, iz);
+	}
+	if (valid) counts[(size_t)y * W + x] = count;
+	uint32_t m = valid ? count : 0u;
+	for (int k = 32; k >= 1; k >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)m, k); m = other > m ? other : m; }
+	if (lane == 0 && m != 0) atomicMax(acMax, m);
+}
+
+// fb = Vec3f{(float)count / (float)acMax} (scene.cpp:627-632): IEEE division, so acMax = 0 gives 0 / 0 = NaN everywhere, as in the reference.
+__global__ void __launch_bounds__(256) rtxAcNormalizeKernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ acMax, float* __restrict__ fb, size_t n)
+{
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float v = (float)counts[i] / (float)(int)*acMax;
+	fb[i * 3] = v; fb[i * 3 + 1] = v; fb[i * 3 + 2] = v;
+}

@@ -25,10 +25,10 @@ inline bool collectStatistics = false;
 inline bool enableOutput = true;
 inline bool imageOutput = true;
 inline bool useAC = true;       // the GPU path always walks the acceleration structure (useAC=0 is a debug quirk, out of scope)
-inline bool showAC = false;     // debug heat-map, out of scope
+inline bool showAC = false;     // debug heat map of the acceleration structures (Scene::render -> rtx_render_ac)
 inline bool useSkybox = false;
 inline bool useTextures = true;
-inline bool showNormals = false; // debug mode, out of scope
+inline bool showNormals = false; // debug view of the first hit's normal (RTX_FLAG_SHOW_NORMALS)
 inline bool enableSSAA = true;
 // Where Mesh::loadOBJ builds the acceleration structure: -1 = decide on first use (the device if one is visible,
 // environment RENDERING_AMD_AC_BUILD=host|device overrides), 0 = host builder, 1 = rtx_bvh_build on the device.

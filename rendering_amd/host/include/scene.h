@@ -80,13 +80,19 @@ public:
 	void attachComm(rtx_comm* comm, int nRanks, int rank);
 	double lastPass1Ms = 0, lastSobelMs = 0, lastSsaaMs = 0, lastFrameMs = 0;      // (lastFrameMs: the whole of render(), rtx_render_frame)
 	// The switches the render reads are process-global in the reference (options::useBackfaceCulling, useSkybox,
-	// collectStatistics).  A host that keeps several scenes alive (the C API in capi.cpp) pins them per scene here:
-	// -1 = follow the global (the reference's behaviour), 0 / 1 = this scene's own value.
-	int useBackfaceCulling = -1, useSkybox = -1, collectStatistics = -1;
+	// collectStatistics, and the debug views showNormals / showAC).  A host that keeps several scenes alive (the C API in capi.cpp) pins them
+	// per scene here: -1 = follow the global (the reference's behaviour), 0 / 1 = this scene's own value.
+	int useBackfaceCulling = -1, useSkybox = -1, collectStatistics = -1, showNormals = -1, showAC = -1;
 	bool cullingOn() const { return useBackfaceCulling < 0 ? options::useBackfaceCulling : useBackfaceCulling != 0; }
 	bool skyboxOn() const { return useSkybox < 0 ? options::useSkybox : useSkybox != 0; }
 	bool statisticsOn() const { return collectStatistics < 0 ? options::collectStatistics : collectStatistics != 0; }
-	void pinFlags() { useBackfaceCulling = options::useBackfaceCulling; useSkybox = options::useSkybox; collectStatistics = options::collectStatistics; }
+	bool normalsOn() const { return showNormals < 0 ? options::showNormals : showNormals != 0; }
+	bool acOn() const { return showAC < 0 ? options::showAC : showAC != 0; }
+	void pinFlags()
+	{
+		useBackfaceCulling = options::useBackfaceCulling; useSkybox = options::useSkybox; collectStatistics = options::collectStatistics;
+		showNormals = options::showNormals; showAC = options::showAC;
+	}
 
 private:
 	struct DeviceFrame;
@@ -94,6 +100,7 @@ private:
 	void pass1OnDevice();
 	void ssaaOnDevice();
 	void readTimes();
+	void renderAC();
 	rtx_scene* gpu_ = nullptr;
 	bool viewDirty_ = true;
 	std::unique_ptr<DeviceFrame> frame_;

@@ -79,6 +79,8 @@ void rah_set_flag(void* h, const char* name, int v)
 	if (!strcmp(name, "useBackfaceCulling")) s->useBackfaceCulling = v != 0;
 	else if (!strcmp(name, "collectStatistics")) s->collectStatistics = v != 0;
 	else if (!strcmp(name, "useSkybox")) s->useSkybox = v != 0;
+	else if (!strcmp(name, "showNormals")) s->showNormals = v != 0;
+	else if (!strcmp(name, "showAC")) s->showAC = v != 0;
 	s->invalidateView();
 }
 

@@ -27,6 +27,12 @@ int renderRank(const std::string& path, int nRanks, int rank, const unsigned cha
 		options::acBuildDevice = rank;          // the acceleration structure is built on this rank's own GPU
 		Scene scene(path);
 		if (rank != 0) options::enableOutput = false;      // (scene files may switch it back on)
+		// (every rank reads the same file, so every rank stops here and none is left waiting for the others' rows)
+		if (nRanks > 1 && scene.acOn()) {
+			if (rank == 0) std::fprintf(stderr, "--gpus %d: showAC renders on one GPU only (the heat map is normalised by the maximum of the whole frame); run without --gpus\n", nRanks);
+			rtx_comm_destroy(comm);
+			return 2;
+		}
 		scene.device = rank;
 		scene.attachComm(comm, nRanks, rank);
 		scene.render();

@@ -357,7 +357,7 @@ void fillView(Scene& sc, rtx_view& v)
 	v.width = (uint32_t)sc.options.width; v.height = (uint32_t)sc.options.height;
 	v.bias = sc.options.bias; v.max_ray_depth = sc.options.maxRayDepth;
 	put3(v.background, sc.options.backgroundColor);
-	v.flags = (sc.cullingOn() ? RTX_FLAG_BACKFACE_CULL : 0u) | (sc.skyboxOn() ? RTX_FLAG_SKYBOX : 0u);
+	v.flags = (sc.cullingOn() ? RTX_FLAG_BACKFACE_CULL : 0u) | (sc.skyboxOn() ? RTX_FLAG_SKYBOX : 0u) | (sc.normalsOn() ? RTX_FLAG_SHOW_NORMALS : 0u);
 	put3(v.cam_pos, sc.camera.pos);
 	for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) v.cam_matrix[i * 4 + j] = sc.camera.rMatrix[i][j];
 	v.scale = tanf(sc.camera.fov * 0.5f / 180.0f * (float)(3.14159265358979323846));   // scene.cpp:447
@@ -622,12 +622,49 @@ static uint32_t bandHeight(uint32_t height, uint32_t nParts)
 	return b < 64u ? 64u : (b > 256u ? 256u : b);
 }
 
+// The showAC branch of Scene::render (scene.cpp:607-633): the heat map of the whole frame (rtx_render_ac), then saveImage.
+void Scene::renderAC()
+{
+	if (comm_ && nRanks_ > 1) {
+		std::cout << "showAC: the heat map is normalised by the maximum of the whole frame and is rendered on one GPU only\n";
+		noteError("showAC with more than one rank");
+		LOG_ERROR();
+	}
+	if (statisticsOn()) {
+		std::cout << "showAC: statistics are not collected in the debug views\n";
+		noteError("showAC with collectStatistics");
+		LOG_ERROR();
+	}
+	rtx_scene* g = gpu();
+	DeviceFrame& d = deviceFrame();
+	{
+		Timer tp("Render AC heat map");
+		gpuCheck(rtx_render_ac(g, d.fb, nullptr, nullptr), "rtx_render_ac");
+		hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
+	}
+	if (options::imageOutput) {
+		if (options.width % 4 != 0) { std::cout << "saveImage is only defined for width % 4 == 0 (util.cpp:28-29)\n"; LOG_ERROR(); }
+		gpuCheck(rtx_quantize_bgr8(g, d.fb, d.bgr, nullptr), "rtx_quantize_bgr8");
+		std::vector<unsigned char> bgr(options.width * options.height * 3);
+		hipCheck(hipMemcpy(bgr.data(), d.bgr, bgr.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+		saveImageBGR(bgr.data(), options);
+	}
+	if (options::enableOutput) std::cout << '\n';
+}
+
 void Scene::render()
 {
 	if (!sceneLoadSuccess) return;
 	Timer t("Total time");
-	if (options::showAC || options::showNormals || !options::useAC) {
-		std::cout << "showAC / showNormals / useAC=0 are debug modes outside the accelerated hot path\n";
+	if (!options::useAC) {
+		std::cout << "useAC=0 (every box test forced to pass) is a debug mode outside the accelerated hot path\n";
+		LOG_ERROR();
+	}
+	// showAC first, as in the reference (scene.cpp:601); showNormals is a flag of the view (fillView) and takes the ordinary path
+	if (acOn()) { renderAC(); return; }
+	if (normalsOn() && statisticsOn()) {
+		std::cout << "showNormals: statistics are not collected in the debug views\n";
+		noteError("showNormals with collectStatistics");
 		LOG_ERROR();
 	}
 	rtx_scene* g = gpu();
