@@ -8,8 +8,14 @@ reflect/refract and SSAA rays; rays/frame is counted once by the instrumented ke
 Of these, `moot_shadow_rays` are shadow rays whose answer cannot influence the pixel (Diffuse surface turned away from
 the light: vis * max(0, N.-L) is +0 either way); the timed kernels do not walk them, the frame is bit-identical.
 N > 1: rows are dealt to the ranks in bands of 64 to 256 rows (rendering_amd/parallel.py band_height), every frame ends
-with an RCCL gather to rank 0 (rtx_gather; strong scaling of the same frame), and after the timed region the gathered
-image is compared with the frame rank 0 renders alone (--no-verify skips that).  Prints ONE JSON line on rank 0.
+with an RCCL gather to rank 0 (rtx_gather; strong scaling of the same frame), and with --full, after the timed region the
+gathered image is compared with the frame rank 0 renders alone (--no-verify skips that).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: it loads the scene, counts the rays of one frame, warms up, times the steps,
+writes --dump-outputs and prints the line.  --full also measures and checks everything else, after the timed region: the
+CPU baselines (the reference and the oracle port, with the whole-frame comparison against the reference; --no-cpu-baseline
+skips them), the first frames of fresh scenes and of a new view (N = 1), and the serial frame latency and the gathered-image
+check (N > 1).  The fields of what a run did not measure are null, and cpu_baseline is left out.
 """
 import argparse
 import subprocess
@@ -356,10 +362,13 @@ def main():
     ap.add_argument("--scene", default=None)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check what the headline does not need: CPU baselines and the whole-frame comparison with "
+                         "the reference, first frames of fresh scenes and of a new view (N = 1), frame latency and the gathered-image check (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-ssaa", action="store_true")
-    ap.add_argument("--verify", dest="verify", action="store_true", default=True,
-                    help="N > 1 (default): after the timed region rank 0 also renders the whole frame alone and compares the gathered image with it")
+    ap.add_argument("--verify", dest="verify", action="store_true", default=None,
+                    help="N > 1 (default with --full): after the timed region rank 0 also renders the whole frame alone and compares the gathered image with it")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--pipelined", action="store_true",
                     help="N = 1: after the timed region also measure a SEQUENCE of frames with the SSAA launch of frame k beside pass 1 of frame k + 1 (two streams, two "
@@ -372,6 +381,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.verify is None:
+        args.verify = args.full
     cscene, cw, ch = CONFIGS[args.config]
     custom = bool(args.scene or args.width or args.height or args.no_ssaa)
     args.scene = args.scene or cscene
@@ -556,10 +567,10 @@ def main():
             dumped = dump_outputs(args.dump_outputs, {"framebuffer": fb, "ssaa_mask": mask} if ssaa else {"framebuffer": fb})
 
     # N > 1: what the timed region measured is THROUGHPUT when the exchange of frame k runs beside the rendering of frame k + 1 (the default); the LATENCY of one
-    # frame -- render this rank's rows, quantise, gather on the render stream, wait -- is measured here, frame by frame (max over the ranks)
+    # frame -- render this rank's rows, quantise, gather on the render stream, wait -- is measured here with --full, frame by frame (max over the ranks)
     frame_latency_ms = None
     gather_ms_rank = 0.0
-    if world > 1:
+    if world > 1 and args.full:
         def one_frame_serial():
             parallel.shard_frame(scene, fb, mask, world, rank, ssaa=ssaa, clear=False)
             scene.quantize(fb, img)
@@ -661,9 +672,9 @@ def main():
     # order its queues by (the reference's use case is one frame per process)
     # The GPU has been idle while the host loaded that scene, and its clocks need a few milliseconds to come back: a second
     # fresh scene is timed (HIP events) directly behind three frames of the warm one -- what the first frame costs in software
-    # (no measured tile costs: the estimate of rtx_scene_create orders and splits it; tools/cold_probe.py).
+    # (no measured tile costs: the estimate of rtx_scene_create orders and splits it; tools/cold_probe.py).  --full only.
     cold_ms = cold_busy_ms = set_view_ms = new_view_host_ms = new_view_frame_ms = new_view_device_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         scene2 = load_scene()
         torch.cuda.synchronize()
         tc = time.perf_counter()
@@ -765,7 +776,7 @@ def main():
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s @%dx%d, pass 1%s" % (os.path.basename(args.scene), W, H, " + Sobel-adaptive SSAA" if ssaa else ""),
-                   "name": args.config, "flags": flags or None,
+                   "name": args.config, "flags": flags or None, "full": args.full,
                    "rays_per_frame": rays_per_frame, "moot_shadow_rays": int(tot[3]),
                    "walked_rays_per_frame": walked, "counted_mrays_s": round(rays_per_frame * args.steps / dt / 1e6, 3),
                    "parallelism": "rows in %d-row bands over %d GPU(s)%s" % (parallel.band_height(H, world), world, ", BGR8 bands collected on rank 0" if world > 1 else ""),
@@ -799,7 +810,7 @@ def main():
         out["config"]["gathered_image_equals_single_gpu_image"] = verified
     if dumped is not None:
         out["config"]["dumped_outputs"] = dumped
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.scene, W, H, scene, flags=flags)
         par = (out["cpu_baseline"] or {}).get("parity")
         if par:      # the reference's own framebuffers of this very frame against the product path's (reference_baseline)

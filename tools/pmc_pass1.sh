@@ -6,7 +6,7 @@ export RTX_ALLOW_ENV_KNOBS=1      # the product ignores RTX_* environment knobs 
 # configuration has a stamped roofline; rounds 2-4 had headline + cfg2 only).  The way the frame is rendered is fixed (RTX_FRAME_MODE) to what
 # rtx_render_frame settles on without a profiler attached: one un-profiled bench run per workload asks it first.
 # Per workload five rocprofv3 --pmc passes (counters only, no trace domains: gpurun refuses the combination) of
-#     python bench.py --config <cfg> --steps 2 --warmup 1 --no-cpu-baseline
+#     python bench.py --config <cfg> --steps 2 --warmup 1 --full --no-cpu-baseline
 # FETCH_SIZE and WRITE_SIZE cannot share a pass (TCC slots); the SQ counters fill two passes (the split of the wave-cycles --
 # SQ_WAIT_ANY = parked on s_waitcnt, SQ_WAIT_INST_ANY = ready but not issued, SQ_ACTIVE_INST_ANY = issuing -- and SQ_THREAD_CYCLES_VALU).
 # Every GPU run has a time limit of its own; the first that fails ends the script (nothing more is started on the card).
@@ -23,7 +23,7 @@ for cfg in $WLS; do
   echo "$cfg $mode" >> $OUT/modes.txt
   for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "sq:SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY" "sq2:SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_THREAD_CYCLES_VALU SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_VMEM_WR" "tcc:TCC_HIT_sum TCC_MISS_sum"; do
     name=${pass%%:*}; cnt=${pass#*:}
-    RTX_FRAME_MODE=$mode timeout -k 10 300 rocprofv3 --pmc $cnt --output-format csv -d $OUT/$cfg/$name -o $name -- python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > $OUT/$cfg.$name.log 2>&1 \
+    RTX_FRAME_MODE=$mode timeout -k 10 300 rocprofv3 --pmc $cnt --output-format csv -d $OUT/$cfg/$name -o $name -- python $R/bench.py --config $cfg --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/$cfg.$name.log 2>&1 \
       || { echo "$cfg $name: rocprofv3 run failed (exit $?)"; tail -5 $OUT/$cfg.$name.log; exit 1; }
   done
 done
@@ -35,7 +35,7 @@ from srchash import source_hash
 out, tag = sys.argv[1], sys.argv[2]
 modes = dict(l.split() for l in open(out + "/modes.txt"))
 res = {"source_hash": source_hash(),
-       "command": "RTX_ALLOW_ENV_KNOBS=1 RTX_FRAME_MODE=<split|fused> rocprofv3 --pmc <counters> -- python bench.py --config <workload> --steps 2 --warmup 1 --no-cpu-baseline",
+       "command": "RTX_ALLOW_ENV_KNOBS=1 RTX_FRAME_MODE=<split|fused> rocprofv3 --pmc <counters> -- python bench.py --config <workload> --steps 2 --warmup 1 --full --no-cpu-baseline",
        "units": "per launch (average over the dispatches of the kernel); FETCH_SIZE / WRITE_SIZE in KB as reported; SQ_*_CYCLES in quad-cycles",
        "workloads": {}}
 for cfg, m in modes.items():

@@ -6,8 +6,8 @@ export RTX_ALLOW_ENV_KNOBS=1      # the product ignores RTX_* environment knobs 
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out/r05; mkdir -p $O
 bash tools/pmc_pass1.sh r05 > $O/pmc.log 2>&1
-python bench.py > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log > $O/r05_bench_default.json
-for c in cfg1 cfg2 cfg3 cfg4 cfg5 area; do python bench.py --config $c --no-cpu-baseline 2>/dev/null | grep '^{' > $O/r05_bench_$c.json; done
+python bench.py --full > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log > $O/r05_bench_default.json
+for c in cfg1 cfg2 cfg3 cfg4 cfg5 area; do python bench.py --config $c --full --no-cpu-baseline 2>/dev/null | grep '^{' > $O/r05_bench_$c.json; done
 bash tools/profile.sh r05 --steps 5 --warmup 1 > $O/profile_headline.log 2>&1
 cp $(find gpurun_out/prof_r05 -name '*kernel_stats.csv' | head -1) $O/r05_kernel_stats.csv; cp gpurun_out/prof_r05/bench.json $O/r05_bench_under_rocprof.json
 for c in cfg1 cfg2 cfg3 cfg4 cfg5 area; do

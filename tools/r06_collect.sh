@@ -19,7 +19,7 @@ if [ "$1" = 1 ]; then
   tail -3 $O/pmc.log; head -3 $O/r06_dbg_counts.txt
 elif [ "$1" = 3 ]; then
   # (only the runs under rocprofv3 and the default line again: after a change of bench.py alone)
-  python bench.py > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log > $O/r06_bench_default.json
+  python bench.py --full > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log > $O/r06_bench_default.json
   bash tools/profile.sh r06 --steps 20 --warmup 5 > $O/profile_headline.log 2>&1
   cp $(find gpurun_out/prof_r06 -name '*kernel_stats.csv' | head -1) $O/r06_kernel_stats.csv; cp gpurun_out/prof_r06/bench.json $O/r06_bench_under_rocprof.json
   for c in cfg1 cfg2 cfg3 cfg4 cfg5 area knot ref_bunny headline_nocull; do
@@ -28,8 +28,8 @@ elif [ "$1" = 3 ]; then
   done
   head -4 $O/r06_kernel_stats.csv; cat $O/r06_bench_default.json | head -c 400
 else
-  for c in $WL; do python bench.py --config $c --steps 20 --warmup 5 --pipelined 2> $O/bench_$c.err | grep '^{' > $O/r06_bench_$c.json; done
-  python bench.py 2>/dev/null | grep '^{' > $O/r06_bench_default.json
+  for c in $WL; do python bench.py --config $c --steps 20 --warmup 5 --pipelined --full 2> $O/bench_$c.err | grep '^{' > $O/r06_bench_$c.json; done
+  python bench.py --full 2>/dev/null | grep '^{' > $O/r06_bench_default.json
   bash tools/profile.sh r06 --steps 5 --warmup 1 > $O/profile_headline.log 2>&1
   cp $(find gpurun_out/prof_r06 -name '*kernel_stats.csv' | head -1) $O/r06_kernel_stats.csv; cp gpurun_out/prof_r06/bench.json $O/r06_bench_under_rocprof.json
   for c in cfg1 cfg2 cfg3 cfg4 cfg5 area knot ref_bunny headline_nocull; do
@@ -40,6 +40,6 @@ else
   (python tools/shard_time.py 2 4 8; python tools/shard_time.py 2 4 8 --size 8192) 2>&1 | grep -v amdgpu > $O/r06_shard_emulation.txt
   python tools/new_view_probe.py 2>&1 | grep -v amdgpu > $O/r06_new_view_probe.txt
   python tools/bvh_build_time.py 2>&1 | grep -v amdgpu | tail -3 > $O/r06_bvh_build_time.txt
-  BENCH_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 2>/dev/null | grep '^{' > $O/r06_bench_gloo2_functional.json
+  BENCH_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --full 2>/dev/null | grep '^{' > $O/r06_bench_gloo2_functional.json
   cat $O/r06_configs.txt
 fi
