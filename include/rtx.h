@@ -265,6 +265,17 @@ int rtx_gather_plan(uint32_t height, uint32_t band_height, uint32_t n_parts, siz
  * colours: n x 3.  Used by the per-ray parity tests. */
 int rtx_cast_rays(rtx_scene* scene, uint32_t n, const float* rays_host, float* hits_host, float* colours_host);
 
+/* The same for a batch of caller-supplied rays in device memory (picking, visibility queries, custom cameras, secondary rays):
+ * rays_dev n x 6 floats {orig xyz, dir xyz}; hits_dev n x 8 floats in rtx_cast_rays' layout, or NULL; colours_dev n x 3 floats =
+ * Render::castRay(ray, scene, 0), or NULL -- at least one of the two.  Every ray's results are the bits rtx_cast_rays returns for it
+ * under the same view (flags included: culling, skybox, RTX_FLAG_SHOW_NORMALS), whatever the other rays of the batch.  Large batches
+ * are grouped into coherent bundles on the device first unless their order is already coherent; the results go
+ * to each ray's own index.
+ * Asynchronous on `stream`: nothing is queued on the NULL stream and, once the scene's scratch has grown to n rays, nothing waits for
+ * the device.  n == 0 does nothing; row ownership is ignored; counters are neither collected nor refused.  The scratch and the
+ * recursion frames are the scene's: calls on one scene are not to overlap on different streams (as the render calls). */
+int rtx_trace_rays(rtx_scene* scene, uint32_t n, const float* rays_dev, float* hits_dev, float* colours_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

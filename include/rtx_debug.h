@@ -35,7 +35,9 @@ int rtx_cost_grid_read(rtx_scene* scene, uint32_t* out, size_t n, uint32_t* grid
 /* Experiment / test knobs of a live scene.  Their environment variables (RTX_STRIP_LIMIT, RTX_SSAA_HEAVY_TICKS,
  * RTX_SSAA_SPREAD_SLOTS, RTX_SPLIT_PERCENT, RTX_SSAA_LOCAL_BELOW, RTX_SSAA_SPARSE_BELOW, RTX_FRAME_QUEUE_CAP, RTX_DEBUG_ITEMS, ...) are read
  * once, by rtx_scene_create, and only when RTX_ALLOW_ENV_KNOBS=1 is set (the product ignores RTX_* variables otherwise); names here: strip_limit, ssaa_heavy_ticks, ssaa_spread_slots, split_percent,
- * ssaa_local_below, ssaa_sparse_below, frame_queue_cap, frame_rule_tiles, frame_rule_tiles_analytic, debug_items.  No knob changes a pixel. */
+ * ssaa_local_below, ssaa_sparse_below, frame_queue_cap, frame_rule_tiles, frame_rule_tiles_analytic, debug_items; and for rtx_trace_rays
+ * trace_reorder (1 always group the rays by key first, 0 never, -1 by their number and the coherence of their order: the default) and trace_key_origin_first (1: the key's interleave
+ * starts with the origin's bits, the default; 0: with the direction's).  No knob changes a pixel or a ray's result. */
 int rtx_set_knob(rtx_scene* scene, const char* name, double value);
 
 /* Launch counts and summed durations of kernel `which` (rtx_last_kernel_ms in rtx.h) since rtx_kernel_time_reset; synchronises on the recorded events. */

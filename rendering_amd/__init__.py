@@ -36,7 +36,7 @@ RTX_SYMBOLS = [
     "rtx_last_error", "rtx_device_count", "rtx_scene_create", "rtx_scene_destroy", "rtx_scene_set_view", "rtx_scene_bytes",
     "rtx_render_pass1", "rtx_sobel", "rtx_render_ssaa", "rtx_render_frame", "rtx_render_ac", "rtx_frame_status", "rtx_frame_mode", "rtx_set_frame_mode", "rtx_set_knob", "rtx_cost_grid_read", "rtx_mesh_flatten_probe", "rtx_wide_node_slots", "rtx_source_p_probe", "rtx_quantize_bgr8", "rtx_render_frame_host",
     "rtx_counters_enable", "rtx_counters_reset", "rtx_counters_read", "rtx_last_kernel_ms", "rtx_math_probe",
-    "rtx_cast_rays", "rtx_kernel_time_reset", "rtx_kernel_time_stats", "rtx_tile_cost_read", "rtx_set_row_ownership",
+    "rtx_cast_rays", "rtx_trace_rays", "rtx_kernel_time_reset", "rtx_kernel_time_stats", "rtx_tile_cost_read", "rtx_set_row_ownership",
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
 ]
@@ -81,6 +81,7 @@ def load():
     rtx.rtx_last_kernel_ms.argtypes = [vp, i32, C.POINTER(C.c_float)]
     rtx.rtx_math_probe.argtypes = [i32, i32, u32, vp, vp, vp]
     rtx.rtx_cast_rays.argtypes = [vp, u32, vp, vp, vp]
+    rtx.rtx_trace_rays.argtypes = [vp, u32, vp, vp, vp, vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -521,6 +522,44 @@ class Scene:
         col = np.zeros((n, 3), np.float32)
         _check(self.rtx.rtx_cast_rays(self.gpu(), n, _np_ptr(rays), _np_ptr(hits), _np_ptr(col)), "rtx_cast_rays")
         return hits, col
+
+    def trace_rays(self, rays, hits=True, colours=True, stream=None):
+        """rtx_trace_rays: Render::trace + Render::castRay(depth 0) for the rays of a device tensor, on the device.
+        rays: contiguous float32 torch tensor (n, 6) = {orig xyz, dir xyz} on this scene's device.  Returns (hits (n, 8) | None,
+        colours (n, 3) | None): new float32 tensors on that device, each ray's the bits of cast_rays.  Asynchronous on `stream` (None:
+        torch's current stream of the rays' device); the results are ready when that stream is.  With a torch.cuda.Stream the outputs are
+        allocated on it and the rays recorded on it (torch's caching allocator); a raw hipStream_t handle is used as given, so the caller
+        then keeps the rays and the outputs alive and unreused until that stream has finished with them."""
+        import torch
+        if not (hits or colours):
+            raise ValueError("trace_rays: nothing to compute (hits and colours are both off)")
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("trace_rays: rays must be a torch tensor, got %s" % type(rays).__name__)
+        if rays.dtype != torch.float32:
+            raise ValueError("trace_rays: rays must be float32, got %s" % rays.dtype)
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("trace_rays: rays must have shape (n, 6), got %s" % (tuple(rays.shape),))
+        if not rays.is_contiguous():
+            raise ValueError("trace_rays: rays must be contiguous")
+        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError("trace_rays: rays must be on cuda:%d, the scene's device, got %s" % (self.device, rays.device))
+        n = rays.shape[0]
+        if n > 0xFFFFFFC0:
+            raise ValueError("trace_rays: at most %d rays per call, got %d" % (0xFFFFFFC0, n))
+        # the outputs belong to the stream they are written on (torch's caching allocator), and so do the rays while it reads them
+        alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+        with torch.cuda.stream(alloc_on):
+            h = torch.empty((n, 8), dtype=torch.float32, device=rays.device) if hits else None
+            c = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if colours else None
+        if n == 0:
+            return h, c
+        if alloc_on is not None:
+            rays.record_stream(alloc_on)
+        _check(self.rtx.rtx_trace_rays(self.gpu(), n, C.c_void_p(rays.data_ptr()), C.c_void_p(h.data_ptr()) if h is not None else None,
+                                       C.c_void_p(c.data_ptr()) if c is not None else None,
+                                       C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
+               "rtx_trace_rays")
+        return h, c
 
     def counters_enable(self, on=True):
         _check(self.rtx.rtx_counters_enable(self.gpu(), int(on)), "rtx_counters_enable")

@@ -22,6 +22,11 @@ using namespace rtxd;
 // single translation unit: the kernels are compiled together with their launch code
 #include "rtx_kernels.hip"
 #include "rtx_source.hip"
+#include "rtx_rays.hip"
+
+// rtx_sort.hip
+hipError_t rtxSortRayKeys(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, uint32_t* order, uint32_t n, int endBit,
+                          hipStream_t st);
 
 namespace {
 
@@ -121,6 +126,8 @@ struct Knobs {
 	                                     // without probing (measured on one MI355X: rtx_render_frame); 0xffffffff = always measure
 	uint32_t frameQueueCap = 0;          // RTX_FRAME_QUEUE_CAP: entries per SSAA item queue of the frame kernel; 0 = sized from the frame
 	bool debugItems = false;             // RTX_DEBUG_ITEMS: rtx_counters_read prints the wave-level counters
+	int traceReorder = -1;               // knob trace_reorder: rtx_trace_rays groups the rays by key always (1), never (0), by their number and coherence (-1)
+	int traceOriginFirst = 1;            // knob trace_key_origin_first: the key's interleave starts with the origin's bits (1) or the direction's (0)
 	uint32_t dbgTile = 0;                // RTX_DBG_TILE=tx,ty (RTX_DBG builds): only this tile
 };
 
@@ -174,6 +181,11 @@ struct rtx_scene {
 	// rtx_render_ac: per-pixel counts when the caller passes none, and the frame's maximum
 	uint32_t* acCounts = nullptr; size_t acCap = 0;
 	uint32_t* acMax = nullptr;
+	// rtx_trace_rays: sort keys (in, out) and the order of up to rayCap rays, the sort's scratch, queue heads + key box (rtxRayInitKernel);
+	// blocks per CU of the hit kernel launched for culling off / on (0: not asked yet)
+	uint32_t* rayKeys = nullptr; uint32_t* rayOrder = nullptr; void* raySortTemp = nullptr; size_t rayCap = 0, raySortBytes = 0;
+	uint32_t* rayWork = nullptr;
+	int rayHitBlocks[2] = { 0, 0 };
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
 	struct MeshLeaves { const float* boxes; uint32_t n; };      // 8 floats per non-empty leaf: true box lo, hi, reference count, -
@@ -963,6 +975,9 @@ void rtx_scene_destroy(rtx_scene* s)
 	if (s->ssaaPixels) (void)hipFree(s->ssaaPixels);
 	if (s->acCounts) (void)hipFree(s->acCounts);
 	if (s->acMax) (void)hipFree(s->acMax);
+	if (s->rayKeys) { (void)hipFree(s->rayKeys); (void)hipFree(s->rayOrder); }
+	if (s->raySortTemp) (void)hipFree(s->raySortTemp);
+	if (s->rayWork) (void)hipFree(s->rayWork);
 	if (s->work) {
 		(void)hipFree(s->work); (void)hipFree(s->counters); (void)hipFree(s->orderWork);
 		for (int i = 0; i < 5; i++) for (hipEvent_t e : s->evPool[i]) (void)hipEventDestroy(e);
@@ -1607,6 +1622,8 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 	else if (n == "frame_rule_tiles") k.frameRuleTiles = value >= 4294967295.0 ? 0xffffffffu : (uint32_t)value;
 	else if (n == "frame_rule_tiles_analytic") k.frameRuleTilesAnalytic = value >= 4294967295.0 ? 0xffffffffu : (uint32_t)value;
 	else if (n == "debug_items") k.debugItems = value != 0;
+	else if (n == "trace_reorder") k.traceReorder = value < 0 ? -1 : (value != 0 ? 1 : 0);
+	else if (n == "trace_key_origin_first") k.traceOriginFirst = value != 0 ? 1 : 0;
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
 	return RTX_OK;
 }
@@ -2078,6 +2095,117 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 32, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(colours, dc.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+	return RTX_OK;
+}
+
+namespace {
+
+// rtx_trace_rays groups the rays by key from this many on, unless they already come in coherent groups (rtxRayKeyKernel; measured on one
+// MI355X: profiles/trace_rays_time.json)
+constexpr uint32_t kTraceReorderMin = 1u << 20;
+
+// The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
+// for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
+// in case a smaller n ever needed more.)
+int ensureRayScratch(rtx_scene* s, uint32_t n, bool reorder, hipStream_t st)
+{
+	if (!s->rayWork) HIPCHK(hipMalloc((void**)&s->rayWork, 64 * sizeof(uint32_t)));
+	if (!reorder) return RTX_OK;
+	if (n > s->rayCap) {
+		if (s->rayKeys) { HIPCHK(hipFree(s->rayKeys)); HIPCHK(hipFree(s->rayOrder)); }
+		s->rayKeys = s->rayOrder = nullptr; s->rayCap = 0;
+		HIPCHK(hipMalloc((void**)&s->rayKeys, 2 * (size_t)n * sizeof(uint32_t)));
+		HIPCHK(hipMalloc((void**)&s->rayOrder, (size_t)n * sizeof(uint32_t)));
+		s->rayCap = n;
+	}
+	size_t bytes = 0;
+	HIPCHK(rtxSortRayKeys(nullptr, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
+	if (bytes > s->raySortBytes) {
+		if (s->raySortTemp) HIPCHK(hipFree(s->raySortTemp));
+		s->raySortTemp = nullptr; s->raySortBytes = 0;
+		HIPCHK(hipMalloc(&s->raySortTemp, bytes));
+		s->raySortBytes = bytes;
+	}
+	return RTX_OK;
+}
+
+// the kernels of the scene's kind (as RTX_LAUNCH_MESH_KERNEL picks them for pass 1)
+typedef void (*RayKernel)(const Params, const uint32_t*, float*);
+RayKernel rayHitKernel(const rtx_scene* s, bool cull)
+{
+	if (s->analytic) return rtxRayHitKernel<false, true, -1>;
+	if (cull) return s->boxPrune ? rtxRayHitKernel<true, true, 1> : rtxRayHitKernel<true, false, 1>;
+	return s->boxPrune ? rtxRayHitKernel<true, true, 0> : rtxRayHitKernel<true, false, 0>;
+}
+RayKernel rayColourKernel(const rtx_scene* s, bool cull)
+{
+	if (s->analytic) return rtxRayColourKernel<false, true, -1, false>;
+	if (s->plain) {
+		if (cull) return s->boxPrune ? rtxRayColourKernel<true, true, 1, true> : rtxRayColourKernel<true, false, 1, true>;
+		return s->boxPrune ? rtxRayColourKernel<true, true, 0, true> : rtxRayColourKernel<true, false, 0, true>;
+	}
+	if (cull) return s->boxPrune ? rtxRayColourKernel<true, true, 1, false> : rtxRayColourKernel<true, false, 1, false>;
+	return s->boxPrune ? rtxRayColourKernel<true, true, 0, false> : rtxRayColourKernel<true, false, 0, false>;
+}
+
+} // namespace
+
+int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_dev, float* colours_dev, void* stream)
+{
+	RoctxRange range("Trace rays (rtx_trace_rays)");
+	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
+	if (!hits_dev && !colours_dev) return fail(RTX_ERR_ARG, "rtx_trace_rays: no output (hits and colours are both NULL)");
+	if (n == 0) return RTX_OK;
+	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
+	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	hipStream_t st = (hipStream_t)stream;
+	if ((rc = renderOn(s, st))) return rc;
+	const bool reorder = s->knobs.traceReorder < 0 ? n >= kTraceReorderMin : s->knobs.traceReorder != 0;
+	if ((rc = ensureRayScratch(s, n, reorder, st))) return rc;
+	Params p = s->params;
+	p.probeRays = rays_dev; p.nProbe = n;
+	const uint32_t waves = (n + 63) / 64;
+	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork);
+	const uint32_t* order = nullptr;
+	if (reorder) {
+		// the camera's position and axes: the frame of the key's coordinates (rtx_rays.hip, rayCoords)
+		const float* M = p.view.camM;
+		const RayAxes ax = { { M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10] }, { p.view.camPos[0], p.view.camPos[1], p.view.camPos[2] } };
+		const uint32_t groups = (uint32_t)(((size_t)n + 255) / 256);
+		double* spread = (double*)(s->rayWork + 44);
+		hipLaunchKernelGGL(rtxRayBoxKernel, dim3(std::min<uint32_t>(groups, (uint32_t)s->numCUs * 8u)), dim3(256), 0, st, rays_dev, n, ax, s->rayWork + 32, spread);
+		// (by default the caller's order is kept where it is already as coherent: rtxRayKeyKernel; trace_reorder = 1 always sorts)
+		hipLaunchKernelGGL(rtxRayKeyKernel, dim3(groups), dim3(256), 0, st, rays_dev, n, ax, (const uint32_t*)(s->rayWork + 32), (const double*)spread,
+		                   s->knobs.traceOriginFirst, s->knobs.traceReorder < 0 ? 1 : 0, s->rayKeys);
+		size_t bytes = s->raySortBytes;
+		HIPCHK(rtxSortRayKeys(s->raySortTemp, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
+		order = s->rayOrder;
+	}
+	const bool cull = (p.view.flags & RTX_FLAG_BACKFACE_CULL) != 0;
+	if (showNormals(s)) {
+		p.workCounter = s->rayWork;
+		const uint32_t blocks = std::min<uint32_t>((uint32_t)s->blocksPass1, (waves + 3) / 4);
+		hipLaunchKernelGGL(rtxRayNormalsKernel, dim3(blocks), dim3(256), 0, st, p, order, hits_dev, colours_dev);
+	}
+	else {
+		if (hits_dev) {
+			const RayKernel k = rayHitKernel(s, cull);
+			int& perCU = s->rayHitBlocks[cull ? 1 : 0];
+			if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k, 256, 0)); perCU = std::max(perCU, 1); }
+			p.workCounter = s->rayWork;
+			const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
+			hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, hits_dev);
+		}
+		if (colours_dev) {
+			// (the recursion frames of the pass-1 area hold blocksPass1 blocks)
+			p.workCounter = s->rayWork + 16;
+			const uint32_t blocks = std::min<uint32_t>((uint32_t)s->blocksPass1, (waves + 3) / 4);
+			hipLaunchKernelGGL(rayColourKernel(s, cull), dim3(blocks), dim3(256), 0, st, p, order, colours_dev);
+		}
+	}
+	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
 

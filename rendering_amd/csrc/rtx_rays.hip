@@ -1,0 +1,257 @@
+// Caller-supplied rays on the device (rtx_trace_rays, include/rtx.h): Render::trace and Render::castRay at depth 0 for a batch of rays
+// handed over in device memory, on the caller's stream.  DESIGN.md section 3.6.
+//
+// The walk (traceWave) is built for bundles of 64 coherent rays: one box of origins times one box of directions.  Rays in the order a
+// caller hands them over can be anything but coherent, so by default they are first grouped (the launch code in rtx_api.hip):
+//   1. rtxRayBoxKernel: the range of the rays' five key coordinates (direction and origin as seen from the camera: rayCoords), and how
+//      far they spread within the caller's own groups of 64;
+//   2. rtxRayKeyKernel: a 30-bit key per ray, the Morton interleave of the coordinates whose range is not empty, normalised to it
+//      (camera rays: all bits go to the direction -- their 64-ray groups are 8 x 8 pixel blocks) -- or 0 for every ray when the caller's
+//      groups are already as tight as sorted ones would be (the sort then keeps the caller's order);
+//   3. a stable radix sort of (key, index) pairs (rtx_sort.hip: rocPRIM), ties in index order;
+//   4. rtxRayHitKernel / rtxRayColourKernel / rtxRayNormalsKernel: persistent waves take 64 consecutive entries of the order, read
+//      their rays through it and write every result at the ray's own index.
+// Grouping changes the amount of work only: the walk's result for a ray does not depend on the other lanes of its bundle (the filter
+// rejects only what the reference is certain to reject, ties are broken in index order), so every ray's hit record and colour are
+// the bits rtx_cast_rays returns for it (tests/test_gpu_trace_rays.py).
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kRayKeyBits = 30;          // bits of the sort key (the radix sort runs over these only)
+
+// float <-> uint32 with the order of the floats (min / max by integer atomics)
+__device__ __forceinline__ uint32_t orderedBits(float f)
+{
+	const uint32_t u = __float_as_uint(f);
+	return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float orderedFloat(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
+// A direction in the frame of the camera axes (ax), as a point of the octahedral map whose centre is the camera's view direction (-z):
+// the map's only seam, its corners, is then behind the camera.  (A zero vector gives NaN.)
+struct RayAxes { float m[9]; float cam[3]; };
+__device__ __forceinline__ void octahedral(const RayAxes& ax, float dx, float dy, float dz, float& u, float& v)
+{
+	const float x = dx * ax.m[0] + dy * ax.m[1] + dz * ax.m[2];
+	const float y = dx * ax.m[3] + dy * ax.m[4] + dz * ax.m[5];
+	const float z = dx * ax.m[6] + dy * ax.m[7] + dz * ax.m[8];
+	const float l1 = fabsf(x) + fabsf(y) + fabsf(z);
+	u = x / l1; v = y / l1;
+	if (z > 0) {
+		const float fu = (1.0f - fabsf(v)) * (u < 0 ? -1.0f : 1.0f), fv = (1.0f - fabsf(u)) * (v < 0 ? -1.0f : 1.0f);
+		u = fu; v = fv;
+	}
+}
+
+// The five key coordinates of a ray: its direction on the map, and its origin as seen from the camera -- the map point of the way from
+// the camera to it and the log of its distance.  (Hit points of camera rays keep their pixels' neighbourhoods, and a far-away plane
+// does not squeeze the rest of the scene into a few cells.  A ray starting at the camera has no finite origin coordinates.)
+__device__ __forceinline__ void rayCoords(const float* ray, const RayAxes& ax, float c[5])
+{
+	octahedral(ax, ray[3], ray[4], ray[5], c[0], c[1]);
+	const float ox = ray[0] - ax.cam[0], oy = ray[1] - ax.cam[1], oz = ray[2] - ax.cam[2];
+	octahedral(ax, ox, oy, oz, c[2], c[3]);
+	c[4] = __builtin_log2f(fabsf(ox) + fabsf(oy) + fabsf(oz));
+}
+
+__device__ __forceinline__ float waveMinF(float v)
+{
+	for (int k = 32; k >= 1; k >>= 1) v = fminf(v, __shfl_xor(v, k));
+	return v;
+}
+__device__ __forceinline__ float waveMaxF(float v)
+{
+	for (int k = 32; k >= 1; k >>= 1) v = fmaxf(v, __shfl_xor(v, k));
+	return v;
+}
+
+} // namespace
+
+// box[0, 5): the ordered bits of the smallest finite value of each coordinate, box[5, 10) of the largest (~0 / 0 before the launch);
+// spread[k]: the sum over the caller's groups of 64 consecutive rays of the range of coordinate k within the group (0 before the launch).
+// Non-finite coordinates take no part: such rays go to the edges of the key's range.  One wave per group.
+__global__ void __launch_bounds__(256) rtxRayBoxKernel(const float* rays, uint32_t n, RayAxes ax, uint32_t* box, double* spread)
+{
+	float lo[5], hi[5];
+	double sp[5];
+	for (int k = 0; k < 5; k++) { lo[k] = __builtin_inff(); hi[k] = -__builtin_inff(); sp[k] = 0.0; }
+	const uint32_t groups = (uint32_t)(((size_t)n + 63) / 64), waves = gridDim.x * 4;
+	for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < groups; g += waves) {
+		const size_t i = (size_t)g * 64 + __lane_id();
+		float c[5] = { 0, 0, 0, 0, 0 };
+		const bool valid = i < n;
+		if (valid) rayCoords(rays + i * 6, ax, c);
+		for (int k = 0; k < 5; k++) {
+			const bool fin = valid && fabsf(c[k]) < __builtin_inff();
+			const float a = waveMinF(fin ? c[k] : __builtin_inff()), b = waveMaxF(fin ? c[k] : -__builtin_inff());
+			if (a <= b) { lo[k] = fminf(lo[k], a); hi[k] = fmaxf(hi[k], b); sp[k] += (double)b - (double)a; }
+		}
+	}
+	// (lo, hi, sp are the same in every lane of a wave)
+	__shared__ float part[2][5][4];
+	__shared__ double partSp[5][4];
+	const uint32_t w = threadIdx.x >> 6;
+	if (__lane_id() == 0) for (int k = 0; k < 5; k++) { part[0][k][w] = lo[k]; part[1][k][w] = hi[k]; partSp[k][w] = sp[k]; }
+	__syncthreads();
+	if (threadIdx.x < 5) {
+		const int k = threadIdx.x;
+		const float a = fminf(fminf(part[0][k][0], part[0][k][1]), fminf(part[0][k][2], part[0][k][3]));
+		const float b = fmaxf(fmaxf(part[1][k][0], part[1][k][1]), fmaxf(part[1][k][2], part[1][k][3]));
+		if (a <= b) {
+			atomicMin(box + k, orderedBits(a)); atomicMax(box + 5 + k, orderedBits(b));
+			atomicAdd(spread + k, (partSp[k][0] + partSp[k][1]) + (partSp[k][2] + partSp[k][3]));
+		}
+	}
+}
+
+// keys[i] = the Morton interleave of ray i's coordinates, each normalised to the box of rtxRayBoxKernel.  A coordinate whose range is
+// empty (every camera ray has the same origin) gets no bits; the others share kRayKeyBits in turns, most significant bits first,
+// starting with the direction (originFirst = 0) or the origin (1).
+// check != 0: every key is 0 -- the stable sort then keeps the caller's order -- when the caller's groups of 64 rays are already as tight
+// as sorting would make them in the coordinates the walks depend on most: the origin's, which shadow rays share (the direction's for rays
+// from one point).  Sorted, a group covers about (64 / n)^(1 / dims) of each coordinate's range (n rays filling the box); the caller's
+// groups cover spread[k] / groups of it on average.
+__global__ void __launch_bounds__(256) rtxRayKeyKernel(const float* rays, uint32_t n, RayAxes ax, const uint32_t* box, const double* spread,
+                                                       int originFirst, int check, uint32_t* keys)
+{
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	int dims[5], nd = 0;
+	float base[5], scale[5];
+	double haveO = 0, haveD = 0;
+	int nO = 0, nD = 0;
+	const double groups = (double)(((size_t)n + 63) / 64);
+	for (int j = 0; j < 5; j++) {
+		const int k = originFirst ? (j + 2) % 5 : j;
+		const float a = orderedFloat(box[k]), b = orderedFloat(box[5 + k]);
+		if (!(b > a) || !(b - a < __builtin_inff())) continue;
+		base[nd] = a; scale[nd] = 1.0f / (b - a); dims[nd] = k; nd++;
+		const double have = spread[k] / groups / ((double)b - (double)a);
+		if (k >= 2) { haveO += have; nO++; } else { haveD += have; nD++; }
+	}
+	uint32_t key = 0;
+	const bool keep = check && nd > 0 && (nO ? haveO / nO : haveD / nD) <= exp2(log2(64.0 / (double)n) / nd);
+	if (nd > 0 && !keep) {
+		float c[5];
+		rayCoords(rays + i * 6, ax, c);
+		const int per = kRayKeyBits / nd;
+		uint32_t q[5];
+		for (int j = 0; j < nd; j++) {
+			// (NaN: fmaxf gives 0)
+			const float f = fminf(fmaxf((c[dims[j]] - base[j]) * scale[j], 0.0f), 1.0f) * (float)(1u << per);
+			q[j] = min((uint32_t)f, (1u << per) - 1u);
+		}
+		for (int b = per - 1; b >= 0; b--)
+			for (int j = 0; j < nd; j++) key = key << 1 | ((q[j] >> b) & 1u);
+		key <<= kRayKeyBits - per * nd;
+	}
+	keys[i] = key;
+}
+
+namespace {
+
+// Entry k of the order: the index of the ray lane k takes (order == nullptr: the rays as handed over).
+__device__ __forceinline__ void loadRay(const Params& P, const uint32_t* order, uint32_t k, bool valid, uint32_t& i, V3& o, V3& d)
+{
+	i = valid ? (order ? order[k] : k) : 0u;
+	o = mk(0, 0, 0); d = mk(0, 0, -1);
+	if (valid) { o = load3(P.probeRays + (size_t)i * 6); d = load3(P.probeRays + (size_t)i * 6 + 3); }
+}
+
+// rtx_cast_rays' hit record (rtxProbeKernel)
+__device__ __forceinline__ void storeHit(const Params& P, const Hit& h, float* out)
+{
+	const bool hit = h.obj >= 0;
+	const bool mesh = hit && P.objects[hit ? h.obj : 0].type == 3;
+	out[0] = hit ? 1.f : 0.f; out[1] = hit ? (float)h.obj : -1.f; out[2] = mesh ? (float)h.tri : -1.f;
+	out[3] = h.t; out[4] = hit ? h.u : -1.f; out[5] = hit ? h.v : -1.f; out[6] = 0; out[7] = 0;
+}
+
+} // namespace
+
+// Render::trace alone (hits only): no castRay state machine, no LDS park area, no recursion frames.  P.workCounter: this launch's queue
+// head; P.nProbe rays at P.probeRays.
+template <bool MESH, bool BOXES, int CULLK>
+__global__ void __launch_bounds__(256) rtxRayHitKernel(const Params P, const uint32_t* order, float* hits)
+{
+	const uint32_t lane = __lane_id();
+	const uint32_t nWork = (P.nProbe + 63) / 64;
+	Counts cnt = {};
+	for (;;) {
+		const uint32_t work = nextWork(P.workCounter);
+		if (work >= nWork) break;
+		const uint32_t k = work * 64 + lane;
+		const bool valid = k < P.nProbe;
+		uint32_t i; V3 o, d;
+		loadRay(P, order, k, valid, i, o, d);
+		Hit h;
+		traceWave<false, MESH, false, BOXES, CULLK>(P, valid, false, o, d, kFltMax, h, cnt);
+		if (valid) storeHit(P, h, hits + (size_t)i * 8);
+	}
+}
+
+// Render::castRay(ray, scene, 0): the pass-1 kernels' state machine (castRayWave) with CAM = false -- no ray is known to start at the
+// camera.  Recursion frames: the pass-1 area of rtx_scene::frames, indexed by the global lane (the grid is at most blocksPass1).
+template <bool MESH, bool BOXES, int CULLK, bool PLAIN>
+__global__ void __launch_bounds__(256, MESH ? (PLAIN ? RTX_WAVES_PLAIN : RTX_WAVES) : RTX_WAVES_ANALYTIC) rtxRayColourKernel(const Params P, const uint32_t* order, float* colours)
+{
+	if (!PLAIN) fillPowTab();
+	const uint32_t gl = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t lane = __lane_id();
+	const uint32_t nWork = (P.nProbe + 63) / 64;
+	Counts cnt = {};
+	for (;;) {
+		const uint32_t work = nextWork(P.workCounter);
+		if (work >= nWork) break;
+		const uint32_t k = work * 64 + lane;
+		const bool valid = k < P.nProbe;
+		uint32_t i; V3 o, d;
+		loadRay(P, order, k, valid, i, o, d);
+		const V3 c = castRayWave<false, MESH, false, BOXES, false, CULLK, PLAIN>(P, valid, o, d, gl, cnt);
+		if (valid) { float* pc = colours + (size_t)i * 3; pc[0] = c.x; pc[1] = c.y; pc[2] = c.z; }
+	}
+}
+
+// RTX_FLAG_SHOW_NORMALS: rtxNormalsKernel's mode 2 through the order; either output may be NULL.
+__global__ void __launch_bounds__(256) rtxRayNormalsKernel(const Params P, const uint32_t* order, float* hits, float* colours)
+{
+	const uint32_t lane = __lane_id();
+	const uint32_t nWork = (P.nProbe + 63) / 64;
+	for (;;) {
+		const uint32_t work = nextWork(P.workCounter);
+		if (work >= nWork) break;
+		const uint32_t k = work * 64 + lane;
+		const bool valid = k < P.nProbe;
+		uint32_t i; V3 o, d;
+		loadRay(P, order, k, valid, i, o, d);
+		Hit h;
+		const V3 c = normalsCast(P, valid, o, d, 0u, h);
+		if (valid && hits) storeHit(P, h, hits + (size_t)i * 8);
+		if (valid && colours) { float* pc = colours + (size_t)i * 3; pc[0] = c.x; pc[1] = c.y; pc[2] = c.z; }
+	}
+}
+
+// the kernels of every scene kind: mesh scenes per (box test of the prune records, culling), their colours also per PLAIN; scenes without
+// meshes one of each (as rtxPass1Kernel<false, false>)
+template __global__ void rtxRayHitKernel<true, true, 1>(const Params, const uint32_t*, float*);
+template __global__ void rtxRayHitKernel<true, false, 1>(const Params, const uint32_t*, float*);
+template __global__ void rtxRayHitKernel<true, true, 0>(const Params, const uint32_t*, float*);
+template __global__ void rtxRayHitKernel<true, false, 0>(const Params, const uint32_t*, float*);
+template __global__ void rtxRayHitKernel<false, true, -1>(const Params, const uint32_t*, float*);
+#define RTX_RAY_COLOUR_INSTANCES(PL)                                                                         \
+template __global__ void rtxRayColourKernel<true, true, 1, PL>(const Params, const uint32_t*, float*);     \
+template __global__ void rtxRayColourKernel<true, false, 1, PL>(const Params, const uint32_t*, float*);    \
+template __global__ void rtxRayColourKernel<true, true, 0, PL>(const Params, const uint32_t*, float*);     \
+template __global__ void rtxRayColourKernel<true, false, 0, PL>(const Params, const uint32_t*, float*);
+RTX_RAY_COLOUR_INSTANCES(false) RTX_RAY_COLOUR_INSTANCES(true)
+#undef RTX_RAY_COLOUR_INSTANCES
+template __global__ void rtxRayColourKernel<false, true, -1, false>(const Params, const uint32_t*, float*);
+
+// The queue heads of the trace launches ([0] hits, [16] colours), the box of rtxRayBoxKernel ([32, 37) minima as ~0, [37, 42) maxima as 0)
+// and its spreads ([44, 54): five doubles, 0).
+__global__ void __launch_bounds__(64) rtxRayInitKernel(uint32_t* work)
+{
+	const uint32_t t = threadIdx.x;
+	if (t < 54) work[t] = (t >= 32 && t < 37) ? ~0u : 0u;
+}

@@ -9,7 +9,7 @@ for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   ( mkdir -p build/var/$name
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -shared -save-temps=obj -Rpass-analysis=kernel-resource-usage $defs \
-    -o build/var/$name/librtx.so rendering_amd/csrc/rtx_api.hip 2> build/var/$name.log || { echo "$name FAILED"; tail -5 build/var/$name.log; }
+    -o build/var/$name/librtx.so rendering_amd/csrc/rtx_api.hip rendering_amd/csrc/rtx_sort.hip 2> build/var/$name.log || { echo "$name FAILED"; tail -5 build/var/$name.log; }
     cp build/var/$name/librtx.so rendering_amd/_variants/librtx_$name.so
     rm -f build/var/$name/*.bc build/var/$name/*.hipi build/var/$name/*.o build/var/$name/*host*.s build/var/$name/*.hipfb
     grep -E 'Function Name|VGPRs:|ScratchSize|Occupancy' build/var/$name.log | sed -e 's/.*usage-analysis..//' -e 's/remark: [^ ]* *//' -e 's/ \[-Rpass.*//' | paste - - - - | grep -E 'Pass1KernelILb0ELb1ELb1' | sed "s/^/$name: /" ) &
