@@ -431,14 +431,17 @@ __device__ __forceinline__ void centreRadius(float lo, float hi, float& c, float
 // max and min of one value over the wave, as two interleaved chains of v_max_f32 / v_min_f32 with a DPP source (one
 // instruction per step and chain; s_nop 0 + the other chain's instruction = the two wait states a DPP read of a
 // just-written VGPR needs).  Through __builtin_amdgcn_update_dpp every step is v_mov + v_mov_dpp + canonicalising v_max + v_max.
-__device__ __forceinline__ void waveMaxMin(float& hi, float& lo)
+// Both chains start from ONE value v (lanes that must not contribute pass a quiet NaN, which v_max / v_min drop: one select per coordinate
+// instead of one per chain).
+__device__ __forceinline__ void waveMaxMin(float v, float& hi, float& lo)
 {
 #define RTX_STEP(ctrl) "v_max_f32_dpp %0, %0, %0 " ctrl "\n\tv_min_f32_dpp %1, %1, %1 " ctrl "\n\ts_nop 0\n\t"
 	asm volatile("s_nop 1\n\t"
-		RTX_STEP("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf") RTX_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+		"v_max_f32_dpp %0, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\tv_min_f32_dpp %1, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\ts_nop 0\n\t"
+		RTX_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
 		RTX_STEP("row_half_mirror row_mask:0xf bank_mask:0xf") RTX_STEP("row_mirror row_mask:0xf bank_mask:0xf")
 		RTX_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf") RTX_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
-		"s_nop 0" : "+v"(hi), "+v"(lo));
+		"s_nop 0" : "=&v"(hi), "=&v"(lo) : "v"(v));
 #undef RTX_STEP
 	hi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hi), 63));
 	lo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lo), 63));
@@ -448,11 +451,13 @@ __device__ __forceinline__ void waveMaxMin(float& hi, float& lo)
 // radius 0 (three of the six wave reductions are not needed)
 __device__ __forceinline__ Bundle makeBundle(bool active, const V3& o, const V3& d, bool sameOrigin = false)
 {
-	const float ninf = -__builtin_inff();
+	const float qnan = __builtin_nanf("");
 	Bundle B;
 	float lo, hi;
-	// (max and min of a coordinate as one pair of interleaved DPP chains, waveMaxMin: profiles/r05_ab_*.txt)
-#define RTX_RANGE(x, c, r) hi = active ? (x) : ninf; lo = active ? (x) : -ninf; waveMaxMin(hi, lo); centreRadius(lo, hi, c, r)
+	// (max and min of a coordinate as one pair of interleaved DPP chains, waveMaxMin: profiles/r05_ab_*.txt).  The inactive lanes' quiet NaN drops out of
+	// both chains as the -inf / +inf it replaces did: the same box bit for bit whenever an active lane's coordinate is a number, and the same NaN centre
+	// and radius (a NaN box, B.sane false) when none is.
+#define RTX_RANGE(x, c, r) waveMaxMin(active ? (x) : qnan, hi, lo); centreRadius(lo, hi, c, r)
 	if (sameOrigin) {
 		const int first = __builtin_ctzll(ballot(active) | (1ull << 63));
 		B.ocx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.x), first)); B.ocy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.y), first));
@@ -1439,6 +1444,7 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 {
 	const int maxDepth = P.view.maxDepth;
 	const float bias = P.view.bias;
+	V3& col = PLAIN ? s.diff : s.col;      // (PLAIN: the value returned lives in diff -- see castRayWave)
 	// One loop for the whole wave with a UNIFORM exit: a lane that has reached a waiting state (or ST_DONE) sits out the remaining steps (run = false) instead
 	// of leaving the loop.  With per-lane `return`s the compiler kept every field of the lane state twice -- the value a lane left with and the value the others go on
 	// changing -- and copied 16-20 registers at the head of every step and at every exit (pass 1 -2.7 %: profiles/r06_ab_control_flow.txt).
@@ -1447,7 +1453,7 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 		if (!run) continue;
 		if (s.state == ST_NEWRAY) {
 			RTX_T0
-			if (s.sp > maxDepth) { s.col = skyColor(P, s.rd); s.state = ST_RETURN; RTX_ACC(0) continue; }   // scene.cpp:760
+			if (s.sp > maxDepth) { col = skyColor(P, s.rd); s.state = ST_RETURN; RTX_ACC(0) continue; }     // scene.cpp:760
 			s.qtmax = kFltMax;
 			s.state = ST_WAIT_PRIMARY;
 			run = false; continue;
@@ -1459,10 +1465,15 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 			// them; the others stay in this state and take their turn in a later step of the loop (the per-lane form was a chain of dependent vector loads --
 			// type, then the fields of that type -- and merging it with the scalar form cost 13 copies per step).
 			const uint32_t li0 = __builtin_amdgcn_readfirstlane(s.li);
+			// (PLAIN: an opaque copy for the addresses below -- with li0 itself the compiler substitutes the lane's s.li, equal past the compare, and fetches
+			// the record with three vector loads from a 64-bit per-lane index, which it then keeps, spilled, across the walk.  The other kernels keep the
+			// form they had: the analytic pass-1 kernel needs a 97th VGPR with it, i.e. loses its fifth wave)
+			uint32_t liS = li0;
+			if (PLAIN) asm volatile("" : "+s"(liS));
 			if (s.li != li0) continue;
 			LightRec lr;
 			{
-				const u32x16 w = sload16(P.lights + li0);
+				const u32x16 w = sload16(P.lights + liS);
 				lr.type = (int)w[0]; lr.color = mk(F(w[1]), F(w[2]), F(w[3])); lr.intensity = F(w[4]);
 				lr.dir = mk(F(w[5]), F(w[6]), F(w[7])); lr.pos = mk(F(w[8]), F(w[9]), F(w[10])); lr.nPoints = w[11];
 				lr.points = (const float*)(((uint64_t)w[13] << 32) | w[12]);
@@ -1512,7 +1523,7 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 			s.qarea = lt == 3;
 			// (a light's source copy was derived for shadow-ray origins within srcNmax |bias| of the surface: a shading normal longer than the host
 			// looked at -- a caller's un-normalised tri_nrm, a future object type -- or NaN falls back to copy 0 instead of pruning with too small a sigma)
-			s.qsrc = (lt == 2 && s.li < P.nSrcLights && len2(s.N) <= P.srcNmax2) ? 2u + s.li : 0u;
+			s.qsrc = (lt == 2 && liS < P.nSrcLights && len2(s.N) <= P.srcNmax2) ? 2u + liS : 0u;      // (liS == s.li here)
 			s.qtmax = dist;               // the ray itself: Ray{P + N*bias, -L, ShadowRay} (scene.cpp:787), built in castRayWave
 			s.state = ST_WAIT_SHADOW;
 			RTX_ACC(1)
@@ -1522,7 +1533,7 @@ __device__ __forceinline__ void advance(const Params& P, Lane& s, uint32_t gl)
 			RTX_T0
 			const Object* ob = P.objects + s.obj;
 			if (PLAIN && s.mat != 0) __builtin_unreachable();
-			if (s.mat == 0) { s.col = s.objColor * s.diff; s.state = ST_RETURN; continue; }       // scene.cpp:808
+			if (s.mat == 0) { col = s.objColor * s.diff; s.state = ST_RETURN; continue; }         // scene.cpp:808
 			if (s.mat == 3) {                                                                   // scene.cpp:852
 				s.col = s.objColor * ob->ambient + s.diff * ob->diffuse + s.spec * s.specCoef;
 				s.state = ST_RETURN; continue;
@@ -1597,8 +1608,9 @@ __device__ __forceinline__ void consume(const Params& P, Lane& s, const Hit& h)
 {
 	if (s.state == ST_WAIT_PRIMARY) {
 		RTX_T0
-		if (h.obj < 0) { s.col = skyColor(P, s.rd); s.state = ST_RETURN; RTX_ACC(7) return; }             // scene.cpp:945
+		if (h.obj < 0) { (PLAIN ? s.diff : s.col) = skyColor(P, s.rd); s.state = ST_RETURN; RTX_ACC(7) return; }   // scene.cpp:945
 		shadePrimary(P, s, h);
+		if (PLAIN) s.mat = 0;      // (a PLAIN scene's objects are all Diffuse: rtx_scene_create.  A constant, not a register kept -- spilled -- across the walk)
 		s.state = ST_NEXT_LIGHT;
 		RTX_ACC(8)
 		return;
@@ -1713,6 +1725,9 @@ __device__ __forceinline__ V3 castRayWave(const Params& P0, bool valid, V3 o, V3
 		const float qtmax = s.qtmax;
 		// (a ray of recursion depth 0 is the one handed in; reflected / refracted rays pass through no known point)
 		const uint32_t qsrc = qshadow ? s.qsrc : ((CAM && s.sp == 0) ? 1u : 0u);
+		// The request fields belong to this round: consume() does not read them, and no lane is in a waiting state after it, so advance() sets them again
+		// before they are read.  Said explicitly, they are dead across the walk instead of kept -- spilled -- there for the lanes that sit the next round out.
+		if (MESH) { s.qtmax = kFltMax; s.qmoot = false; s.qsrc = 0; }      // (without a walk -- MESH = false -- the register file holds them: as it was)
 		if (MESH) {
 			const uint32_t t = threadIdx.x;
 			float (*parkedState)[256] = parkArea<PLAIN>();
@@ -1759,7 +1774,7 @@ __device__ __forceinline__ V3 castRayWave(const Params& P0, bool valid, V3 o, V3
 		atomicAdd(&gDbgHist[12], dbgRounds); atomicAdd(&gDbgHist[13], dbgTrace); atomicAdd(&gDbgHist[14], dbgState); atomicAdd(&gDbgHist[15], 1ull);
 	}
 	)
-	return s.col;
+	return PLAIN ? s.diff : s.col;      // (PLAIN: ST_RETURN is reached once, at depth 0, and the colour is kept in diff, which is parked with the rest: see advance)
 }
 
 // Row ownership for the pixel-sharded multi-GPU path (bands of bandH rows dealt round-robin to nParts devices).

@@ -15,7 +15,7 @@
 #define RTX_WAVES 5             // waves per SIMD of the general pass-1 kernels (512 / RTX_WAVES VGPRs; their 31.7 KB of LDS hold five blocks per CU): 4 loses 11-20 %; the PLAIN kernels: RTX_WAVES_PLAIN
 #endif
 #ifndef RTX_WAVES_PLAIN
-#define RTX_WAVES_PLAIN 6       // waves per SIMD of the PLAIN pass-1 kernels: their LDS fits six blocks per CU; 80 VGPRs and 48 B of scratch, 3-4 % faster than 5 (89 VGPRs, no scratch at all)
+#define RTX_WAVES_PLAIN 6       // waves per SIMD of the PLAIN pass-1 kernels: their LDS fits six blocks per CU; 80 VGPRs and 16 B of scratch (48 before round 7), 3-4 % faster than 5 (round 6: 89 VGPRs, no scratch)
 #endif
 #ifndef RTX_WAVES_SSAA
 #define RTX_WAVES_SSAA 4        // the SSAA launch lasts as long as its slowest wave: fewer, unspilled waves (128 VGPRs)
