@@ -72,6 +72,16 @@ int rtx_bvh_build_mode(int mode);
 /* Kernel launches (fills included) of a finished build, and whether the persistent launches did it (1) or the level-by-level build (0). */
 int rtx_bvh_launches(const rtx_bvh* bvh, uint32_t* launches, int* queued);
 
+/* Read-backs of a scene's current geometry (the edits of include/rtx_scene_edit.h are checked through them).  rtx_scene_mesh_read: mesh
+ * `mesh`'s tree as the device holds it, in the rtx_mesh layout (counts2 = {n_nodes, n_refs}; with every array NULL only the counts).
+ * rtx_scene_mesh_flat_read: its wide nodes, prune blocks (the copy any ray uses) and whole-mesh record in rtx_mesh_flatten_probe's layout.
+ * rtx_scene_edit_times: host wall ms of the last rtx_scene_update_mesh -- {device build, flatten on the device + records swapped in, view
+ * preparation queued, whole call}. */
+int rtx_scene_mesh_read(rtx_scene* scene, uint32_t mesh, uint32_t* counts2, float* node_bounds, int32_t* node_skip, int32_t* leaf_begin,
+                        int32_t* leaf_count, uint32_t* refs);
+int rtx_scene_mesh_flat_read(rtx_scene* scene, uint32_t mesh, uint32_t* n_wide, void* wide_out, void* prune_out, uint32_t cap_wide, float* root_rec8);
+int rtx_scene_edit_times(rtx_scene* scene, float* ms4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,11 @@ RTX_SYMBOLS = [
     "rtx_cast_rays", "rtx_trace_rays", "rtx_kernel_time_reset", "rtx_kernel_time_stats", "rtx_tile_cost_read", "rtx_set_row_ownership",
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
+    "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times",
 ]
+
+# the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
+RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh"]
 
 
 def load():
@@ -131,6 +135,14 @@ def load():
     host.rah_scene_digest.argtypes = [vp, vp, i32]
     host.rah_view_flags.argtypes = [vp]
     host.rah_load_bmp.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, i32]
+    host.rah_object_move.argtypes = [vp, i32] + [vp] * 5
+    host.rah_object_type.argtypes = [vp, i32]
+    host.rah_object_move_times.argtypes = [vp, vp]
+    rtx.rtx_scene_set_object.argtypes = [vp, C.c_uint32, vp]
+    rtx.rtx_scene_update_mesh.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, i32, vp]
+    rtx.rtx_scene_mesh_read.argtypes = [vp, C.c_uint32] + [vp] * 6
+    rtx.rtx_scene_mesh_flat_read.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    rtx.rtx_scene_edit_times.argtypes = [vp, vp]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -138,7 +150,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -426,6 +438,29 @@ class Scene:
             return None
         return bool(on.value), ms.value
 
+    def move_object(self, index, pos=None, rot=None, size=None, radius=None, normal=None):
+        """Places object `index` (scene-file order) as its [object] block would with these values; None keeps a value.  A mesh takes
+        pos / rot / size (its vertices are placed again by the loader's code), a sphere pos / radius, a plane pos / normal; any other key
+        raises ValueError.  With a live GPU scene the device rebuilds the mesh's structure (rtx_scene_update_mesh): renders queued before
+        the move see the old scene, later ones the new one.  Afterwards bvh(), digest() and the frames describe the moved scene."""
+        keys = {"mesh": ("pos", "rot", "size"), "sphere": ("pos", "radius"), "plane": ("pos", "normal")}
+        given = {k: v for k, v in (("pos", pos), ("rot", rot), ("size", size), ("radius", radius), ("normal", normal)) if v is not None}
+        if not 0 <= index < self.n_objects:
+            raise ValueError("move_object: object index %d out of range (%d objects)" % (index, self.n_objects))
+        kind = {1: "sphere", 2: "plane", 3: "mesh"}.get(self.host.rah_object_type(self.h, index))
+        bad = [k for k in given if kind is None or k not in keys[kind]]
+        if bad:
+            raise ValueError("move_object: a %s has no key %s (it takes %s)" % (kind, ", ".join(bad), ", ".join(keys.get(kind, ()))))
+        arrs = {}
+        for k, v in given.items():
+            a = np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1))
+            if a.size != (1 if k == "radius" else 3):
+                raise ValueError("move_object: %s takes %d values, got %d" % (k, 1 if k == "radius" else 3, a.size))
+            arrs[k] = a
+        ptr = lambda k: _np_ptr(arrs[k]) if k in arrs else None
+        if self.host.rah_object_move(self.h, index, ptr("pos"), ptr("rot"), ptr("size"), ptr("radius"), ptr("normal")) != 0:
+            raise RtxError("move_object: %s" % self.host.rah_last_error().decode(errors="replace"))
+
     # ---- GPU ------------------------------------------------------------------------------------
     def gpu(self):
         """rtx_scene* of the uploaded scene (flatten + upload on first use; re-applies the view after resize)."""
@@ -560,6 +595,44 @@ class Scene:
                                        C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
                "rtx_trace_rays")
         return h, c
+
+    def device_mesh(self, mesh):
+        """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,
+        refs (rtx_scene_mesh_read)."""
+        g = self.gpu()
+        cnt = np.zeros(2, np.uint32)
+        _check(self.rtx.rtx_scene_mesh_read(g, mesh, _np_ptr(cnt), None, None, None, None, None), "rtx_scene_mesh_read")
+        nn, nr = int(cnt[0]), int(cnt[1])
+        d = dict(bounds=np.zeros((nn, 6), np.float32), skip=np.zeros(nn, np.int32), leaf_begin=np.zeros(nn, np.int32),
+                 leaf_count=np.zeros(nn, np.int32), refs=np.zeros(nr, np.uint32))
+        _check(self.rtx.rtx_scene_mesh_read(g, mesh, _np_ptr(cnt), _np_ptr(d["bounds"]), _np_ptr(d["skip"]), _np_ptr(d["leaf_begin"]),
+                                            _np_ptr(d["leaf_count"]), _np_ptr(d["refs"])), "rtx_scene_mesh_read")
+        return d
+
+    def device_mesh_flat(self, mesh):
+        """(wide, box records, plane records, root record) of mesh `mesh` as the device holds them, in mesh_flatten_probe's layout
+        (rtx_scene_mesh_flat_read)."""
+        g = self.gpu()
+        n = C.c_uint32(0)
+        root = np.zeros(8, np.float32)
+        _check(self.rtx.rtx_scene_mesh_flat_read(g, mesh, C.byref(n), None, None, 0, _np_ptr(root)), "rtx_scene_mesh_flat_read")
+        S = int(self.rtx.rtx_wide_node_slots())
+        wide = np.zeros((n.value, S, 8), np.float32); prune = np.zeros((n.value, 2 * S, 8), np.float32)
+        _check(self.rtx.rtx_scene_mesh_flat_read(g, mesh, C.byref(n), _np_ptr(wide), _np_ptr(prune), n.value, _np_ptr(root)), "rtx_scene_mesh_flat_read")
+        return wide, prune[:, 0:S], prune[:, S:2 * S], root
+
+    def edit_times(self):
+        """Host wall ms of the last rtx_scene_update_mesh: {build, flatten (on the device, records swapped in), sources + estimate queued,
+        whole call} (rtx_scene_edit_times)."""
+        ms = np.zeros(4, np.float32)
+        _check(self.rtx.rtx_scene_edit_times(self.gpu(), _np_ptr(ms)), "rtx_scene_edit_times")
+        return dict(zip(("build", "flatten", "prepare", "total"), (float(x) for x in ms)))
+
+    def move_times(self):
+        """Host wall ms of the last move_object: {place (the loader's placement), upload (the triangles), set_object, update_mesh}."""
+        ms = np.zeros(4, np.float32)
+        self.host.rah_object_move_times(self.h, _np_ptr(ms))
+        return dict(zip(("place", "upload", "set_object", "update_mesh"), (float(x) for x in ms)))
 
     def counters_enable(self, on=True):
         _check(self.rtx.rtx_counters_enable(self.gpu(), int(on)), "rtx_counters_enable")

@@ -15,6 +15,7 @@
 
 #include "../../include/rtx.h"
 #include "../../include/rtx_debug.h"
+#include "../../include/rtx_scene_edit.h"
 #include "rtx_device.h"
 
 using namespace rtxd;
@@ -136,6 +137,17 @@ struct rtx_scene {
 	int numCUs = 0;
 	Knobs knobs;
 	std::vector<void*> owned;     // device allocations freed on destroy
+	// the records as uploaded, kept for the edits (rtx_scene_set_object, rtx_scene_update_mesh: rtx_edit.hip): per mesh its device record, the
+	// allocations of its geometry, normals and tangents (replaced as a whole by rtx_scene_update_mesh) and their bytes; per object its record and
+	// its description
+	std::vector<Mesh> meshRecs;
+	std::vector<std::vector<void*>> meshOwned;
+	std::vector<size_t> meshBytes;
+	std::vector<Object> objectRecs;
+	std::vector<rtx_object> objectDescs;
+	void* sphereLeafDev = nullptr;     // the spheres' entry of meshLeaves once an edit has rebuilt it
+	void* flatScratch = nullptr; size_t flatScratchBytes = 0;      // rtx_scene_update_mesh: the device flatten's scratch (rtx_flatten.hip)
+	float editMs[4] = { 0, 0, 0, 0 };  // the last rtx_scene_update_mesh: build, read-back + flatten + upload, sources + estimate queued, whole call (host wall ms)
 	size_t sceneBytes = 0;        // bytes of scene data resident in HBM (nodes, leaf references, shading arrays, maps, skybox)
 	Params params;                // template of the kernel argument block
 	bool stats = false;
@@ -706,6 +718,121 @@ int flattenMesh(const rtx_mesh& m, bool pruneWanted, FlatMesh& out)
 	return RTX_OK;
 }
 
+// The geometry of mesh `mi` as rtx_scene_create uploads it: the flattened tree (flattenMesh), the leaf boxes of the cost estimate, the wide nodes,
+// the prune blocks and their source copies, the leaf references, the bundle-splitting terms.  Fills those fields of dm, the mesh's source
+// record, its leaves and its root box; every allocation goes to `owned`.  rtx_scene_update_mesh (rtx_edit.hip) runs it again on new triangles.
+int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, std::vector<void*>& owned, Mesh& dm, rtx_scene::SrcMesh& sm,
+                       rtx_scene::MeshLeaves& leaves, float bounds[6])
+{
+	FlatMesh flat;
+	{
+		const int frc = flattenMesh(m, s->knobs.prune, flat);
+		if (frc) return frc;
+	}
+	std::vector<Node>& nodes = flat.nodes;
+	std::vector<WideNode>& wide = flat.wide;
+	std::vector<PruneBlock>& prune = flat.prune;
+	const PruneRec rootRec = flat.rootRec;
+	const float vmaxMesh = flat.vmaxMesh;
+	const bool boxesRegular = flat.boxesRegular;
+	// leaf references in the reference's order, three parallel arrays padded by one wave
+	std::vector<RefA> refA((size_t)m.n_refs + 64);
+	std::vector<RefB> refB((size_t)m.n_refs + 64);
+	std::vector<RefC> refC((size_t)m.n_refs + 64);
+	memset(refA.data(), 0, refA.size() * sizeof(RefA)); memset(refB.data(), 0, refB.size() * sizeof(RefB)); memset(refC.data(), 0, refC.size() * sizeof(RefC));
+	for (uint32_t r = 0; r < m.n_refs; r++) {
+		if (m.refs[r] >= m.n_tris) return (fail(RTX_ERR_ARG, "leaf reference out of range"));
+		makeRef(m, r, refA[r], refB[r], refC[r]);
+	}
+	for (int c = 0; c < 6; c++) bounds[c] = m.n_nodes ? m.node_bounds[c] : 0.0f;
+	int rc;
+	if ((rc = upload(owned, nodes.data(), nodes.size(), &dm.nodes))) return rc;
+	{
+		// for the first-frame cost estimate: the TRUE box of every non-empty leaf's triangles and its reference count
+		std::vector<float> lb;
+		for (uint32_t i = 0; i < m.n_nodes; i++) {
+			if (m.leaf_count[i] <= 0) continue;
+			float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+			for (uint32_t r = (uint32_t)m.leaf_begin[i]; r < (uint32_t)(m.leaf_begin[i] + m.leaf_count[i]); r++) {
+				const float* p = m.tri_pos + (size_t)m.refs[r] * 9;
+				for (int v = 0; v < 9; v++) { lo[v % 3] = std::min(lo[v % 3], p[v]); hi[v % 3] = std::max(hi[v % 3], p[v]); }
+			}
+			if (!(std::isfinite(lo[0] + lo[1] + lo[2] + hi[0] + hi[1] + hi[2]))) continue;
+			lb.insert(lb.end(), { lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], (float)m.leaf_count[i], 0.0f });
+		}
+		const float* dev = nullptr;
+		if ((rc = upload(owned, lb.data(), lb.size(), &dev))) return rc;
+		leaves = { dev, (uint32_t)(lb.size() / 8) };
+	}
+	if ((rc = upload(owned, wide.data(), wide.size(), &dm.wide))) return rc;
+	dm.nWide = (uint32_t)wide.size();
+	// prune blocks: copy 0 (any ray) followed by the source copies (rtxd::PruneRec: the camera's, the point lights'), all
+	// equal to copy 0 until buildSources patches their P
+	sm = rtx_scene::SrcMesh();
+	const uint32_t nCopies = (s->knobs.sources && !prune.empty()) ? 2u + std::min<uint32_t>(nLights, kMaxSrcLights) : 1u;
+	if (!prune.empty()) {
+		PruneBlock* pb = nullptr;
+		if (hipMalloc((void**)&pb, (size_t)nCopies * prune.size() * sizeof(PruneBlock)) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (prune blocks)"));
+		owned.push_back(pb);
+		gUploadedBytes += (size_t)nCopies * prune.size() * sizeof(PruneBlock);
+		for (uint32_t c = 0; c < nCopies; c++)
+			if (hipMemcpy(pb + (size_t)c * prune.size(), prune.data(), prune.size() * sizeof(PruneBlock), hipMemcpyHostToDevice) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMemcpy (prune blocks)"));
+		dm.prune = pb;
+		if (nCopies > 1) { sm.base = pb; sm.nWide = (uint32_t)prune.size(); }
+	}
+	dm.vmax = vmaxMesh;
+	dm.rootRec = rootRec;
+	if (!(vmaxMesh < 0x1p40f)) { dm.prune = nullptr; dm.rootRec.h[0] = dm.rootRec.h[1] = dm.rootRec.h[2] = INFINITY; }      // (huge or non-finite coordinates: nothing is pruned)
+	if ((rc = upload(owned, refA.data(), refA.size(), &dm.refA))) return rc;
+	if ((rc = upload(owned, refB.data(), refB.size(), &dm.refB))) return rc;
+	if ((rc = upload(owned, refC.data(), refC.size(), &dm.refC))) return rc;
+	if (sm.base && vmaxMesh < 0x1p40f && m.n_refs) {
+		sm.nRefs = m.n_refs; sm.refA = dm.refA; sm.refB = dm.refB; sm.refC = dm.refC; sm.vmax = vmaxMesh; sm.meshIndex = mi;
+		if ((rc = upload(owned, flat.slotRange.data(), flat.slotRange.size(), &sm.slotRange))) return rc;
+		if (hipMalloc((void**)&sm.refP, ((size_t)m.n_refs + m.n_refs / 64 + 2) * sizeof(float)) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (source scratch)"));
+		owned.push_back(sm.refP);
+		sm.blockP = sm.refP + m.n_refs;
+	}
+	else sm.base = nullptr;
+	dm.nNodes = m.n_nodes; dm.nRefs = m.n_refs; dm.nTris = m.n_tris; dm.boxesRegular = boxesRegular ? 1u : 0u;
+	{
+		// mean edge length of the referenced triangles -> width above which a ray bundle is split (performance only)
+		double sum = 0; size_t cnt = 0;
+		const size_t stride = m.n_refs > 65536 ? m.n_refs / 65536 : 1;
+		for (size_t r = 0; r < m.n_refs; r += stride) {
+			const RefB& b = refB[r]; const RefC& c = refC[r];
+			const double l1 = std::sqrt((double)b.e1x * b.e1x + (double)b.e1y * b.e1y + (double)b.e1z * b.e1z);
+			const double l2 = std::sqrt((double)b.e2x * b.e2x + (double)c.e2y * c.e2y + (double)c.e2z * c.e2z);
+			if (std::isfinite(l1 + l2)) { sum += l1 + l2; cnt += 2; }
+		}
+		const float factor = s->knobs.fatFactor;
+		dm.fatRadius = cnt && factor > 0 ? (float)(sum / (double)cnt) * factor : INFINITY;
+		double rad = 0;
+		for (int c = 0; c < 3; c++) {
+			const double lo = m.n_nodes ? m.node_bounds[c] : 0.0, hi = m.n_nodes ? m.node_bounds[3 + c] : 0.0;
+			dm.centre[c] = (float)(0.5 * (lo + hi)); rad += 0.25 * (hi - lo) * (hi - lo);
+		}
+		dm.radius = (float)std::sqrt(rad);
+		if (!std::isfinite(dm.radius)) { dm.radius = 0; dm.fatRadius = INFINITY; }
+	}
+	return RTX_OK;
+}
+
+// The fields of a mesh object's record that derive from its mesh (rootBox from meshBounds).
+void meshObjectRecord(const rtx_scene* s, Object& d, const Mesh& dm, const rtx_scene::SrcMesh& sm)
+{
+	const float* bx = &s->meshBounds[(size_t)d.mesh * 6];
+	for (int c = 0; c < 3; c++) { d.rootBox[2 * c] = bx[c]; d.rootBox[2 * c + 1] = bx[3 + c]; }
+	d.fatRadius = dm.fatRadius; memcpy(d.centre, dm.centre, 12); d.radius = dm.radius;
+	d.meshFlags = (dm.nNodes ? 1u : 0u) | (dm.boxesRegular ? 2u : 0u) | (dm.nWide ? 4u : 0u);
+	d.nodes = dm.nodes; d.refA = dm.refA; d.refB = dm.refB; d.refC = dm.refC; d.wide = dm.wide; d.prune = dm.prune;
+	d.nNodes = dm.nNodes; d.vmax = dm.vmax;
+	d.srcStride = (dm.prune && sm.base) ? sm.nWide : 0u;
+	// The box test inflates a slot's true box by 216 dmax |orig - v0|_inf P (pruneAlive): with the origin about a mesh size away
+	// that is 216 P mesh sizes, so only meshes of small triangles gain from it; the plane test does not depend on P.
+	d.pruneBoxes = (dm.prune && std::isfinite(dm.rootRec.P) && dm.rootRec.P < 1.0f / 216.0f) ? 1u : 0u;
+}
+
 } // namespace
 
 extern "C" {
@@ -745,111 +872,32 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 
 	// meshes: nodes -> 32-byte records, leaf references -> (v0, e1, e2, tri) in three parallel arrays
 	std::vector<Mesh> meshes(desc->n_meshes);
+	s->meshOwned.resize(desc->n_meshes); s->meshBytes.assign(desc->n_meshes, 0);
 	for (uint32_t mi = 0; mi < desc->n_meshes; mi++) {
 		const rtx_mesh& m = desc->meshes[mi];
 		if (!m.node_bounds || !m.node_skip || !m.leaf_begin || !m.leaf_count || (m.n_refs && !m.refs) || (m.n_tris && (!m.tri_pos || !m.tri_nrm || !m.tri_uv)))
 			return bail(fail(RTX_ERR_ARG, "mesh arrays missing"));
 		if (m.normal_map && !m.tri_tb) return bail(fail(RTX_ERR_ARG, "normal map without tangents"));
-		FlatMesh flat;
-		{
-			const int frc = flattenMesh(m, s->knobs.prune, flat);
-			if (frc) return bail(frc);
-		}
-		std::vector<Node>& nodes = flat.nodes;
-		std::vector<WideNode>& wide = flat.wide;
-		std::vector<PruneBlock>& prune = flat.prune;
-		const PruneRec rootRec = flat.rootRec;
-		const float vmaxMesh = flat.vmaxMesh;
-		const bool boxesRegular = flat.boxesRegular;
-		// leaf references in the reference's order, three parallel arrays padded by one wave
-		std::vector<RefA> refA((size_t)m.n_refs + 64);
-		std::vector<RefB> refB((size_t)m.n_refs + 64);
-		std::vector<RefC> refC((size_t)m.n_refs + 64);
-		memset(refA.data(), 0, refA.size() * sizeof(RefA)); memset(refB.data(), 0, refB.size() * sizeof(RefB)); memset(refC.data(), 0, refC.size() * sizeof(RefC));
-		for (uint32_t r = 0; r < m.n_refs; r++) {
-			if (m.refs[r] >= m.n_tris) return bail(fail(RTX_ERR_ARG, "leaf reference out of range"));
-			makeRef(m, r, refA[r], refB[r], refC[r]);
-		}
-		for (int c = 0; c < 6; c++) s->meshBounds.push_back(m.n_nodes ? m.node_bounds[c] : 0.0f);
 		Mesh& dm = meshes[mi];
 		memset(&dm, 0, sizeof(dm));
-		int rc;
-		if ((rc = upload(s->owned, nodes.data(), nodes.size(), &dm.nodes))) return bail(rc);
-		{
-			// for the first-frame cost estimate: the TRUE box of every non-empty leaf's triangles and its reference count
-			std::vector<float> lb;
-			for (uint32_t i = 0; i < m.n_nodes; i++) {
-				if (m.leaf_count[i] <= 0) continue;
-				float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-				for (uint32_t r = (uint32_t)m.leaf_begin[i]; r < (uint32_t)(m.leaf_begin[i] + m.leaf_count[i]); r++) {
-					const float* p = m.tri_pos + (size_t)m.refs[r] * 9;
-					for (int v = 0; v < 9; v++) { lo[v % 3] = std::min(lo[v % 3], p[v]); hi[v % 3] = std::max(hi[v % 3], p[v]); }
-				}
-				if (!(std::isfinite(lo[0] + lo[1] + lo[2] + hi[0] + hi[1] + hi[2]))) continue;
-				lb.insert(lb.end(), { lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], (float)m.leaf_count[i], 0.0f });
-			}
-			const float* dev = nullptr;
-			if ((rc = upload(s->owned, lb.data(), lb.size(), &dev))) return bail(rc);
-			s->meshLeaves.push_back({ dev, (uint32_t)(lb.size() / 8) });
-		}
-		if ((rc = upload(s->owned, wide.data(), wide.size(), &dm.wide))) return bail(rc);
-		dm.nWide = (uint32_t)wide.size();
-		// prune blocks: copy 0 (any ray) followed by the source copies (rtxd::PruneRec: the camera's, the point lights'), all
-		// equal to copy 0 until buildSources patches their P
 		rtx_scene::SrcMesh sm;
-		const uint32_t nCopies = (s->knobs.sources && !prune.empty()) ? 2u + std::min<uint32_t>(desc->n_lights, kMaxSrcLights) : 1u;
-		if (!prune.empty()) {
-			PruneBlock* pb = nullptr;
-			if (hipMalloc((void**)&pb, (size_t)nCopies * prune.size() * sizeof(PruneBlock)) != hipSuccess) return bail(fail(RTX_ERR_DEVICE, "hipMalloc (prune blocks)"));
-			s->owned.push_back(pb);
-			gUploadedBytes += (size_t)nCopies * prune.size() * sizeof(PruneBlock);
-			for (uint32_t c = 0; c < nCopies; c++)
-				if (hipMemcpy(pb + (size_t)c * prune.size(), prune.data(), prune.size() * sizeof(PruneBlock), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(RTX_ERR_DEVICE, "hipMemcpy (prune blocks)"));
-			dm.prune = pb;
-			if (nCopies > 1) { sm.base = pb; sm.nWide = (uint32_t)prune.size(); }
-		}
-		dm.vmax = vmaxMesh;
-		dm.rootRec = rootRec;
-		if (!(vmaxMesh < 0x1p40f)) { dm.prune = nullptr; dm.rootRec.h[0] = dm.rootRec.h[1] = dm.rootRec.h[2] = INFINITY; }      // (huge or non-finite coordinates: nothing is pruned)
-		if ((rc = upload(s->owned, refA.data(), refA.size(), &dm.refA))) return bail(rc);
-		if ((rc = upload(s->owned, refB.data(), refB.size(), &dm.refB))) return bail(rc);
-		if ((rc = upload(s->owned, refC.data(), refC.size(), &dm.refC))) return bail(rc);
-		if (sm.base && vmaxMesh < 0x1p40f && m.n_refs) {
-			sm.nRefs = m.n_refs; sm.refA = dm.refA; sm.refB = dm.refB; sm.refC = dm.refC; sm.vmax = vmaxMesh; sm.meshIndex = mi;
-			if ((rc = upload(s->owned, flat.slotRange.data(), flat.slotRange.size(), &sm.slotRange))) return bail(rc);
-			if (hipMalloc((void**)&sm.refP, ((size_t)m.n_refs + m.n_refs / 64 + 2) * sizeof(float)) != hipSuccess) return bail(fail(RTX_ERR_DEVICE, "hipMalloc (source scratch)"));
-			s->owned.push_back(sm.refP);
-			sm.blockP = sm.refP + m.n_refs;
-		}
-		else sm.base = nullptr;
+		rtx_scene::MeshLeaves leaves{ nullptr, 0 };
+		float bounds[6];
+		const size_t bytes0 = gUploadedBytes;
+		int rc;
+		if ((rc = uploadMeshGeometry(s, m, mi, desc->n_lights, s->meshOwned[mi], dm, sm, leaves, bounds))) return bail(rc);
+		s->meshBounds.insert(s->meshBounds.end(), bounds, bounds + 6);
+		s->meshLeaves.push_back(leaves);
 		s->srcMeshes.push_back(sm);
-		if ((rc = upload(s->owned, m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm))) return bail(rc);
+		if ((rc = upload(s->meshOwned[mi], m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm))) return bail(rc);
+		const size_t bytesUv = gUploadedBytes;
 		if ((rc = upload(s->owned, m.tri_uv, (size_t)m.n_tris * 6, &dm.uv))) return bail(rc);
-		if ((rc = upload(s->owned, m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb))) return bail(rc);
+		const size_t bytesTb = gUploadedBytes;
+		if ((rc = upload(s->meshOwned[mi], m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb))) return bail(rc);
+		s->meshBytes[mi] = (bytesUv - bytes0) + (gUploadedBytes - bytesTb);
 		if ((rc = upload(s->owned, m.diffuse_map, (size_t)m.diffuse_w * m.diffuse_h * 3, &dm.diffuse))) return bail(rc);
 		if ((rc = upload(s->owned, m.normal_map, (size_t)m.normal_w * m.normal_h * 3, &dm.normal))) return bail(rc);
 		if ((rc = upload(s->owned, m.specular_map, (size_t)m.specular_w * m.specular_h, &dm.specular))) return bail(rc);
-		dm.nNodes = m.n_nodes; dm.nRefs = m.n_refs; dm.nTris = m.n_tris; dm.boxesRegular = boxesRegular ? 1u : 0u;
-		{
-			// mean edge length of the referenced triangles -> width above which a ray bundle is split (performance only)
-			double sum = 0; size_t cnt = 0;
-			const size_t stride = m.n_refs > 65536 ? m.n_refs / 65536 : 1;
-			for (size_t r = 0; r < m.n_refs; r += stride) {
-				const RefB& b = refB[r]; const RefC& c = refC[r];
-				const double l1 = std::sqrt((double)b.e1x * b.e1x + (double)b.e1y * b.e1y + (double)b.e1z * b.e1z);
-				const double l2 = std::sqrt((double)b.e2x * b.e2x + (double)c.e2y * c.e2y + (double)c.e2z * c.e2z);
-				if (std::isfinite(l1 + l2)) { sum += l1 + l2; cnt += 2; }
-			}
-			const float factor = s->knobs.fatFactor;
-			dm.fatRadius = cnt && factor > 0 ? (float)(sum / (double)cnt) * factor : INFINITY;
-			double rad = 0;
-			for (int c = 0; c < 3; c++) {
-				const double lo = m.n_nodes ? m.node_bounds[c] : 0.0, hi = m.n_nodes ? m.node_bounds[3 + c] : 0.0;
-				dm.centre[c] = (float)(0.5 * (lo + hi)); rad += 0.25 * (hi - lo) * (hi - lo);
-			}
-			dm.radius = (float)std::sqrt(rad);
-			if (!std::isfinite(dm.radius)) { dm.radius = 0; dm.fatRadius = INFINITY; }
-		}
 		dm.dW = m.diffuse_w; dm.dH = m.diffuse_h; dm.nW = m.normal_w; dm.nH = m.normal_h; dm.sW = m.specular_w; dm.sH = m.specular_h;
 	}
 	std::vector<Object> objs(desc->n_objects);
@@ -873,16 +921,7 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		d.r2 = o.radius2; d.mesh = o.mesh;
 		if (o.type == RTX_OBJ_MESH) {
 			const Mesh& dm = meshes[o.mesh];
-			const rtx_mesh& hm = desc->meshes[o.mesh];
-			for (int c = 0; c < 3; c++) { d.rootBox[2 * c] = hm.n_nodes ? hm.node_bounds[c] : 0.0f; d.rootBox[2 * c + 1] = hm.n_nodes ? hm.node_bounds[3 + c] : 0.0f; }
-			d.fatRadius = dm.fatRadius; memcpy(d.centre, dm.centre, 12); d.radius = dm.radius;
-			d.meshFlags = (hm.n_nodes ? 1u : 0u) | (dm.boxesRegular ? 2u : 0u) | (dm.nWide ? 4u : 0u);
-			d.nodes = dm.nodes; d.refA = dm.refA; d.refB = dm.refB; d.refC = dm.refC; d.wide = dm.wide; d.prune = dm.prune;
-			d.nNodes = dm.nNodes; d.vmax = dm.vmax;
-			d.srcStride = (dm.prune && s->srcMeshes[o.mesh].base) ? s->srcMeshes[o.mesh].nWide : 0u;
-			// The box test inflates a slot's true box by 216 dmax |orig - v0|_inf P (pruneAlive): with the origin about a mesh size away
-			// that is 216 P mesh sizes, so only meshes of small triangles gain from it; the plane test does not depend on P.
-			d.pruneBoxes = (dm.prune && std::isfinite(dm.rootRec.P) && dm.rootRec.P < 1.0f / 216.0f) ? 1u : 0u;
+			meshObjectRecord(s, d, dm, s->srcMeshes[o.mesh]);
 			if (d.pruneBoxes && s->knobs.pruneBoxes != 0) s->boxPrune = true;
 			if (s->knobs.pruneBoxes > 0 && dm.prune) s->boxPrune = true;
 		}
@@ -926,6 +965,8 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 	int rc;
 	if ((rc = upload(s->owned, meshes.data(), meshes.size(), &s->params.meshes))) return bail(rc);
 	if ((rc = upload(s->owned, objs.data(), objs.size(), &s->params.objects))) return bail(rc);
+	s->meshRecs = meshes; s->objectRecs = objs;
+	s->objectDescs.assign(desc->objects, desc->objects + desc->n_objects);
 	if ((rc = upload(s->owned, lights.data(), lights.size(), &s->params.lights))) return bail(rc);
 	s->params.nObjects = desc->n_objects; s->params.nLights = desc->n_lights;
 	s->params.nSrcLights = s->knobs.sources ? std::min<uint32_t>(desc->n_lights, kMaxSrcLights) : 0u;
@@ -954,6 +995,9 @@ void rtx_scene_destroy(rtx_scene* s)
 	(void)hipSetDevice(s->device);
 	(void)hipDeviceSynchronize();
 	for (void* p : s->owned) (void)hipFree(p);
+	for (auto& v : s->meshOwned) for (void* p : v) (void)hipFree(p);
+	if (s->sphereLeafDev) (void)hipFree(s->sphereLeafDev);
+	if (s->flatScratch) (void)hipFree(s->flatScratch);
 	if (s->frames) (void)hipFree(s->frames);
 	if (s->tileCost) { (void)hipFree(s->tileCost); (void)hipFree(s->items); }
 	if (s->needSlab) (void)hipFree(s->needSlab);
@@ -2251,3 +2295,6 @@ int rtx_vec_probe(int device, int op, uint32_t n, const float* a, const float* b
 
 // multi-GPU: RCCL communicator + frame gather (uses fail / HIPCHK above)
 #include "rtx_comm.hip"
+
+// editing a live scene (include/rtx_scene_edit.h; uses the scene's internals above and the device build of rtx_bvh.hip)
+#include "rtx_edit.hip"

@@ -705,7 +705,7 @@ int scanExclusive(uint32_t* data, uint32_t n, uint32_t* tmp, hipStream_t st, uin
 
 // The build as one persistent launch (bvhq).  RTX_OK with *out = nullptr: not done here (a pool ran out, the watchdog fired, RTX_BVH_BUILD=levels) -- the
 // caller builds level by level.
-int buildQueued(const float* tri_pos, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out)
+int buildQueued(const float* tri_pos_dev, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out)
 {
 	using namespace bvhq;
 	*out = nullptr;
@@ -737,7 +737,7 @@ int buildQueued(const float* tri_pos, uint32_t n_tris, const float* root_lo, con
 	hipEvent_t ev0, ev1;
 	HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
 	struct EvCleanup { hipEvent_t a, b; ~EvCleanup() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evCleanup{ ev0, ev1 };
-	if (n_tris) HIPCHK(hipMemcpy(dPos, tri_pos, (size_t)n_tris * 9 * sizeof(float), hipMemcpyHostToDevice));
+	if (n_tris) HIPCHK(hipMemcpyAsync(dPos, tri_pos_dev, (size_t)n_tris * 9 * sizeof(float), hipMemcpyDeviceToDevice, st));
 	uint32_t launches = 0;
 	HIPCHK(hipEventRecord(ev0, st));
 	HIPCHK(hipMemsetAsync(dNodes, 0, szNodes, st));
@@ -777,13 +777,9 @@ int buildQueued(const float* tri_pos, uint32_t n_tris, const float* root_lo, con
 	return RTX_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int rtx_bvh_build(const float* tri_pos, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out)
+// The arguments of a build, checked; selects the device.
+int checkBuildArgs(const float* tri_pos, uint32_t n_tris, const float* root_lo, const float* root_hi, int device, rtx_bvh** out)
 {
-	using namespace bvhb;
 	if (!out) return fail(RTX_ERR_ARG, "out is NULL");
 	*out = nullptr;
 	if ((n_tris && !tri_pos) || !root_lo || !root_hi) return fail(RTX_ERR_ARG, "tri_pos / root bounds missing");
@@ -793,10 +789,23 @@ int rtx_bvh_build(const float* tri_pos, uint32_t n_tris, const float* root_lo, c
 	if (device < 0 || device >= nDev) return fail(RTX_ERR_ARG, "bad device index");
 	HIPCHK(hipSetDevice(device));
 	if (!std::isfinite(root_lo[0] + root_lo[1] + root_lo[2] + root_hi[0] + root_hi[1] + root_hi[2])) return fail(RTX_ERR_ARG, "root bounds are not finite");
+	return RTX_OK;
+}
+
+} // namespace
+
+// The build from triangles already in device memory (n_tris x 9 floats on `device`): one persistent launch (bvhq), level by level only when its
+// pools ran out or its watchdog fired.  rtx_bvh_build (host triangles) and rtx_scene_update_mesh (rtx_edit.hip) both end here.
+int rtxBvhBuildDevice(const float* tri_pos_dev, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out)
+{
+	using namespace bvhb;
 	{
-		// one persistent launch (bvhq); level by level (below) only when its pools ran out or its watchdog fired
+		const int rc = checkBuildArgs(tri_pos_dev, n_tris, root_lo, root_hi, device, out);
+		if (rc) return rc;
+	}
+	{
 		rtx_bvh* q = nullptr;
-		const int rcq = buildQueued(tri_pos, n_tris, root_lo, root_hi, ac_penalty, device, &q);
+		const int rcq = buildQueued(tri_pos_dev, n_tris, root_lo, root_hi, ac_penalty, device, &q);
 		if (rcq) return rcq;
 		if (q) { *out = q; return RTX_OK; }
 	}
@@ -828,7 +837,7 @@ int rtx_bvh_build(const float* tri_pos, uint32_t n_tris, const float* root_lo, c
 	float* dPos = nullptr; float* dExt = nullptr;
 	HIPCHK(dalloc((void**)&dPos, (size_t)n_tris * 9 * sizeof(float)));
 	HIPCHK(dalloc((void**)&dExt, (size_t)n_tris * 6 * sizeof(float)));
-	if (n_tris) HIPCHK(hipMemcpy(dPos, tri_pos, (size_t)n_tris * 9 * sizeof(float), hipMemcpyHostToDevice));
+	if (n_tris) HIPCHK(hipMemcpyAsync(dPos, tri_pos_dev, (size_t)n_tris * 9 * sizeof(float), hipMemcpyDeviceToDevice, st));
 	uint32_t* dFlags = nullptr;      // [0] unfinished nodes of the running bisection
 	HIPCHK(dalloc((void**)&dFlags, 256 * 4));
 	uint32_t launches = 0;
@@ -952,6 +961,23 @@ int rtx_bvh_build(const float* tri_pos, uint32_t n_tris, const float* root_lo, c
 	b->launches = launches;
 	*out = b;
 	return RTX_OK;
+}
+
+extern "C" {
+
+int rtx_bvh_build(const float* tri_pos, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out)
+{
+	int rc = checkBuildArgs(tri_pos, n_tris, root_lo, root_hi, device, out);
+	if (rc) return rc;
+	// the host triangles in device memory once; the build reads them from there
+	float* dTris = nullptr;
+	if (n_tris) {
+		HIPCHK(hipMalloc((void**)&dTris, (size_t)n_tris * 9 * sizeof(float)));
+		if (hipMemcpy(dTris, tri_pos, (size_t)n_tris * 9 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dTris); return fail(RTX_ERR_DEVICE, "hipMemcpy (triangles)"); }
+	}
+	rc = rtxBvhBuildDevice(dTris, n_tris, root_lo, root_hi, ac_penalty, device, out);
+	if (dTris) (void)hipFree(dTris);
+	return rc;
 }
 
 int rtx_bvh_build_mode(int mode) { if (mode < 0 || mode > 2) return fail(RTX_ERR_ARG, "rtx_bvh_build_mode: 0, 1 or 2"); gBvhBuildMode = mode; return RTX_OK; }

@@ -81,6 +81,20 @@ public:
 	std::vector<Triangle> allTris;
 	std::unique_ptr<AccelerationStructure> ac;
 
+	// What the loader read, kept so that the mesh can be placed again (Scene::moveObject): the OBJ's vertices and normals as read, how many
+	// of them existed when the first face was read (only those are placed -- later ones stay as read, as in the reference), the vertices'
+	// box at that moment, the uv, and the corners of every triangle (0-based; n[0] / t[0] = -1: the face gave no normals / no uv).
+	struct Corners { uint32_t v[3]; int32_t n[3], t[3]; };
+	std::vector<Vec3f> objP, objN;
+	std::vector<Vec2f> objT;
+	std::vector<Corners> corners;
+	size_t placedP = 0, placedN = 0;
+	Vec3f objLo, objHi;
+	bool hasFaces = false;
+	// allTris from the above with the current pos / rot / size, and the root box of `ac` (the loader's own placement, objects.cpp:282-331)
+	void place(const Options& options);
+	bool treeOnDevice = false;      // the GPU scene holds the structure of allTris and `ac` an older one (Scene::syncTrees)
+
 	bool diffuseMapLoaded = false; int diffuseMapWidth = 0, diffuseMapHeight = 0; std::vector<Vec3f> diffuseMap;
 	bool normalMapLoaded = false; int normalMapWidth = 0, normalMapHeight = 0; std::vector<Vec3f> normalMap;
 	bool specularMapLoaded = false; int specularMapWidth = 0, specularMapHeight = 0; std::vector<float> specularMap;

@@ -75,6 +75,15 @@ public:
 	int device = 0;
 	rtx_scene* gpu();                          // flattens + uploads on first use; LOG_ERROR()s without a GPU
 	void invalidateView();                     // call after changing options.width/height, camera, flags
+	// Places object `index` as its [object] block would with these values (NULL: unchanged): a mesh takes pos / rot / size (its vertices are
+	// placed again by the loader's own code), a sphere pos / radius, a plane pos / normal; any other key is an error.  With a live GPU scene
+	// the new triangles go up and the device rebuilds the structure (rtx_scene_set_object / rtx_scene_update_mesh, include/rtx_scene_edit.h);
+	// without one the host structure is built again as the loader builds it.
+	void moveObject(size_t index, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3);
+	void moveObjectApply(size_t index, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3, double (*now)());
+	void syncTrees();                          // meshes moved on the GPU: their `ac` read back from the device (done by every reader of `ac`)
+	// host wall ms of the last moveObject: {placement (Mesh::place), upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
+	double lastMoveMs[4] = { 0, 0, 0, 0 };
 	// Multi-GPU (one process per GPU): with a communicator of the C ABI attached (rtx_comm_create), render() renders this
 	// rank's rows only and collects the image on rank 0 (rtx_gather), which writes the file.
 	void attachComm(rtx_comm* comm, int nRanks, int rank);

@@ -98,6 +98,7 @@ void rah_set_ac_build_device(int device) { options::acBuildDevice = device; }
 int rah_bvh_build_info(void* h, int obj, int* onDevice, float* ms)
 {
 	Scene* s = (Scene*)h;
+	if (guarded<int>(-1, [&] { s->syncTrees(); return 0; }) != 0) return -1;
 	if (obj < 0 || obj >= (int)s->objects.size() || s->objects[obj]->objectType != ObjectType::Mesh) return -1;
 	const Mesh& m = static_cast<const Mesh&>(*s->objects[obj]);
 	if (!m.ac) return -1;
@@ -109,6 +110,7 @@ int rah_bvh_build_info(void* h, int obj, int* onDevice, float* ms)
 int rah_bvh_counts(void* h, int obj, long long* c)
 {
 	Scene* s = (Scene*)h;
+	if (guarded<int>(-1, [&] { s->syncTrees(); return 0; }) != 0) return -1;
 	if (obj < 0 || obj >= (int)s->objects.size() || s->objects[obj]->objectType != ObjectType::Mesh) return -1;
 	const Mesh& m = static_cast<const Mesh&>(*s->objects[obj]);
 	if (!m.ac) return -1;
@@ -120,6 +122,7 @@ int rah_bvh_counts(void* h, int obj, long long* c)
 int rah_bvh_dump(void* h, int obj, float* bounds, int32_t* skip, int32_t* leafBegin, int32_t* leafCount, uint32_t* refs)
 {
 	Scene* s = (Scene*)h;
+	if (guarded<int>(-1, [&] { s->syncTrees(); return 0; }) != 0) return -1;
 	if (obj < 0 || obj >= (int)s->objects.size() || s->objects[obj]->objectType != ObjectType::Mesh) return -1;
 	const Mesh& m = static_cast<const Mesh&>(*s->objects[obj]);
 	if (!m.ac) return -1;
@@ -223,6 +226,32 @@ int rah_load_bmp(const char* path, int* w, int* h, unsigned char* out, int cap)
 		delete[] d;
 		return need > 0x7fffffffu ? -2 : (int)need;
 	});
+}
+
+// Places object `obj` again as its [object] block would with these values (Scene::moveObject; NULL = unchanged): mesh pos3 / rot3 / size3,
+// sphere pos3 / radius1, plane pos3 / normal3.  0, or -1 with rah_last_error (bad index, a key the type does not have, a device error).
+int rah_object_move(void* h, int obj, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3)
+{
+	return guarded<int>(-1, [&] {
+		if (obj < 0) { noteError("moveObject: object index out of range"); LOG_ERROR(); }
+		((Scene*)h)->moveObject((size_t)obj, pos3, rot3, size3, radius1, normal3);
+		return 0;
+	});
+}
+
+// RTX_OBJ_* of object `obj` (-1: no such object)
+int rah_object_type(void* h, int obj)
+{
+	Scene* s = (Scene*)h;
+	if (obj < 0 || obj >= (int)s->objects.size()) return -1;
+	const ObjectType t = s->objects[obj]->objectType;
+	return t == ObjectType::Sphere ? RTX_OBJ_SPHERE : t == ObjectType::Plane ? RTX_OBJ_PLANE : t == ObjectType::Mesh ? RTX_OBJ_MESH : -1;
+}
+
+// host wall ms of the last rah_object_move: {placement, upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
+void rah_object_move_times(void* h, float* ms4)
+{
+	for (int k = 0; k < 4; k++) ms4[k] = (float)((Scene*)h)->lastMoveMs[k];
 }
 
 // Numeric digest of objects and lights (for loader tests): per object 16 floats

@@ -224,26 +224,17 @@ void tangentFrame(Triangle& t)                                                 /
 
 } // namespace
 
-bool Mesh::loadOBJ(const std::string& filename, const Options& options)
+// First face: fit the vertices into `size` (keeping proportions), centre, rotate, translate; pin flat axes; derive the root box from
+// the rotated size vector (objects.cpp:282-331).  Then the triangle fans of the faces (objects.cpp:344-373) over the placed vertices.
+void Mesh::place(const Options& options)
 {
+	allTris.clear();
+	if (!hasFaces) return;
 	const Matrix44f R = Matrix44f::fromEulerDegrees(rot);
-	Timer timer("OBJ loading");
-	std::ifstream in(filename);
-	if (!in.good()) {
-		std::cout << "Error, failed to load obj, filename: " << filename << '\n';
-		return false;
-	}
-	if (options::enableOutput) std::cout << "Mesh: " << filename << '\n';
-	ac = std::make_unique<AccelerationStructure>();
-	std::vector<Vec3f> P, N;
-	std::vector<Vec2f> T;
-	const float big = std::numeric_limits<float>::max(), tiny = std::numeric_limits<float>::min();
-	Vec3f lo(big), hi(tiny);              // `max` starts at the smallest positive float (objects.cpp:231)
-	bool placed = false;
-
-	// First face: fit the vertices into `size` (keeping proportions), centre, rotate, translate; pin flat axes;
-	// derive the root box from the rotated size vector (objects.cpp:282-331).
-	auto place = [&]() {
+	std::vector<Vec3f> P(objP), N(objN);
+	const std::vector<Vec2f>& T = objT;
+	{
+		const Vec3f lo = objLo, hi = objHi;
 		const Vec3f range = hi - lo;
 		Vec3f ns = size;
 		if (!(range.x < options.bias || range.y < options.bias || range.z < options.bias)) {
@@ -253,7 +244,8 @@ bool Mesh::loadOBJ(const std::string& filename, const Options& options)
 			else if (m == stretch.y) { ns.x = ns.y / (range.y / range.x); ns.z = ns.y / (range.y / range.z); }
 			else { ns.x = ns.z / (range.z / range.x); ns.y = ns.z / (range.z / range.y); }
 		}
-		for (Vec3f& v : P) {
+		for (size_t i = 0; i < placedP; ++i) {
+			Vec3f& v = P[i];
 			v.x = ns.x * ((v.x - lo.x) / range.x - 0.5f);
 			v.y = ns.y * ((v.y - lo.y) / range.y - 0.5f);
 			v.z = ns.z * ((v.z - lo.z) / range.z - 0.5f);
@@ -263,11 +255,45 @@ bool Mesh::loadOBJ(const std::string& filename, const Options& options)
 			if (range.y < options.bias) v.y = pos.y;
 			if (range.z < options.bias) v.z = pos.z;
 		}
-		for (Vec3f& n : N) n = R.multVecMatrix(n);
+		for (size_t i = 0; i < placedN; ++i) N[i] = R.multVecMatrix(N[i]);
 		Vec3f ext = R.multVecMatrix(ns);
 		ext = Vec3f(std::fabs(ext.x), std::fabs(ext.y), std::fabs(ext.z));
 		ac->setBounds(pos - ext / 2, pos + ext / 2);
-	};
+	}
+	allTris.reserve(corners.size());
+	for (const Corners& c : corners) {
+		Triangle t;
+		t.a = P[c.v[0]]; t.b = P[c.v[1]]; t.c = P[c.v[2]];
+		faceNormal(t);
+		if (c.n[0] >= 0) {
+			t.n_a = N[c.n[0]]; t.n_b = N[c.n[1]]; t.n_c = N[c.n[2]];
+			if (c.t[0] >= 0) {
+				t.t_a = T[c.t[0]]; t.t_b = T[c.t[1]]; t.t_c = T[c.t[2]];
+				tangentFrame(t);
+			}
+		}
+		allTris.push_back(t);
+	}
+}
+
+bool Mesh::loadOBJ(const std::string& filename, const Options& options)
+{
+	Timer timer("OBJ loading");
+	std::ifstream in(filename);
+	if (!in.good()) {
+		std::cout << "Error, failed to load obj, filename: " << filename << '\n';
+		return false;
+	}
+	if (options::enableOutput) std::cout << "Mesh: " << filename << '\n';
+	ac = std::make_unique<AccelerationStructure>();
+	objP.clear(); objN.clear(); objT.clear(); corners.clear(); placedP = placedN = 0; hasFaces = false;
+	std::vector<Vec3f>& P = objP;
+	std::vector<Vec3f>& N = objN;
+	std::vector<Vec2f>& T = objT;
+	const float big = std::numeric_limits<float>::max(), tiny = std::numeric_limits<float>::min();
+	Vec3f lo(big), hi(tiny);              // `max` starts at the smallest positive float (objects.cpp:231)
+	bool placed = false;
+	// (the vertices are placed at the first face -- Mesh::place, run once the whole file is read: the faces only keep their corners)
 
 	// The file in one read, its lines in place (a 250 000-triangle OBJ is 18 MB and 630 000 lines: getline + sscanf per line took
 	// twice as long as the rest of the scene load).  Same tokens as before: a line ends at '\n' (a '\r' stays part of it), a '#' ends
@@ -328,7 +354,7 @@ bool Mesh::loadOBJ(const std::string& filename, const Options& options)
 			T.emplace_back(c[0], c[1]);
 		}
 		else if (!strcmp(tag, "f")) {
-			if (!placed) { placed = true; place(); }
+			if (!placed) { placed = true; hasFaces = true; placedP = P.size(); placedN = N.size(); objLo = lo; objHi = hi; }
 			int slashes = 0;
 			for (const char* p = rest; *p; ++p) slashes += (*p == '/');
 			if (slashes != 0 && slashes % 2 != 0) {
@@ -345,22 +371,21 @@ bool Mesh::loadOBJ(const std::string& filename, const Options& options)
 					if (n > 0) ni.push_back(n);
 				}
 			}
-			// triangle fan (objects.cpp:344-373)
+			// triangle fan (objects.cpp:344-373): the corners, checked against what has been read so far as the reference's lookups are
 			for (size_t k = 1; k + 1 < vi.size(); ++k) {
-				Triangle t;
-				t.a = P.at(vi[0] - 1); t.b = P.at(vi[k] - 1); t.c = P.at(vi[k + 1] - 1);
-				faceNormal(t);
+				Corners c;
+				const size_t at[3] = { 0, k, k + 1 };
+				for (int j = 0; j < 3; ++j) { (void)P.at(vi[at[j]] - 1); c.v[j] = (uint32_t)(vi[at[j]] - 1); c.n[j] = c.t[j] = -1; }
 				if (!ni.empty()) {
-					t.n_a = N.at(ni.at(0) - 1); t.n_b = N.at(ni.at(k) - 1); t.n_c = N.at(ni.at(k + 1) - 1);
-					if (!ti.empty()) {
-						t.t_a = T.at(ti.at(0) - 1); t.t_b = T.at(ti.at(k) - 1); t.t_c = T.at(ti.at(k + 1) - 1);
-						tangentFrame(t);
-					}
+					for (int j = 0; j < 3; ++j) { (void)N.at(ni.at(at[j]) - 1); c.n[j] = (int32_t)(ni[at[j]] - 1); }
+					if (!ti.empty())
+						for (int j = 0; j < 3; ++j) { (void)T.at(ti.at(at[j]) - 1); c.t[j] = (int32_t)(ti[at[j]] - 1); }
 				}
-				allTris.push_back(t);
+				corners.push_back(c);
 			}
 		}
 	}
+	place(options);
 	if (!ac->setup(allTris, options)) return false;
 	stats::meshCount += allTris.size();
 	return true;

@@ -5,6 +5,7 @@
 #include "scene.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -13,6 +14,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../../include/rtx.h"
+#include "../../../include/rtx_debug.h"
+#include "../../../include/rtx_scene_edit.h"
 #include "stats.h"
 #include "timer.h"
 #include "util.h"
@@ -351,6 +354,21 @@ namespace {
 
 void put3(float* d, const Vec3f& v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }
 
+// the object's record in the description (mesh: its index among the meshes)
+rtx_object objectRecord(const Object& o, int32_t mesh)
+{
+	rtx_object ro{};
+	ro.type = o.objectType == ObjectType::Sphere ? RTX_OBJ_SPHERE : (o.objectType == ObjectType::Plane ? RTX_OBJ_PLANE : RTX_OBJ_MESH);
+	ro.material = (int32_t)o.materialType;
+	put3(ro.pos, o.pos); put3(ro.color, o.color);
+	ro.ior = o.indexOfRefraction; ro.ambient = o.ambient; ro.diffuse = o.diffuse; ro.specular = o.specular; ro.n_specular = o.nSpecular;
+	ro.mesh = -1;
+	if (o.objectType == ObjectType::Sphere) ro.radius2 = static_cast<const Sphere&>(o).r2;
+	else if (o.objectType == ObjectType::Plane) put3(ro.normal, static_cast<const Plane&>(o).normal);
+	else ro.mesh = mesh;
+	return ro;
+}
+
 void fillView(Scene& sc, rtx_view& v)
 {
 	sc.camera.ensureMatrix();
@@ -368,22 +386,15 @@ void fillView(Scene& sc, rtx_view& v)
 
 FlatScene* flattenScene(Scene& sc)
 {
+	sc.syncTrees();
 	auto* fs = new FlatScene;
 	fillView(sc, fs->desc.view);
 	for (auto& op : sc.objects) {
 		const Object& o = *op;
-		rtx_object ro{};
-		ro.type = o.objectType == ObjectType::Sphere ? RTX_OBJ_SPHERE : (o.objectType == ObjectType::Plane ? RTX_OBJ_PLANE : RTX_OBJ_MESH);
-		ro.material = (int32_t)o.materialType;
-		put3(ro.pos, o.pos); put3(ro.color, o.color);
-		ro.ior = o.indexOfRefraction; ro.ambient = o.ambient; ro.diffuse = o.diffuse; ro.specular = o.specular; ro.n_specular = o.nSpecular;
-		ro.mesh = -1;
-		if (o.objectType == ObjectType::Sphere) ro.radius2 = static_cast<const Sphere&>(o).r2;
-		else if (o.objectType == ObjectType::Plane) put3(ro.normal, static_cast<const Plane&>(o).normal);
-		else {
+		rtx_object ro = objectRecord(o, (int32_t)fs->meshes.size());
+		if (o.objectType == ObjectType::Mesh) {
 			const Mesh& m = static_cast<const Mesh&>(o);
 			if (!m.ac) { std::cout << "Mesh without acceleration structure (OBJ failed to load)\n"; LOG_ERROR(); }
-			ro.mesh = (int32_t)fs->meshes.size();
 			fs->meshArrays.push_back(std::make_unique<FlatScene::MeshArrays>());
 			auto& A = *fs->meshArrays.back();
 			const auto& nodes = m.ac->nodes;
@@ -524,6 +535,148 @@ void hipCheck(hipError_t e, const char* what)
 	noteError(std::string(what) + ": " + hipGetErrorString(e));
 	LOG_ERROR();
 }
+}
+
+void Scene::moveObject(size_t index, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3)
+{
+	if (index >= objects.size()) { noteError("moveObject: object index out of range"); LOG_ERROR(); }
+	Object& o = *objects[index];
+	// the keys of the type's [object] block (scene.cpp:285-312)
+	const char* bad = nullptr;
+	if (o.objectType == ObjectType::Mesh) bad = radius1 ? "radius" : normal3 ? "normal" : nullptr;
+	else if (o.objectType == ObjectType::Sphere) bad = rot3 ? "rot" : size3 ? "size" : normal3 ? "normal" : nullptr;
+	else if (o.objectType == ObjectType::Plane) bad = rot3 ? "rot" : size3 ? "size" : radius1 ? "radius" : nullptr;
+	else bad = "pos";
+	if (bad) { noteError(std::string("moveObject: object ") + std::to_string(index) + " has no key " + bad); LOG_ERROR(); }
+	if (o.objectType == ObjectType::Mesh && !static_cast<Mesh&>(o).ac) { noteError("moveObject: mesh without acceleration structure"); LOG_ERROR(); }
+	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	for (double& t : lastMoveMs) t = 0;
+	// what a failed move puts back (the triangles by swapping, not copying)
+	const Vec3f keepPos = o.pos;
+	float keepR = 0, keepR2 = 0;
+	Vec3f keepNormal, keepRot, keepSize, keepBounds[2];
+	std::vector<Triangle> keepTris;
+	if (o.objectType == ObjectType::Sphere) { keepR = static_cast<Sphere&>(o).r; keepR2 = static_cast<Sphere&>(o).r2; }
+	if (o.objectType == ObjectType::Plane) keepNormal = static_cast<Plane&>(o).normal;
+	if (o.objectType == ObjectType::Mesh) {
+		auto& m = static_cast<Mesh&>(o);
+		keepRot = m.rot; keepSize = m.size; keepBounds[0] = m.ac->rootBounds[0]; keepBounds[1] = m.ac->rootBounds[1];
+		keepTris.swap(m.allTris);
+	}
+	auto restore = [&]() {
+		o.pos = keepPos;
+		if (o.objectType == ObjectType::Sphere) { static_cast<Sphere&>(o).r = keepR; static_cast<Sphere&>(o).r2 = keepR2; }
+		if (o.objectType == ObjectType::Plane) static_cast<Plane&>(o).normal = keepNormal;
+		if (o.objectType == ObjectType::Mesh) {
+			auto& m = static_cast<Mesh&>(o);
+			m.rot = keepRot; m.size = keepSize; m.ac->setBounds(keepBounds[0], keepBounds[1]);
+			m.allTris.swap(keepTris);
+		}
+	};
+	try {
+		moveObjectApply(index, pos3, rot3, size3, radius1, normal3, now);
+	}
+	catch (...) {
+		restore();
+		throw;
+	}
+}
+
+void Scene::moveObjectApply(size_t index, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3,
+                            double (*now)())
+{
+	Object& o = *objects[index];
+	if (pos3) o.pos = Vec3f(pos3[0], pos3[1], pos3[2]);
+	if (o.objectType == ObjectType::Sphere && radius1) {
+		auto& sp = static_cast<Sphere&>(o);
+		sp.r = radius1[0];
+		sp.r2 = sp.r * sp.r;          // as the loader computes it (scene.cpp:294)
+	}
+	if (o.objectType == ObjectType::Plane && normal3) static_cast<Plane&>(o).normal = Vec3f(normal3[0], normal3[1], normal3[2]);
+	int32_t meshIndex = -1;
+	if (o.objectType == ObjectType::Mesh) {
+		meshIndex = 0;
+		for (size_t i = 0; i < index; ++i) meshIndex += objects[i]->objectType == ObjectType::Mesh;
+		auto& m = static_cast<Mesh&>(o);
+		if (rot3) m.rot = Vec3f(rot3[0], rot3[1], rot3[2]);
+		if (size3) m.size = Vec3f(size3[0], size3[1], size3[2]);
+		const double t0 = now();
+		m.place(options);
+		lastMoveMs[0] = now() - t0;
+		if (!gpu_) {
+			m.treeOnDevice = false;
+			if (!m.ac->setup(m.allTris, options)) { noteError("moveObject: the acceleration structure could not be built"); LOG_ERROR(); }
+		}
+	}
+	if (!gpu_) return;
+	const rtx_object ro = objectRecord(o, meshIndex);
+	double t0 = now();
+	gpuCheck(rtx_scene_set_object(gpu_, (uint32_t)index, &ro), "rtx_scene_set_object");
+	lastMoveMs[2] = now() - t0;
+	if (o.objectType != ObjectType::Mesh) return;
+	auto& m = static_cast<Mesh&>(o);
+	t0 = now();
+	// the placed triangles in the description's layout (flattenScene): positions, normals, tangent + bitangent
+	const size_t nt = m.allTris.size();
+	std::vector<float> host(nt * 24);
+	float* pos = host.data(); float* nrm = pos + nt * 9; float* tb = nrm + nt * 9;
+	for (size_t i = 0; i < nt; ++i) {
+		const Triangle& t = m.allTris[i];
+		put3(&pos[i * 9], t.a); put3(&pos[i * 9 + 3], t.b); put3(&pos[i * 9 + 6], t.c);
+		put3(&nrm[i * 9], t.n_a); put3(&nrm[i * 9 + 3], t.n_b); put3(&nrm[i * 9 + 6], t.n_c);
+		put3(&tb[i * 6], t.tangent); put3(&tb[i * 6 + 3], t.bitangent);
+	}
+	const float lo[3] = { m.ac->rootBounds[0].x, m.ac->rootBounds[0].y, m.ac->rootBounds[0].z };
+	const float hi[3] = { m.ac->rootBounds[1].x, m.ac->rootBounds[1].y, m.ac->rootBounds[1].z };
+	hipCheck(hipSetDevice(device), "hipSetDevice");
+	float* dev = nullptr;
+	if (nt) {
+		hipCheck(hipMalloc((void**)&dev, host.size() * sizeof(float)), "hipMalloc");
+		const hipError_t e = hipMemcpy(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+		if (e != hipSuccess) { (void)hipFree(dev); hipCheck(e, "hipMemcpy"); }
+	}
+	lastMoveMs[1] = now() - t0;
+	t0 = now();
+	const int rc = rtx_scene_update_mesh(gpu_, (uint32_t)meshIndex, dev, nt ? dev + nt * 9 : nullptr, nt ? dev + nt * 18 : nullptr, lo, hi, options.acPenalty, nullptr);
+	lastMoveMs[3] = now() - t0;
+	if (dev) (void)hipFree(dev);
+	gpuCheck(rc, "rtx_scene_update_mesh");
+	m.treeOnDevice = true;
+	float ms[4];
+	if (rtx_scene_edit_times(gpu_, ms) == RTX_OK) { m.ac->buildMs = ms[0]; m.ac->builtOnDevice = true; }
+}
+
+void Scene::syncTrees()
+{
+	int32_t meshIndex = 0;
+	for (auto& op : objects) {
+		if (op->objectType != ObjectType::Mesh) continue;
+		auto& m = static_cast<Mesh&>(*op);
+		const int32_t mi = meshIndex++;
+		if (!m.treeOnDevice || !gpu_) continue;
+		uint32_t counts[2] = { 0, 0 };
+		gpuCheck(rtx_scene_mesh_read(gpu_, (uint32_t)mi, counts, nullptr, nullptr, nullptr, nullptr, nullptr), "rtx_scene_mesh_read");
+		const uint32_t nn = counts[0];
+		std::vector<float> bounds((size_t)nn * 6);
+		std::vector<int32_t> skip(nn), lb(nn), lc(nn);
+		m.ac->refs.resize(counts[1]);
+		gpuCheck(rtx_scene_mesh_read(gpu_, (uint32_t)mi, counts, bounds.data(), skip.data(), lb.data(), lc.data(), m.ac->refs.data()), "rtx_scene_mesh_read");
+		m.ac->nodes.resize(nn);
+		// (the depth of the deepest node, the root at depth 1, as the builders count it)
+		std::vector<int32_t> ends;
+		int maxDepth = 0;
+		for (uint32_t i = 0; i < nn; ++i) {
+			auto& nd = m.ac->nodes[i];
+			nd.bounds[0] = Vec3f(bounds[(size_t)i * 6], bounds[(size_t)i * 6 + 1], bounds[(size_t)i * 6 + 2]);
+			nd.bounds[1] = Vec3f(bounds[(size_t)i * 6 + 3], bounds[(size_t)i * 6 + 4], bounds[(size_t)i * 6 + 5]);
+			nd.skip = skip[i]; nd.leafBegin = lb[i]; nd.leafCount = lc[i];
+			while (!ends.empty() && ends.back() <= (int32_t)i) ends.pop_back();
+			ends.push_back(skip[i]);
+			maxDepth = std::max(maxDepth, (int)ends.size());
+		}
+		m.ac->maxDepth = maxDepth;
+		m.treeOnDevice = false;
+	}
 }
 
 // The frame lives in HBM across pass 1, the Sobel mask and the 4-ray pass (one allocation per Scene, re-used by every
