@@ -37,8 +37,30 @@ int rtx_cost_grid_read(rtx_scene* scene, uint32_t* out, size_t n, uint32_t* grid
  * once, by rtx_scene_create, and only when RTX_ALLOW_ENV_KNOBS=1 is set (the product ignores RTX_* variables otherwise); names here: strip_limit, ssaa_heavy_ticks, ssaa_spread_slots, split_percent,
  * ssaa_local_below, ssaa_sparse_below, frame_queue_cap, frame_rule_tiles, frame_rule_tiles_analytic, debug_items; and for rtx_trace_rays
  * trace_reorder (1 always group the rays by key first, 0 never, -1 by their number and the coherence of their order: the default) and trace_key_origin_first (1: the key's interleave
- * starts with the origin's bits, the default; 0: with the direction's).  No knob changes a pixel or a ray's result. */
+ * starts with the origin's bits, the default; 0: with the direction's).  prune_boxes (RTX_PRUNE_BOXES): the mesh kernels with the box test of
+ * the prune records -1 where some mesh has small enough triangles (the default), 0 never, 1 for every mesh with prune records; taken by the
+ * next launch.  No knob changes a pixel or a ray's result. */
 int rtx_set_knob(rtx_scene* scene, const char* name, double value);
+
+/* The compile-time variant the scene's next mesh launches take (pass 1, SSAA, the single-launch frame, rtx_trace_rays' hit and colour
+ * kernels): the fields the launches read, as bits.  The hit kernel has no PLAIN variant; analytic scenes (no mesh) launch kernels without the
+ * walk, and statistics the instrumented ones, whatever the other bits say. */
+#define RTX_VARIANT_BOXES    1u      /* the box test of the prune records */
+#define RTX_VARIANT_PLAIN    2u      /* every object Diffuse, no area light: no recursion, powf or area-light sums */
+#define RTX_VARIANT_ANALYTIC 4u      /* no triangle mesh */
+#define RTX_VARIANT_STATS    8u      /* statistics collected (rtx_counters_enable) */
+#define RTX_VARIANT_CULL     16u     /* back-face culling of the view */
+int rtx_kernel_variant(rtx_scene* scene, uint32_t* bits);
+
+/* What the last rtx_render_ssaa built (also the SSAA stage of a frame rendered in three launches); synchronises the device.
+ * info[16]: [0] tile-local layout (every tile's pixels padded to whole waves), [1] the flagged pixels the layout was decided from,
+ * [2] the "sparse" layout, [3] tiles of the list (T = ceil(width/8) * ceil(height/8) for a whole frame), [4] tiles per row
+ * (ceil(width/8)), [5] the heavy threshold the list was built with (ticks), [6] its slot budget of the 4-pixel and one-pixel waves,
+ * [7] RTX_SSAA_VERY, [8] RTX_SSAA_SPREAD_PX; of the last frame rendered in one launch: [9] [10] its two split limits (ticks, 0xffffffff:
+ * nothing split), [11] [12] the cost sum they were derived from (low, high word), [13] its waves.  scan (NULL: only info), n = 2 T + 1:
+ * the list's exclusive scan -- tile t owns the slots [scan[t], scan[t + 1]) when it was heavy, [scan[T + t], scan[T + t + 1]) otherwise,
+ * and its other range is empty.  Valid until the next rtx_render_ssaa of the scene: a frame in one launch builds no list and leaves it. */
+int rtx_ssaa_list_read(rtx_scene* scene, uint32_t* info, uint32_t* scan, size_t n);
 
 /* Launch counts and summed durations of kernel `which` (rtx_last_kernel_ms in rtx.h) since rtx_kernel_time_reset; synchronises on the recorded events. */
 int rtx_kernel_time_reset(rtx_scene* scene);

@@ -39,7 +39,7 @@ RTX_SYMBOLS = [
     "rtx_cast_rays", "rtx_trace_rays", "rtx_kernel_time_reset", "rtx_kernel_time_stats", "rtx_tile_cost_read", "rtx_set_row_ownership",
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
-    "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times",
+    "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
@@ -143,6 +143,8 @@ def load():
     rtx.rtx_scene_mesh_read.argtypes = [vp, C.c_uint32] + [vp] * 6
     rtx.rtx_scene_mesh_flat_read.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
     rtx.rtx_scene_edit_times.argtypes = [vp, vp]
+    rtx.rtx_kernel_variant.argtypes = [vp, C.POINTER(C.c_uint32)]
+    rtx.rtx_ssaa_list_read.argtypes = [vp, vp, vp, C.c_size_t]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -152,6 +154,10 @@ def exported_symbols():
     rtx, _ = load()
     missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
+
+
+# rtx_kernel_variant's bits (include/rtx_debug.h RTX_VARIANT_*)
+VARIANT_BITS = {"boxes": 1, "plain": 2, "analytic": 4, "stats": 8, "cull": 16}
 
 
 def _check(rc, what):
@@ -513,6 +519,29 @@ class Scene:
     def set_knob(self, name, value):
         """Experiment / test knob of this scene (include/rtx.h, rtx_set_knob); no knob changes a pixel."""
         _check(self.rtx.rtx_set_knob(self.gpu(), name.encode(), float(value)), "rtx_set_knob")
+
+    def kernel_variant(self):
+        """The compile-time variant the next mesh launches take (rtx_kernel_variant): dict of booleans boxes, plain, analytic, stats, cull."""
+        b = C.c_uint32(0)
+        _check(self.rtx.rtx_kernel_variant(self.gpu(), C.byref(b)), "rtx_kernel_variant")
+        return {k: bool(b.value & bit) for k, bit in VARIANT_BITS.items()}
+
+    def ssaa_list(self):
+        """What the last render_ssaa built, and the split limits of the last frame rendered in one launch (rtx_ssaa_list_read; synchronises
+        the device).  dict: local, sparse (layouts), flagged (the pixels the layout was decided from), tiles, tiles_x, heavy_ticks,
+        spread_slots, very, spread_px, split4, split16, cost_sum, frame_waves, and scan: the 2 tiles + 1 exclusive-scan offsets
+        (None before the first list)."""
+        g = self.gpu()
+        info = np.zeros(16, np.uint32)
+        _check(self.rtx.rtx_ssaa_list_read(g, _np_ptr(info), None, 0), "rtx_ssaa_list_read")
+        d = dict(local=bool(info[0]), flagged=int(info[1]), sparse=bool(info[2]), tiles=int(info[3]), tiles_x=int(info[4]),
+                 heavy_ticks=int(info[5]), spread_slots=int(info[6]), very=int(info[7]), spread_px=int(info[8]),
+                 split4=int(info[9]), split16=int(info[10]), cost_sum=int(info[11]) | int(info[12]) << 32, frame_waves=int(info[13]), scan=None)
+        if d["tiles"]:
+            scan = np.zeros(2 * d["tiles"] + 1, np.uint32)
+            _check(self.rtx.rtx_ssaa_list_read(g, _np_ptr(info), _np_ptr(scan), scan.size), "rtx_ssaa_list_read")
+            d["scan"] = scan
+        return d
 
     def cost_grid(self):
         """First-frame cost estimate of the current view: (refs, leaves) per cell of 2 x 2 tiles, arrays grid_h x grid_w."""

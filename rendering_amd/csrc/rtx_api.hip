@@ -240,6 +240,7 @@ struct rtx_scene {
 	int lastFrameMode = -1, frameModeForced = -1;
 	uint64_t viewSerial = 1, ssaaLayoutKey = 0;      // (the SSAA list layout is decided per view: ssaaStage)
 	uint32_t ssaaLayoutAge = 0;
+	uint32_t ssaaListTiles = 0, ssaaListHeavy = 0, ssaaListSpread = 0;      // the last rtx_render_ssaa's list: tiles, heavyTicks, spreadSlots (rtx_ssaa_list_read)
 	size_t lastFrameQueue = ~(size_t)0;      // the view of the last rtx_render_frame (index into tileQueues)
 	std::vector<TileQueues> tileQueues;   // a few entries: a frame may be rendered in several row ranges
 	uint64_t tileUse = 0;
@@ -279,6 +280,18 @@ void readKnobs(Knobs& k)
 	k.frameQueueCap = (uint32_t)num("RTX_FRAME_QUEUE_CAP", 0);
 	k.debugItems = getenv("RTX_DEBUG_ITEMS") != nullptr;
 	if (const char* e = getenv("RTX_DBG_TILE")) { unsigned tx = 0, ty = 0; if (sscanf(e, "%u,%u", &tx, &ty) == 2) k.dbgTile = ((ty << 16) | tx) + 1; }
+}
+
+// The kernel variant with the box test of the prune records (rtx_scene_create's rule over the current records; again after an
+// edit, rtx_edit.hip, and after the knob prune_boxes).
+void chooseBoxPrune(rtx_scene* s)
+{
+	s->boxPrune = false;
+	for (const Object& d : s->objectRecs) {
+		if (d.type != RTX_OBJ_MESH) continue;
+		if (d.pruneBoxes && s->knobs.pruneBoxes != 0) s->boxPrune = true;
+		if (s->knobs.pruneBoxes > 0 && d.prune) s->boxPrune = true;
+	}
 }
 
 int setView(rtx_scene* s, const rtx_view* v)
@@ -1668,7 +1681,42 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 	else if (n == "debug_items") k.debugItems = value != 0;
 	else if (n == "trace_reorder") k.traceReorder = value < 0 ? -1 : (value != 0 ? 1 : 0);
 	else if (n == "trace_key_origin_first") k.traceOriginFirst = value != 0 ? 1 : 0;
+	else if (n == "prune_boxes") {
+		// (taken by the next launch; launches already queued keep the variant they were launched with)
+		k.pruneBoxes = value < 0 ? -1 : (value != 0 ? 1 : 0);
+		chooseBoxPrune(s);
+		s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;      // (the hit kernel's occupancy is the variant's)
+	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
+	return RTX_OK;
+}
+
+int rtx_kernel_variant(rtx_scene* s, uint32_t* bits)
+{
+	if (!s || !bits) return fail(RTX_ERR_ARG, "scene/bits is NULL");
+	// the fields RTX_LAUNCH_MESH_KERNEL, rayHitKernel and rayColourKernel read at launch
+	*bits = (s->boxPrune ? RTX_VARIANT_BOXES : 0u) | (s->plain ? RTX_VARIANT_PLAIN : 0u) | (s->analytic ? RTX_VARIANT_ANALYTIC : 0u) |
+	        (s->stats ? RTX_VARIANT_STATS : 0u) | ((s->params.view.flags & RTX_FLAG_BACKFACE_CULL) ? RTX_VARIANT_CULL : 0u);
+	return RTX_OK;
+}
+
+int rtx_ssaa_list_read(rtx_scene* s, uint32_t* info, uint32_t* scan, size_t n)
+{
+	if (!s || !info) return fail(RTX_ERR_ARG, "scene/info is NULL");
+	HIPCHK(hipSetDevice(s->device));
+	HIPCHK(hipDeviceSynchronize());
+	memset(info, 0, 16 * sizeof(uint32_t));
+	uint32_t w[20] = { 0 };
+	if (s->work) HIPCHK(hipMemcpy(w, s->work, sizeof(w), hipMemcpyDeviceToHost));
+	info[0] = w[8]; info[1] = w[9]; info[2] = w[11];      // mode[0] local, mode[1] flagged pixels, mode[3] sparse
+	info[3] = s->ssaaListTiles; info[4] = s->params.tilesXFull; info[5] = s->ssaaListHeavy; info[6] = s->ssaaListSpread;
+	info[7] = RTX_SSAA_VERY; info[8] = RTX_SSAA_SPREAD_PX;
+	info[9] = w[18]; info[10] = w[19]; info[11] = w[16]; info[12] = w[17];      // split limits; the cost sum they were derived from
+	info[13] = (uint32_t)s->blocksFrame * 4u;
+	if (!scan) return RTX_OK;
+	if (!s->ssaaListTiles || !s->items) return fail(RTX_ERR_ARG, "no SSAA list has been built");
+	if (n != 2 * (size_t)s->ssaaListTiles + 1) return fail(RTX_ERR_ARG, "n must be 2 tiles + 1 of the last list");
+	HIPCHK(hipMemcpy(scan, s->items, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
 
@@ -1756,6 +1804,10 @@ int rtx_sobel(rtx_scene* s, const float* fb_dev, uint32_t rowBegin, uint32_t row
 	return RTX_OK;
 }
 
+// The SSAA launch of frame k may overlap pass 1 of frame k + 1 on another stream (bench.py --pipelined): pass 1 then rewrites
+// tileCost while the list is built from it.  Each tile's cost is read once, by rtxSsaaCountKernel; the scatter takes the tile's
+// half and layout from the scan, so the list stays consistent and the frame the serial one (tests/test_gpu_overlap.py).  The
+// second area of `frames`, the SSAA queue head (work[1]) and the list (items, ssaaPixels) are this stage's own.
 int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, void* stream)
 {
 	RoctxRange range("MSAA (rtx_render_ssaa)");
@@ -1808,8 +1860,9 @@ int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, ui
 	if (s->knobs.sparseBelow >= 0) sparseBelow = (uint32_t)std::min<long long>(s->knobs.sparseBelow, 0xffffffffll);
 	hipLaunchKernelGGL(rtxSsaaCountKernel, dim3((scanN + 255) / 256), dim3(256), 0, st, p, s->items, mode, heavyTicks, decideNow ? 1u : 2u, localBelow, spreadSlots, sparseBelow);
 	if ((rc = scanExclusive(s->items, scanN, s->items + scanN, st, launches))) return rc;
-	hipLaunchKernelGGL(rtxSsaaScatterKernel, dim3((p.nTiles + 255) / 256), dim3(256), 0, st, p, s->items, mode, s->ssaaPixels, heavyTicks);
+	hipLaunchKernelGGL(rtxSsaaScatterKernel, dim3((p.nTiles + 255) / 256), dim3(256), 0, st, p, s->items, mode, s->ssaaPixels);
 	HIPCHK(hipGetLastError());
+	s->ssaaListTiles = p.nTiles; s->ssaaListHeavy = heavyTicks; s->ssaaListSpread = spreadSlots;
 	if (s->stats) hipLaunchKernelGGL(rtxSsaaKernel<true>, dim3(s->blocksSsaa), dim3(256), 0, st, p);
 	else if (s->analytic) hipLaunchKernelGGL((rtxSsaaKernel<false, false>), dim3(s->blocksSsaa), dim3(256), 0, st, p);
 	else RTX_LAUNCH_MESH_KERNEL(rtxSsaaKernel, false RTX_COMMA true RTX_COMMA, s->blocksSsaa, st, p);

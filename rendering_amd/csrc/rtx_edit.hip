@@ -27,17 +27,6 @@ int editBegin(rtx_scene* s, void* stream)
 	return RTX_OK;
 }
 
-// The kernel variant with the box test of the prune records (rtx_scene_create's rule over the current records).
-void chooseBoxPrune(rtx_scene* s)
-{
-	s->boxPrune = false;
-	for (const Object& d : s->objectRecs) {
-		if (d.type != RTX_OBJ_MESH) continue;
-		if (d.pruneBoxes && s->knobs.pruneBoxes != 0) s->boxPrune = true;
-		if (s->knobs.pruneBoxes > 0 && d.prune) s->boxPrune = true;
-	}
-}
-
 // The spheres' and planes' share of the derived state (rtx_scene_create's loops over the descriptions): the spheres' entry of the
 // cost estimate, the planes the estimate casts shadows on, and the longest plane normal a shadow ray's origin is offset along.
 int refreshAnalytic(rtx_scene* s)

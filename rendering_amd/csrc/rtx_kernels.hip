@@ -2292,7 +2292,9 @@ __global__ void __launch_bounds__(256) rtxTileOrderKernel(uint32_t* __restrict__
 
 // SSAA work list, step 1: one thread per 8x8 tile counts the tile's flagged pixels (of the rows this launch re-renders)
 // into the heavy or the normal half of `scan` (heavy = pass 1 spent more than `heavyTicks` on the tile).  After an
-// exclusive scan over the 2 nTiles + 1 entries, step 2 writes the pixels to their slots.
+// exclusive scan over the 2 nTiles + 1 entries, step 2 writes the pixels to their slots.  The tile's cost is read ONCE,
+// here: pass 1 of the next frame may be rewriting tileCost on another stream meanwhile (frames of a sequence overlapped,
+// rtx_render_ssaa), so step 2 takes the tile's half and layout from the scan, never from tileCost again.
 __device__ __forceinline__ uint64_t ssaaFlagged(const Params& P, uint32_t tx, uint32_t ty)
 {
 	const uint32_t W = P.view.width, H = P.view.height;
@@ -2327,12 +2329,12 @@ __global__ void __launch_bounds__(256) rtxSsaaCountKernel(const Params P, uint32
 	if (t >= P.nTiles) { if (t == 2 * P.nTiles) { scan[t] = 0; if (decide == 1) { mode[0] = local; mode[3] = sparse; } } return; }
 	const uint32_t ty = t / P.tilesXFull, tx = t - ty * P.tilesXFull;
 	uint32_t nf = (uint32_t)__popcll(ssaaFlagged(P, tx, ty));
+	const uint32_t cost = P.tileCost[t];
 	// local mode: a wave holds 16 pixels of one tile -- or only 4 of a tile that was VERY slow in pass 1 (a silhouette),
 	// because the launch lasts as long as its slowest wave.  The 4-pixel layout needs up to 4x the slots; the list holds
 	// spreadSlots extra ones (mode[2] = handed out so far), a tile that does not get its share is packed normally.  The
 	// scatter kernel recognises the layout from the tile's slot count.
 	if (local) {
-		const uint32_t cost = P.tileCost[t];
 		uint32_t per = 16u;
 		if (cost > RTX_SSAA_VERY * heavyTicks) per = sparse ? 1u : RTX_SSAA_SPREAD_PX;
 		else if (sparse && cost > heavyTicks) per = RTX_SSAA_SPREAD_PX;
@@ -2340,13 +2342,13 @@ __global__ void __launch_bounds__(256) rtxSsaaCountKernel(const Params P, uint32
 		nf = packed;
 		if (per < 16u && spread > packed && atomicAdd(mode + 2, spread - packed) + (spread - packed) <= spreadSlots) nf = spread;
 	}
-	const bool heavy = P.tileCost[t] > heavyTicks;
+	const bool heavy = cost > heavyTicks;
 	scan[t] = heavy ? nf : 0u;
 	scan[P.nTiles + t] = heavy ? 0u : nf;
 }
 
 __global__ void __launch_bounds__(256) rtxSsaaScatterKernel(const Params P, const uint32_t* __restrict__ scan, uint32_t* __restrict__ mode,
-                                                            uint32_t* __restrict__ pixels, uint32_t heavyTicks)
+                                                            uint32_t* __restrict__ pixels)
 {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	// (instead of two memsets per frame: the queue head of the SSAA launch that follows, and the slot budget the NEXT count
@@ -2355,10 +2357,11 @@ __global__ void __launch_bounds__(256) rtxSsaaScatterKernel(const Params P, cons
 	if (t >= P.nTiles) return;
 	const uint32_t ty = t / P.tilesXFull, tx = t - ty * P.tilesXFull;
 	uint64_t m = ssaaFlagged(P, tx, ty);
-	const uint32_t idx = P.tileCost[t] > heavyTicks ? t : P.nTiles + t;
+	// the tile's half as the count kernel chose it: the other half's entry is 0 slots wide (a tile without slots writes nothing)
+	const uint32_t idx = scan[t + 1] != scan[t] ? t : P.nTiles + t;
 	P.tileCost[P.nTiles + t] = 0;      // (the SSAA item costs of this frame are collected from here on: rtxSsaaKernel)
 	uint32_t slot = scan[idx];
-	const uint32_t slots = scan[idx + 1] - slot, nf = (uint32_t)__popcll(m);      // (the other half's entry of a tile is 0 slots wide)
+	const uint32_t slots = scan[idx + 1] - slot, nf = (uint32_t)__popcll(m);
 	const bool spread = mode[0] && slots > ((nf + 15u) & ~15u);      // 4 pixels (or one: the count kernel's "sparse" layout) per group of 16 slots
 	const uint32_t per = !spread ? 16u : (slots == ((nf + RTX_SSAA_SPREAD_PX - 1u) / RTX_SSAA_SPREAD_PX) * 16u ? RTX_SSAA_SPREAD_PX : 1u);
 	uint32_t n = 0, px = 0;

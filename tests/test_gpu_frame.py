@@ -64,18 +64,29 @@ def test_frame_equals_three_stages(ra, torch_cuda, path, W, H):
     g.set_frame_mode(AUTO)
 
 
-def test_frame_everything_split(ra, torch_cuda, monkeypatch):
-    """Every tile rendered as sixteen 2x2 parts and every flagged pixel as its own SSAA item (limits forced to the floor)."""
+def test_frame_everything_split(ra, torch_cuda):
+    """Every tile rendered as sixteen 2x2 parts and every flagged pixel as its own SSAA item (limits forced to the floor): the limits read
+    back follow rtxTileOrderKernel's rule from the previous frame's tile costs, and some tile really is over them."""
     torch = torch_cuda
-    monkeypatch.setenv("RTX_SPLIT_PERCENT", "1")
     g = ra.Scene("scenes/cfg2_smooth_4k.scene", 136, 104)
+    g.set_knob("split_percent", 1)
     ref_fb, ref_mask = stages(torch, g)
+    over = 0
     for it in range(3):
+        prev = g.tile_cost().astype(np.int64)      # (what the frame's limits are derived from: the costs of the frame before)
         fb, mask = frame(torch, g, FUSED)
         assert same(torch, ref_fb, fb) and torch.equal(ref_mask, mask)
+        lst = g.ssaa_list()
+        assert lst["cost_sum"] == int(prev.sum()) > 0 and lst["frame_waves"] > 0
+        split4 = max(2000, min(0x0fffffff, lst["cost_sum"] // lst["frame_waves"] * 1 // 100))
+        assert (lst["split4"], lst["split16"]) == (split4, 4 * split4), "frame %d: limits %s" % (it, (lst["split4"], lst["split16"]))
+        over += int((prev > split4).sum())
+    assert over > 0, "no tile was over the split limit: the split path never ran"
     g.set_knob("split_percent", 0)      # and never
     fb, mask = frame(torch, g, FUSED)
     assert same(torch, ref_fb, fb) and torch.equal(ref_mask, mask)
+    lst = g.ssaa_list()
+    assert (lst["split4"], lst["split16"]) == (0xffffffff, 0xffffffff)
 
 
 def test_frame_row_ranges_and_bands(ra, torch_cuda):

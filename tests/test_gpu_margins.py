@@ -109,9 +109,12 @@ def ray_families(tris, rng, n_tri=48):
     return waves(o, d, rng)
 
 
-def check(ra, oracle, path, w, h, obj_idx, seed, frames=True, n_tri=48):
+def check(ra, oracle, path, w, h, obj_idx, seed, frames=True, n_tri=48, boxes=None):
     o = oracle.OracleScene(path, w, h)
     g = ra.Scene(path, w, h)
+    if boxes is not None:
+        g.set_knob("prune_boxes", boxes)
+        assert g.kernel_variant()["boxes"] == bool(boxes), "prune_boxes = %d did not take" % boxes
     tris = g.bvh(obj_idx)["tris"][:, 0:9]
     rays = ray_families(tris, np.random.default_rng(seed), n_tri)
     rh, rc = o.probe(rays)
@@ -170,15 +173,123 @@ def test_fine_meshes_where_the_box_records_prune(ra, oracle, tmp_path, name, n_t
         assert hits > n // 50
 
 
-@pytest.mark.parametrize("name,boxes", [("bumpy_4k.obj", "1"), ("bumpy_25k.obj", "0")])
-def test_either_kernel_variant_on_either_kind_of_mesh(ra, oracle, tmp_path, monkeypatch, name, boxes):
-    """The launch picks the kernels with the box test of the prune records (BOXES) only for scenes with small triangles; the knob
-    forces the other variant: the box test on a mesh of large triangles (its margin is then larger than the mesh: it must
-    simply never prune), and a fine mesh through the kernels without it."""
+@pytest.mark.parametrize("name,size,boxes", [("bumpy_4k.obj", 2, 1), ("bumpy_25k.obj", 1, 0)], ids=["bumpy_4k.obj-1", "bumpy_25k.obj-0"])
+def test_either_kernel_variant_on_either_kind_of_mesh(ra, oracle, tmp_path, name, size, boxes):
+    """The launch picks the kernels with the box test of the prune records (BOXES) only for scenes with small triangles (the whole
+    mesh's P < 1/216: the 25k mesh at size 1, not at size 2); the knob forces the other variant: the box test on a mesh of large
+    triangles (its margin is then larger than the mesh: it must simply never prune), and a fine mesh through the kernels without it."""
     from rendering_amd import assets
     mesh = assets.ensure([name])[name]
-    monkeypatch.setenv("RTX_PRUNE_BOXES", boxes)
     path = tmp_path / "variant.scene"
-    path.write_text(scene_text(mesh, pos=(0, 0, -3), size=(2, 2, 2), rot=(15, 40, 0), cull=1, w=128, h=96))
-    n, hits = check(ra, oracle, str(path), 128, 96, 1, 47, n_tri=24)
+    path.write_text(scene_text(mesh, pos=(0, 0, -3), size=(size,) * 3, rot=(15, 40, 0), cull=1, w=128, h=96))
+    g = ra.Scene(str(path), 128, 96)
+    assert g.kernel_variant()["boxes"] == (not boxes), "%s: the meshes no longer choose the other variant by themselves" % name
+    g.close()
+    n, hits = check(ra, oracle, str(path), 128, 96, 1, 47, n_tri=24, boxes=boxes)
     assert hits > n // 50
+
+
+def test_environment_knobs_need_the_gate(ra, tmp_path, monkeypatch):
+    """The product ignores RTX_* variables unless RTX_ALLOW_ENV_KNOBS=1: a scene created under RTX_PRUNE_BOXES=1 keeps the variant its
+    meshes choose, and takes the forced one only through the gate.  (Tests force knobs with set_knob: an environment knob without the gate
+    forces nothing.)"""
+    from rendering_amd import assets
+    mesh = assets.ensure(["bumpy_4k.obj"])["bumpy_4k.obj"]
+    path = tmp_path / "gate.scene"
+    path.write_text(scene_text(mesh, pos=(0, 0, -3), size=(2, 2, 2), rot=(15, 40, 0), cull=1, w=64, h=48))
+    monkeypatch.delenv("RTX_ALLOW_ENV_KNOBS", raising=False)
+    monkeypatch.setenv("RTX_PRUNE_BOXES", "1")
+    g = ra.Scene(str(path), 64, 48)
+    assert not g.kernel_variant()["boxes"], "RTX_PRUNE_BOXES took effect without RTX_ALLOW_ENV_KNOBS"
+    g.close()
+    monkeypatch.setenv("RTX_ALLOW_ENV_KNOBS", "1")
+    g = ra.Scene(str(path), 64, 48)
+    assert g.kernel_variant()["boxes"], "RTX_PRUNE_BOXES=1 did not take with RTX_ALLOW_ENV_KNOBS=1"
+    g.close()
+
+
+# The variant matrix: the ray families of the margins through the kernels the product launches for frames and rtx_trace_rays -- compile-time
+# variants per (PLAIN, BOXES, CULL) for pass 1, SSAA, the single-launch frame and the colour kernel, per (BOXES, CULL) for the hit kernel
+# (rtx_api.hip RTX_LAUNCH_MESH_KERNEL, rayHitKernel, rayColourKernel).  PLAIN follows from the material (Diffuse everywhere, or a Phong mesh),
+# BOXES is forced with the knob, CULL is the scene's.  Every case asserts the bits it expects, and the list below names every combination
+# on every scene, so no selection of tests can shrink the matrix unnoticed.
+PHONG = "material=phong,0.4,0.1,0.7,10.0\n"
+MATRIX_SCENES = ["lattice_flat", "lattice_bumped", "mesh_1e-4", "mesh_at_1e5"]
+MATRIX = [(scene, plain, boxes, cull) for scene in MATRIX_SCENES for plain in (1, 0) for boxes in (0, 1) for cull in (1, 0)]
+_matrix_oracle = {}
+
+
+def matrix_scene(tmp_path, scene, plain, cull):
+    material = "" if plain else PHONG
+    if scene.startswith("lattice"):
+        bump = 0.0625 if scene == "lattice_bumped" else 0.0
+        obj = tmp_path / "lattice.obj"
+        obj.write_text(lattice_obj(16, bump))
+        text = scene_text(str(obj), pos=(0, 0, -3), size=(2, 2, 2) if bump else (2, 2, 0), rot=(20, 30, 0) if bump else (0, 0, 0), cull=cull,
+                          w=128, h=96, material=material)
+    else:
+        from rendering_amd import assets
+        mesh = assets.ensure(["bumpy_4k.obj"])["bumpy_4k.obj"]
+        scale, shift = {"mesh_1e-4": (1e-4, 0.0), "mesh_at_1e5": (1.0, 1e5)}[scene]
+        cam = (shift, -shift * 0.5, shift * 0.25)
+        text = scene_text(mesh, pos=(cam[0], cam[1], cam[2] - 3 * scale), size=(2 * scale,) * 3, rot=(10, 25, 5), cull=cull, cam=cam,
+                          w=128, h=96, material=material)
+    path = tmp_path / "matrix.scene"
+    path.write_text(text)
+    return str(path)
+
+
+def matrix_reference(oracle, ra, path, key):
+    """The oracle's rays, probe records, frame and mask of a matrix scene (the same for either BOXES: computed once)."""
+    if key not in _matrix_oracle:
+        o = oracle.OracleScene(path, 128, 96)
+        g = ra.Scene(path, 128, 96)
+        tris = g.bvh(1)["tris"][:, 0:9]
+        g.close()
+        rays = ray_families(tris, np.random.default_rng(61), 16)
+        rh, rc = o.probe(rays)
+        p1 = o.pass1()
+        mask = o.sobel(p1)
+        mask[0, :] = 0; mask[-1, :] = 0; mask[:, 0] = 0; mask[:, -1] = 0       # (border = 0 by definition)
+        _matrix_oracle[key] = (rays, rh, rc, o.ssaa(p1), mask)
+        o.close()
+    return _matrix_oracle[key]
+
+
+@pytest.mark.parametrize("scene,plain,boxes,cull", MATRIX)
+def test_variant_matrix_rays_and_frames(ra, oracle, tmp_path, scene, plain, boxes, cull):
+    """The margin rays through rtx_trace_rays (trace_reorder 0: a wave of 64 stays the bundle it was built as) and frames in one and in
+    three launches, on the variant (PLAIN, BOXES, CULL) the case names, against the oracle bit for bit."""
+    import torch
+    path = matrix_scene(tmp_path, scene, plain, cull)
+    rays, rh, rc, ref, ref_mask = matrix_reference(oracle, ra, path, (scene, plain, cull))
+    g = ra.Scene(path, 128, 96)
+    g.set_knob("prune_boxes", boxes)
+    g.set_knob("trace_reorder", 0)
+    v = g.kernel_variant()
+    assert (v["plain"], v["boxes"], v["cull"], v["analytic"], v["stats"]) == (bool(plain), bool(boxes), bool(cull), False, False), v
+    gh, gc = g.trace_rays(torch.from_numpy(rays).cuda())
+    torch.cuda.synchronize()
+    gh, gc = gh.cpu().numpy(), gc.cpu().numpy()
+    bad = (bits(rh) != bits(gh)).any(1) | (bits(rc) != bits(gc)).any(1)
+    assert not bad.any(), "%d of %d rays differ, first %d: ray %s oracle %s %s gpu %s %s" % (
+        int(bad.sum()), len(rays), int(np.argmax(bad)), rays[np.argmax(bad)], rh[np.argmax(bad)], rc[np.argmax(bad)], gh[np.argmax(bad)], gc[np.argmax(bad)])
+    assert (rh[:, 0] >= 0).sum() > len(rays) // 50
+    for mode in (1, 0, 1):          # one launch (cold, then warm: slow tiles split), three launches
+        fb = torch.zeros((96, 128, 3), dtype=torch.float32, device="cuda")
+        mask = torch.zeros((96, 128), dtype=torch.uint8, device="cuda")
+        g.set_frame_mode(mode)
+        g.render_frame(fb, mask)
+        assert g.frame_status() == 0 and g.frame_mode()[0] == mode
+        got = fb.cpu().numpy()
+        nd = int((bits(ref) != bits(got)).any(-1).sum())
+        assert nd == 0, "%s in %s: %d pixels differ" % (scene, "one launch" if mode else "three launches", nd)
+        assert np.array_equal(mask.cpu().numpy() != 0, ref_mask != 0), "%s in %s: mask differs" % (scene, "one launch" if mode else "three launches")
+    assert g.kernel_variant() == v
+    g.close()
+
+
+def test_variant_matrix_is_complete():
+    """Every (PLAIN, BOXES, CULL) on every matrix scene -- so every (BOXES, CULL) of the hit kernel too."""
+    for scene in MATRIX_SCENES:
+        assert {(p, b, c) for s, p, b, c in MATRIX if s == scene} == {(p, b, c) for p in (0, 1) for b in (0, 1) for c in (0, 1)}

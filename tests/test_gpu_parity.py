@@ -126,54 +126,98 @@ def test_counters_match_reference_semantics(ra, oracle):
     assert np.array_equal(ref, got), (ref, got)
 
 
-@pytest.mark.parametrize("local_below", ["0", "4000000000"])
-def test_ssaa_list_modes_bit_exact(ra, oracle, monkeypatch, local_below):
+def stages(g, knobs=()):
+    """The frame through the three device entry points (the mask stays available), after setting `knobs` on the scene; returns
+    (framebuffer, mask, pass-1 tile costs the SSAA list was built from, the list)."""
+    import torch
+    for k, v in knobs:
+        g.set_knob(k, v)
+    fb = torch.zeros((g.height, g.width, 3), dtype=torch.float32, device="cuda")
+    mask = torch.zeros((g.height, g.width), dtype=torch.uint8, device="cuda")
+    g.render_pass1(fb)
+    g.sobel(fb, mask)
+    g.render_ssaa(mask, fb)
+    torch.cuda.synchronize()
+    return fb.cpu().numpy(), mask.cpu().numpy(), g.tile_cost(), g.ssaa_list()
+
+
+@pytest.mark.parametrize("local_below", [0, 4000000000])
+def test_ssaa_list_modes_bit_exact(ra, oracle, local_below):
     """Both layouts of the SSAA flagged-pixel list (dense = full waves, tile-local = padded) give the reference's
-    frame; the knob forces the mode the device would otherwise pick from the number of flagged pixels."""
-    monkeypatch.setenv("RTX_SSAA_LOCAL_BELOW", local_below)
+    frame; the knob forces the mode the device would otherwise pick from the number of flagged pixels, and the list read back
+    is in that mode: packed, every tile exactly its flagged pixels wide; tile-local, every tile whole waves wide."""
+    from tests.util_ssaa import check_list
     for name, w, h in (("cfg2_smooth_4k", 320, 240), ("cfg1_simple_shapes", 256, 256)):
         path = "scenes/%s.scene" % name
         o = oracle.OracleScene(path, w, h)
         g = ra.Scene(path, w, h)
         ref = o.ssaa(o.pass1())
-        got = g.render_host(ssaa=True)
+        got, mask, cost, lst = stages(g, [("ssaa_local_below", local_below)])
         assert ndiff(ref, got) == 0
+        assert lst["local"] == (local_below != 0), "%s: the list is %s" % (name, "tile-local" if lst["local"] else "packed")
+        assert lst["flagged"] == int((mask[:-1, :-1] != 0).sum()) > 0      # (what the layout was decided from)
+        wd, nf, _, _, _ = check_list(lst, cost, mask)
+        if local_below:
+            assert (wd % 16 == 0).all() and (wd > 0).sum() == (nf > 0).sum()
 
 
-@pytest.mark.parametrize("spread_slots", ["1048576", "4096", "0"])
-def test_ssaa_four_pixel_waves_and_slot_budget(ra, oracle, monkeypatch, spread_slots):
+@pytest.mark.parametrize("spread_slots", [1048576, 4096, 0])
+def test_ssaa_four_pixel_waves_and_slot_budget(ra, oracle, spread_slots):
     """Tile-local SSAA list with EVERY tile classified as very slow (knob: threshold of 1 tick), so that every tile asks
     for the 4-pixels-per-wave layout (4x the slots): with a full, a partly and a fully exhausted slot budget the list
-    never overruns (tiles over the budget are packed normally) and the frame is the reference's."""
-    monkeypatch.setenv("RTX_SSAA_LOCAL_BELOW", "4000000000")
-    monkeypatch.setenv("RTX_SSAA_HEAVY_TICKS", "1")
-    monkeypatch.setenv("RTX_SSAA_SPREAD_SLOTS", spread_slots)
+    never overruns (tiles over the budget are packed normally) and the frame is the reference's.  The "sparse" layout
+    (one pixel per wave) is forced off: these are the 4-pixel waves."""
+    from tests.util_ssaa import check_list, pad16
     for name, w, h in (("cfg2_smooth_4k", 320, 240), ("cfg3_reflective_refractive", 240, 136)):
         path = "scenes/%s.scene" % name
         o = oracle.OracleScene(path, w, h)
         g = ra.Scene(path, w, h)
         ref = o.ssaa(o.pass1())
-        got = g.render_host(ssaa=True)
+        got, mask, cost, lst = stages(g, [("ssaa_local_below", 4000000000), ("ssaa_sparse_below", 0), ("ssaa_heavy_ticks", 1),
+                                          ("ssaa_spread_slots", spread_slots)])
         assert ndiff(ref, got) == 0
+        assert lst["local"] and not lst["sparse"] and lst["heavy_ticks"] == 1 and lst["spread_slots"] == spread_slots
+        wd, nf, want, spread, _ = check_list(lst, cost, mask)
+        assert (cost.ravel()[nf > 0] > lst["very"]).all() and want.any()      # (every tile with flagged pixels is very slow)
+        wanted = int((((nf + 3) // 4) * 16 - pad16(nf))[want].sum())
+        extra = int((wd - pad16(nf)).sum())
+        if spread_slots == 1048576:
+            # every tile with flagged pixels that is very slow gets ceil(nf / 4) waves
+            assert wanted <= spread_slots and spread.sum() == want.sum()
+            assert np.array_equal(wd[nf > 0], ((nf + 3) // 4 * 16)[nf > 0])
+        elif spread_slots == 4096:
+            assert wanted > 4096, "%s: the tiles ask for %d extra slots: the budget is never reached" % (name, wanted)
+            assert 0 < extra <= 4096 and 0 < spread.sum() < want.sum()
+        else:
+            assert extra == 0 and not spread.any() and np.array_equal(wd, pad16(nf))
 
 
-@pytest.mark.parametrize("sparse_below", ["0", "4000000000"])
-@pytest.mark.parametrize("heavy_ticks", ["1", "25000"])
-def test_ssaa_sparse_layout_bit_exact(ra, oracle, monkeypatch, sparse_below, heavy_ticks):
+@pytest.mark.parametrize("sparse_below", [0, 4000000000])
+@pytest.mark.parametrize("heavy_ticks", [1, 25000])
+def test_ssaa_sparse_layout_bit_exact(ra, oracle, sparse_below, heavy_ticks):
     """The "sparse" layout of the tile-local SSAA list (rtxSsaaCountKernel: 4 pixels per wave for the tiles that were slow in pass 1, ONE
     for the very slow ones, chosen when a launch has fewer 16-pixel items than half its waves) forced on and off, with every tile classified
-    as very slow (threshold of 1 tick: one-pixel waves everywhere) and with the product's threshold: the frame is the reference's."""
-    monkeypatch.setenv("RTX_SSAA_LOCAL_BELOW", "4000000000")
-    monkeypatch.setenv("RTX_SSAA_SPARSE_BELOW", sparse_below)
-    monkeypatch.setenv("RTX_SSAA_HEAVY_TICKS", heavy_ticks)
+    as very slow (threshold of 1 tick: one-pixel waves everywhere) and with the product's threshold: the frame is the reference's, and the
+    list is in the layout forced."""
+    from tests.util_ssaa import check_list
     for name, w, h in (("cfg2_smooth_4k", 320, 240), ("cfg3_reflective_refractive", 240, 136)):
         path = "scenes/%s.scene" % name
         o = oracle.OracleScene(path, w, h)
         g = ra.Scene(path, w, h)
         ref = o.ssaa(o.pass1())
+        knobs = [("ssaa_local_below", 4000000000), ("ssaa_sparse_below", sparse_below), ("ssaa_heavy_ticks", heavy_ticks)]
         for _ in range(2):          # (the second frame knows the tile costs of the first)
-            got = g.render_host(ssaa=True)
+            got, mask, cost, lst = stages(g, knobs)
             assert ndiff(ref, got) == 0
+            assert lst["local"] and lst["sparse"] == (sparse_below != 0) and lst["heavy_ticks"] == heavy_ticks
+            wd, nf, want, spread, per = check_list(lst, cost, mask)
+            if heavy_ticks == 1:
+                # every tile is very slow: one pixel per wave when sparse, four otherwise -- and the budget covers them all
+                ask = nf > 1 if sparse_below else nf > 4
+                assert (per[nf > 0] == (1 if sparse_below else lst["spread_px"])).all()
+                assert ask.any() and np.array_equal(want, ask) and np.array_equal(spread, want)
+                if sparse_below:
+                    assert np.array_equal(wd[want], 16 * nf[want])
 
 
 def test_event_pool_does_not_grow(ra):
