@@ -37,7 +37,8 @@ int rtx_cost_grid_read(rtx_scene* scene, uint32_t* out, size_t n, uint32_t* grid
  * once, by rtx_scene_create, and only when RTX_ALLOW_ENV_KNOBS=1 is set (the product ignores RTX_* variables otherwise); names here: strip_limit, ssaa_heavy_ticks, ssaa_spread_slots, split_percent,
  * ssaa_local_below, ssaa_sparse_below, frame_queue_cap, frame_rule_tiles, frame_rule_tiles_analytic, debug_items; and for rtx_trace_rays
  * trace_reorder (1 always group the rays by key first, 0 never, -1 by their number and the coherence of their order: the default) and trace_key_origin_first (1: the key's interleave
- * starts with the origin's bits, the default; 0: with the direction's).  prune_boxes (RTX_PRUNE_BOXES): the mesh kernels with the box test of
+ * starts with the origin's bits, the default; 0: with the direction's), both of which act on the occlusion query of include/rtx_query.h too, whose own knob is
+ * occluded_scene_order (1: the objects in scene order; 0: spheres and planes before the meshes, the default).  prune_boxes (RTX_PRUNE_BOXES): the mesh kernels with the box test of
  * the prune records -1 where some mesh has small enough triangles (the default), 0 never, 1 for every mesh with prune records; taken by the
  * next launch.  No knob changes a pixel or a ray's result. */
 int rtx_set_knob(rtx_scene* scene, const char* name, double value);

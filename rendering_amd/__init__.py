@@ -45,6 +45,9 @@ RTX_SYMBOLS = [
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
 RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh"]
 
+# the extension of include/rtx_query.h: queries on a loaded scene that render nothing (not part of the drop-in boundary)
+RTX_QUERY_SYMBOLS = ["rtx_occluded_rays"]
+
 
 def load():
     """Loads the native libraries (raises RtxError when they have not been built: run ./build.sh)."""
@@ -86,6 +89,7 @@ def load():
     rtx.rtx_math_probe.argtypes = [i32, i32, u32, vp, vp, vp]
     rtx.rtx_cast_rays.argtypes = [vp, u32, vp, vp, vp]
     rtx.rtx_trace_rays.argtypes = [vp, u32, vp, vp, vp, vp]
+    rtx.rtx_occluded_rays.argtypes = [vp, u32, vp, vp, vp, vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -152,7 +156,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -624,6 +628,56 @@ class Scene:
                                        C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
                "rtx_trace_rays")
         return h, c
+
+    def occluded(self, rays, tmax=None, stream=None):
+        """rtx_occluded_rays: is anything between a ray's origin and its range?  Render::trace of a shadow ray whose info.tNear starts at
+        tmax -- 1 iff some object that is not Transparent is hit at tNear < tmax (strict, float32; a NaN range occludes nothing).
+        rays: contiguous float32 torch tensor (n, 6) = {orig xyz, dir xyz} on this scene's device.  tmax: a float32 tensor (n,) on that
+        device, a Python float (one range for every ray) or None (+inf: the whole ray).  Returns a new torch.uint8 tensor (n,) of 0 / 1
+        on that device.  Asynchronous on `stream`, which is handled as in trace_rays (a tmax tensor is recorded on it like the rays)."""
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("occluded: rays must be a torch tensor, got %s" % type(rays).__name__)
+        if rays.dtype != torch.float32:
+            raise ValueError("occluded: rays must be float32, got %s" % rays.dtype)
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("occluded: rays must have shape (n, 6), got %s" % (tuple(rays.shape),))
+        if not rays.is_contiguous():
+            raise ValueError("occluded: rays must be contiguous")
+        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError("occluded: rays must be on cuda:%d, the scene's device, got %s" % (self.device, rays.device))
+        n = rays.shape[0]
+        if n > 0xFFFFFFC0:
+            raise ValueError("occluded: at most %d rays per call, got %d" % (0xFFFFFFC0, n))
+        if isinstance(tmax, torch.Tensor):
+            if tmax.dtype != torch.float32:
+                raise ValueError("occluded: tmax must be float32, got %s" % tmax.dtype)
+            if tuple(tmax.shape) != (n,):
+                raise ValueError("occluded: tmax must have shape (%d,), got %s" % (n, tuple(tmax.shape)))
+            if not tmax.is_contiguous():
+                raise ValueError("occluded: tmax must be contiguous")
+            if tmax.device != rays.device:
+                raise ValueError("occluded: tmax must be on the rays' device %s, got %s" % (rays.device, tmax.device))
+        elif tmax is not None and not isinstance(tmax, (int, float)):
+            raise ValueError("occluded: tmax must be a torch tensor, a float or None, got %s" % type(tmax).__name__)
+        alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+        with torch.cuda.stream(alloc_on):
+            out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            if tmax is not None and not isinstance(tmax, torch.Tensor):
+                tmax = torch.full((n,), float(tmax), dtype=torch.float32, device=rays.device)
+                if stream is not None and alloc_on is None:
+                    torch.cuda.current_stream(rays.device).synchronize()      # (a raw handle: torch cannot order the fill before it)
+        if n == 0:
+            return out
+        if alloc_on is not None:
+            rays.record_stream(alloc_on)
+            if tmax is not None:
+                tmax.record_stream(alloc_on)
+        _check(self.rtx.rtx_occluded_rays(self.gpu(), n, C.c_void_p(rays.data_ptr()), C.c_void_p(tmax.data_ptr()) if tmax is not None else None,
+                                          C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
+               "rtx_occluded_rays")
+        return out
 
     def device_mesh(self, mesh):
         """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,

@@ -16,6 +16,7 @@
 #include "../../include/rtx.h"
 #include "../../include/rtx_debug.h"
 #include "../../include/rtx_scene_edit.h"
+#include "../../include/rtx_query.h"
 #include "rtx_device.h"
 
 using namespace rtxd;
@@ -129,7 +130,8 @@ struct Knobs {
 	bool debugItems = false;             // RTX_DEBUG_ITEMS: rtx_counters_read prints the wave-level counters
 	int traceReorder = -1;               // knob trace_reorder: rtx_trace_rays groups the rays by key always (1), never (0), by their number and coherence (-1)
 	int traceOriginFirst = 1;            // knob trace_key_origin_first: the key's interleave starts with the origin's bits (1) or the direction's (0)
-	uint32_t dbgTile = 0;                // RTX_DBG_TILE=tx,ty (RTX_DBG builds): only this tile
+	int occludedSceneOrder = 0;          // knob occluded_scene_order: rtx_occluded_rays asks the objects in scene order (1) instead of spheres and planes first (0)
+	uint32_t dbgTile = 0;               // RTX_DBG_TILE=tx,ty (RTX_DBG builds): only this tile
 };
 
 struct rtx_scene {
@@ -198,6 +200,7 @@ struct rtx_scene {
 	uint32_t* rayKeys = nullptr; uint32_t* rayOrder = nullptr; void* raySortTemp = nullptr; size_t rayCap = 0, raySortBytes = 0;
 	uint32_t* rayWork = nullptr;
 	int rayHitBlocks[2] = { 0, 0 };
+	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
 	struct MeshLeaves { const float* boxes; uint32_t n; };      // 8 floats per non-empty leaf: true box lo, hi, reference count, -
@@ -1681,11 +1684,13 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 	else if (n == "debug_items") k.debugItems = value != 0;
 	else if (n == "trace_reorder") k.traceReorder = value < 0 ? -1 : (value != 0 ? 1 : 0);
 	else if (n == "trace_key_origin_first") k.traceOriginFirst = value != 0 ? 1 : 0;
+	else if (n == "occluded_scene_order") k.occludedSceneOrder = value != 0 ? 1 : 0;
 	else if (n == "prune_boxes") {
 		// (taken by the next launch; launches already queued keep the variant they were launched with)
 		k.pruneBoxes = value < 0 ? -1 : (value != 0 ? 1 : 0);
 		chooseBoxPrune(s);
 		s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;      // (the hit kernel's occupancy is the variant's)
+		for (auto& b : s->rayOccludedBlocks) b[0] = b[1] = 0;
 	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
 	return RTX_OK;
@@ -2200,6 +2205,8 @@ namespace {
 // rtx_trace_rays groups the rays by key from this many on, unless they already come in coherent groups (rtxRayKeyKernel; measured on one
 // MI355X: profiles/trace_rays_time.json)
 constexpr uint32_t kTraceReorderMin = 1u << 20;
+// rtx_occluded_rays' own threshold for the same rule (profiles/occluded_rays_time.json)
+constexpr uint32_t kOccludedReorderMin = kTraceReorderMin;
 
 // The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
 // for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
@@ -2244,6 +2251,37 @@ RayKernel rayColourKernel(const rtx_scene* s, bool cull)
 	if (cull) return s->boxPrune ? rtxRayColourKernel<true, true, 1, false> : rtxRayColourKernel<true, false, 1, false>;
 	return s->boxPrune ? rtxRayColourKernel<true, true, 0, false> : rtxRayColourKernel<true, false, 0, false>;
 }
+// (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
+typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
+OccludedKernel rayOccludedKernel(const rtx_scene* s, bool cull, bool sceneOrder)
+{
+	if (s->analytic) return rtxRayOccludedKernel<false, true, -1, true>;
+	if (sceneOrder) {
+		if (cull) return s->boxPrune ? rtxRayOccludedKernel<true, true, 1, true> : rtxRayOccludedKernel<true, false, 1, true>;
+		return s->boxPrune ? rtxRayOccludedKernel<true, true, 0, true> : rtxRayOccludedKernel<true, false, 0, true>;
+	}
+	if (cull) return s->boxPrune ? rtxRayOccludedKernel<true, true, 1, false> : rtxRayOccludedKernel<true, false, 1, false>;
+	return s->boxPrune ? rtxRayOccludedKernel<true, true, 0, false> : rtxRayOccludedKernel<true, false, 0, false>;
+}
+
+// The order of n rays grouped by key (rtx_rays.hip: box, key with the coherence check, stable sort), queued on st after rtxRayInitKernel:
+// *order = the scene's rayOrder (ensureRayScratch has sized it).
+int groupRays(rtx_scene* s, const Params& p, const float* rays_dev, uint32_t n, hipStream_t st, const uint32_t** order)
+{
+	// the camera's position and axes: the frame of the key's coordinates (rtx_rays.hip, rayCoords)
+	const float* M = p.view.camM;
+	const RayAxes ax = { { M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10] }, { p.view.camPos[0], p.view.camPos[1], p.view.camPos[2] } };
+	const uint32_t groups = (uint32_t)(((size_t)n + 255) / 256);
+	double* spread = (double*)(s->rayWork + 44);
+	hipLaunchKernelGGL(rtxRayBoxKernel, dim3(std::min<uint32_t>(groups, (uint32_t)s->numCUs * 8u)), dim3(256), 0, st, rays_dev, n, ax, s->rayWork + 32, spread);
+	// (by default the caller's order is kept where it is already as coherent: rtxRayKeyKernel; trace_reorder = 1 always sorts)
+	hipLaunchKernelGGL(rtxRayKeyKernel, dim3(groups), dim3(256), 0, st, rays_dev, n, ax, (const uint32_t*)(s->rayWork + 32), (const double*)spread,
+	                   s->knobs.traceOriginFirst, s->knobs.traceReorder < 0 ? 1 : 0, s->rayKeys);
+	size_t bytes = s->raySortBytes;
+	HIPCHK(rtxSortRayKeys(s->raySortTemp, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
+	*order = s->rayOrder;
+	return RTX_OK;
+}
 
 } // namespace
 
@@ -2266,20 +2304,7 @@ int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_
 	const uint32_t waves = (n + 63) / 64;
 	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork);
 	const uint32_t* order = nullptr;
-	if (reorder) {
-		// the camera's position and axes: the frame of the key's coordinates (rtx_rays.hip, rayCoords)
-		const float* M = p.view.camM;
-		const RayAxes ax = { { M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10] }, { p.view.camPos[0], p.view.camPos[1], p.view.camPos[2] } };
-		const uint32_t groups = (uint32_t)(((size_t)n + 255) / 256);
-		double* spread = (double*)(s->rayWork + 44);
-		hipLaunchKernelGGL(rtxRayBoxKernel, dim3(std::min<uint32_t>(groups, (uint32_t)s->numCUs * 8u)), dim3(256), 0, st, rays_dev, n, ax, s->rayWork + 32, spread);
-		// (by default the caller's order is kept where it is already as coherent: rtxRayKeyKernel; trace_reorder = 1 always sorts)
-		hipLaunchKernelGGL(rtxRayKeyKernel, dim3(groups), dim3(256), 0, st, rays_dev, n, ax, (const uint32_t*)(s->rayWork + 32), (const double*)spread,
-		                   s->knobs.traceOriginFirst, s->knobs.traceReorder < 0 ? 1 : 0, s->rayKeys);
-		size_t bytes = s->raySortBytes;
-		HIPCHK(rtxSortRayKeys(s->raySortTemp, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
-		order = s->rayOrder;
-	}
+	if (reorder && (rc = groupRays(s, p, rays_dev, n, st, &order))) return rc;
 	const bool cull = (p.view.flags & RTX_FLAG_BACKFACE_CULL) != 0;
 	if (showNormals(s)) {
 		p.workCounter = s->rayWork;
@@ -2302,6 +2327,38 @@ int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_
 			hipLaunchKernelGGL(rayColourKernel(s, cull), dim3(blocks), dim3(256), 0, st, p, order, colours_dev);
 		}
 	}
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_occluded_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const float* tmax_dev, uint8_t* occluded_dev, void* stream)
+{
+	RoctxRange range("Occluded rays (rtx_occluded_rays)");
+	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
+	if (n == 0) return RTX_OK;
+	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
+	if (!occluded_dev) return fail(RTX_ERR_ARG, "rtx_occluded_rays: no output (occluded is NULL)");
+	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	hipStream_t st = (hipStream_t)stream;
+	if ((rc = renderOn(s, st))) return rc;
+	const bool reorder = s->knobs.traceReorder < 0 ? n >= kOccludedReorderMin : s->knobs.traceReorder != 0;
+	if ((rc = ensureRayScratch(s, n, reorder, st))) return rc;
+	Params p = s->params;
+	p.probeRays = rays_dev; p.nProbe = n;
+	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork);
+	const uint32_t* order = nullptr;
+	if (reorder && (rc = groupRays(s, p, rays_dev, n, st, &order))) return rc;
+	const bool cull = (p.view.flags & RTX_FLAG_BACKFACE_CULL) != 0;
+	const bool sceneOrder = s->knobs.occludedSceneOrder != 0;
+	const OccludedKernel k = rayOccludedKernel(s, cull, sceneOrder);
+	int& perCU = s->rayOccludedBlocks[cull ? 1 : 0][sceneOrder ? 1 : 0];
+	if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k, 256, 0)); perCU = std::max(perCU, 1); }
+	p.workCounter = s->rayWork;
+	const uint32_t waves = (n + 63) / 64;
+	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
+	hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, tmax_dev, occluded_dev);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

@@ -1203,7 +1203,9 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 // state machine fits the register file, and a small frame lasts as long as its slowest wave's chain of dependent rays.
 // CULLK: options::useBackfaceCulling as the kernel knows it -- 1 on, 0 off (the product kernels: a per-view constant, so every kernel exists in both forms and
 // neither carries the other's walks), -1 read from the view at run time (the instrumented and the probe kernels)
-template <bool STATS, bool MESH = true, bool FEWRAYS = false, bool BOXES = true, int CULLK = -1>
+// KINDS: the objects looked at -- 0 all of them, in scene order (every kernel that needs the nearest hit, and castRayWave's shadow rays);
+// 1 only the spheres and planes, 2 only the meshes (rtxRayOccludedKernel: an occlusion answer does not depend on the order of the objects)
+template <bool STATS, bool MESH = true, bool FEWRAYS = false, bool BOXES = true, int CULLK = -1, int KINDS = 0>
 __device__ __forceinline__ void traceWave(const Params& P, bool active, bool shadow, V3 o, V3 d, float tmax,
                                           Hit& h, Counts& cnt, uint32_t src = 0)
 {
@@ -1222,6 +1224,7 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 		const u32x16 rec = sload16(ob);         // type, material, pos[3], r2, normal[3], mesh, ...
 		const int type = (int)rec[0];
 		const int mat = (int)rec[1];
+		if (KINDS != 0 && (type == 3) != (KINDS == 2)) continue;
 		// transparent objects do not cast shadows (scene.cpp:733)
 		const bool consider = live && !(shadow && mat == 2);
 		if (ballot(consider) == 0) continue;

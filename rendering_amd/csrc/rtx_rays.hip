@@ -191,6 +191,59 @@ __global__ void __launch_bounds__(256) rtxRayHitKernel(const Params P, const uin
 	}
 }
 
+// rtx_occluded_rays (include/rtx_query.h): Render::trace of a ShadowRay whose info.tNear starts at the ray's range --
+// one byte per ray, 1 iff some opaque object reports tNear < tmax.  That is "the minimum of tNear over the opaque objects < tmax", which
+// depends neither on the order of the objects nor on which blocker is found first.  So the spheres and planes are asked first (a few
+// instructions per object) and the meshes are walked only for the lanes still unanswered (ORDER = false); ORDER = true keeps the scene
+// order (knob occluded_scene_order, for A/B runs).  A lane that is answered takes no further part (traceWave: live / consider), and an
+// object no lane has a question for is not entered (its ballot).  tmax == nullptr: +inf for every ray.
+// No hit record is kept or stored: of the Hit only obj >= 0 is read, so t, tri, u and v of the nearest triangle are dead outside the walk.
+template <bool MESH, bool BOXES, int CULLK, bool ORDER>
+__global__ void __launch_bounds__(256) rtxRayOccludedKernel(const Params P, const uint32_t* order, const float* tmax, uint8_t* occluded)
+{
+	const uint32_t lane = __lane_id();
+	const uint32_t nWork = (P.nProbe + 63) / 64;
+	Counts cnt = {};
+	for (;;) {
+		const uint32_t work = nextWork(P.workCounter);
+		if (work >= nWork) break;
+		const uint32_t k = work * 64 + lane;
+		const bool valid = k < P.nProbe;
+		uint32_t i; V3 o, d;
+		loadRay(P, order, k, valid, i, o, d);
+		const float tm = (valid && tmax) ? tmax[i] : __builtin_inff();
+		// (a NaN range occludes nothing: such a lane asks no object)
+		const bool asked = valid && !(tm != tm);
+		bool open = asked;
+		Hit h;
+		// A mesh records only t < FLT_MAX (scene.cpp:735, 740), so a range above FLT_MAX is FLT_MAX for its walk, whose bundle limit has
+		// to stay finite; a sphere or a plane is compared with the range itself.
+		const float tmWalk = tm > kFltMax ? kFltMax : tm;
+		if (!MESH) {
+			traceWave<false, false, false, BOXES, CULLK>(P, open, true, o, d, tm, h, cnt);
+			open = open && h.obj < 0;
+		}
+		else if (ORDER) {
+			traceWave<false, true, false, BOXES, CULLK>(P, open, true, o, d, tmWalk, h, cnt);
+			open = open && h.obj < 0;
+			// (what only the unbounded range admits: a sphere or plane at exactly FLT_MAX)
+			if (ballot(open && tm > kFltMax) != 0) {
+				traceWave<false, false, false, BOXES, CULLK, 1>(P, open && tm > kFltMax, true, o, d, tm, h, cnt);
+				open = open && h.obj < 0;
+			}
+		}
+		else {
+			traceWave<false, false, false, BOXES, CULLK, 1>(P, open, true, o, d, tm, h, cnt);
+			open = open && h.obj < 0;
+			if (ballot(open) != 0) {
+				traceWave<false, true, false, BOXES, CULLK, 2>(P, open, true, o, d, tmWalk, h, cnt);
+				open = open && h.obj < 0;
+			}
+		}
+		if (valid) occluded[i] = (asked && !open) ? 1 : 0;
+	}
+}
+
 // Render::castRay(ray, scene, 0): the pass-1 kernels' state machine (castRayWave) with CAM = false -- no ray is known to start at the
 // camera.  Recursion frames: the pass-1 area of rtx_scene::frames, indexed by the global lane (the grid is at most blocksPass1).
 template <bool MESH, bool BOXES, int CULLK, bool PLAIN>
@@ -247,6 +300,14 @@ template __global__ void rtxRayColourKernel<true, false, 0, PL>(const Params, co
 RTX_RAY_COLOUR_INSTANCES(false) RTX_RAY_COLOUR_INSTANCES(true)
 #undef RTX_RAY_COLOUR_INSTANCES
 template __global__ void rtxRayColourKernel<false, true, -1, false>(const Params, const uint32_t*, float*);
+#define RTX_RAY_OCCLUDED_INSTANCES(ORD)                                                                                       \
+template __global__ void rtxRayOccludedKernel<true, true, 1, ORD>(const Params, const uint32_t*, const float*, uint8_t*);   \
+template __global__ void rtxRayOccludedKernel<true, false, 1, ORD>(const Params, const uint32_t*, const float*, uint8_t*);  \
+template __global__ void rtxRayOccludedKernel<true, true, 0, ORD>(const Params, const uint32_t*, const float*, uint8_t*);   \
+template __global__ void rtxRayOccludedKernel<true, false, 0, ORD>(const Params, const uint32_t*, const float*, uint8_t*);
+RTX_RAY_OCCLUDED_INSTANCES(false) RTX_RAY_OCCLUDED_INSTANCES(true)
+#undef RTX_RAY_OCCLUDED_INSTANCES
+template __global__ void rtxRayOccludedKernel<false, true, -1, true>(const Params, const uint32_t*, const float*, uint8_t*);
 
 // The queue heads of the trace launches ([0] hits, [16] colours), the box of rtxRayBoxKernel ([32, 37) minima as ~0, [37, 42) maxima as 0)
 // and its spreads ([44, 54): five doubles, 0).
