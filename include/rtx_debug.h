@@ -105,6 +105,11 @@ int rtx_scene_mesh_read(rtx_scene* scene, uint32_t mesh, uint32_t* counts2, floa
 int rtx_scene_mesh_flat_read(rtx_scene* scene, uint32_t mesh, uint32_t* n_wide, void* wide_out, void* prune_out, uint32_t cap_wide, float* root_rec8);
 int rtx_scene_edit_times(rtx_scene* scene, float* ms4);
 
+/* Device allocations this library holds at the moment, in this process, and their bytes: everything behind scenes, acceleration structures and
+ * communicators, scratch of calls in progress included (not the caller's own buffers).  Back where it was once everything created since has been
+ * destroyed -- which a test can check on a GPU it shares with others.  Either pointer may be NULL. */
+int rtx_live_device_memory(size_t* allocations, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ RTX_SYMBOLS = [
     "rtx_cast_rays", "rtx_trace_rays", "rtx_kernel_time_reset", "rtx_kernel_time_stats", "rtx_tile_cost_read", "rtx_set_row_ownership",
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
-    "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read",
+    "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read", "rtx_live_device_memory",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
@@ -149,6 +149,7 @@ def load():
     rtx.rtx_scene_edit_times.argtypes = [vp, vp]
     rtx.rtx_kernel_variant.argtypes = [vp, C.POINTER(C.c_uint32)]
     rtx.rtx_ssaa_list_read.argtypes = [vp, vp, vp, C.c_size_t]
+    rtx.rtx_live_device_memory.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -174,6 +175,14 @@ def device_count():
     n = C.c_int(0)
     _check(rtx.rtx_device_count(C.byref(n)), "rtx_device_count")
     return n.value
+
+
+def live_device_memory():
+    """(allocations, bytes) of device memory the native library holds in this process (rtx_live_device_memory)."""
+    rtx, _ = load()
+    n, b = C.c_size_t(0), C.c_size_t(0)
+    _check(rtx.rtx_live_device_memory(C.byref(n), C.byref(b)), "rtx_live_device_memory")
+    return n.value, b.value
 
 
 def _np_ptr(a):

@@ -10,7 +10,9 @@
 #include <functional>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rtx.h"
@@ -18,8 +20,10 @@
 #include "../../include/rtx_scene_edit.h"
 #include "../../include/rtx_query.h"
 #include "rtx_device.h"
+#include "rtx_own.h"
 
 using namespace rtxd;
+using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown::PinnedArray;
 
 // single translation unit: the kernels are compiled together with their launch code
 #include "rtx_kernels.hip"
@@ -70,24 +74,13 @@ int fail(int code, const std::string& msg) { gErr = msg; return code; }
 			return fail(RTX_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
 	} while (0)
 
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-thread_local size_t gUploadedBytes = 0;     // bytes uploaded by the rtx_scene_create in progress
-
-template <typename T> int upload(std::vector<void*>& owned, const T* src, size_t count, const T** out)
+// Turns the three run-time choices of a launch -- the box test of the prune records, culling off / on, and a third flag of the kernel
+// family's own -- into template arguments: f(std::bool_constant, std::integral_constant<int, 0 | 1>, std::bool_constant).
+template <typename F> auto dispatchVariant(bool boxes, bool cull, bool third, F&& f)
 {
-	*out = nullptr;
-	if (!src || count == 0) return RTX_OK;
-	void* d = nullptr;
-	HIPCHK(hipMalloc(&d, count * sizeof(T)));
-	gUploadedBytes += count * sizeof(T);
-	owned.push_back(d);
-	HIPCHK(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
-	*out = (const T*)d;
-	return RTX_OK;
+	auto withThird = [&](auto b, auto c) { return third ? f(b, c, std::true_type()) : f(b, c, std::false_type()); };
+	auto withCull = [&](auto b) { return cull ? withThird(b, std::integral_constant<int, 1>()) : withThird(b, std::integral_constant<int, 0>()); };
+	return boxes ? withCull(std::true_type()) : withCull(std::false_type());
 }
 
 } // namespace
@@ -138,43 +131,42 @@ struct rtx_scene {
 	int device = 0;
 	int numCUs = 0;
 	Knobs knobs;
-	std::vector<void*> owned;     // device allocations freed on destroy
-	// the records as uploaded, kept for the edits (rtx_scene_set_object, rtx_scene_update_mesh: rtx_edit.hip): per mesh its device record, the
-	// allocations of its geometry, normals and tangents (replaced as a whole by rtx_scene_update_mesh) and their bytes; per object its record and
-	// its description
+	// device allocations that live as long as the scene.  Their counted bytes, with the meshes', are the scene data resident in HBM
+	// (rtx_scene_bytes: nodes, leaf references, shading arrays, maps, skybox)
+	DevBag owned;
+	// the records as uploaded, kept for the edits (rtx_scene_set_object, rtx_scene_update_mesh: rtx_edit.hip): per mesh its device record and the
+	// allocations of its geometry, normals and tangents (replaced as a whole by rtx_scene_update_mesh); per object its record and its description
 	std::vector<Mesh> meshRecs;
-	std::vector<std::vector<void*>> meshOwned;
-	std::vector<size_t> meshBytes;
+	std::vector<DevBag> meshOwned;
 	std::vector<Object> objectRecs;
 	std::vector<rtx_object> objectDescs;
-	void* sphereLeafDev = nullptr;     // the spheres' entry of meshLeaves once an edit has rebuilt it
-	void* flatScratch = nullptr; size_t flatScratchBytes = 0;      // rtx_scene_update_mesh: the device flatten's scratch (rtx_flatten.hip)
+	DevArray<float> sphereLeafDev;     // the spheres' entry of meshLeaves once an edit has rebuilt it
+	DevArray<char> flatScratch;        // rtx_scene_update_mesh: the device flatten's scratch (rtx_flatten.hip)
 	float editMs[4] = { 0, 0, 0, 0 };  // the last rtx_scene_update_mesh: build, read-back + flatten + upload, sources + estimate queued, whole call (host wall ms)
-	size_t sceneBytes = 0;        // bytes of scene data resident in HBM (nodes, leaf references, shading arrays, maps, skybox)
 	Params params;                // template of the kernel argument block
 	bool stats = false;
 	bool analytic = true;         // no object is a triangle mesh: the ray kernels without the walk are launched
 	bool boxPrune = false;        // some mesh has triangles small enough for the box test of the prune records: the kernels with it are launched
 	bool plain = true;            // every object is Diffuse and every light a point / distant light: the mesh kernels without recursion, powf and area-light sums are launched (PLAIN)
 	// lazily sized work buffers
-	float* frames = nullptr; size_t framesBytes = 0, framesArea = 0;
-	uint32_t* tileCost = nullptr; uint32_t* items = nullptr; size_t tileCap = 0;   // per-tile pass-1 cost, SSAA scan array (2 tiles + 1, then scan scratch)
-	uint32_t* ssaaPixels = nullptr; size_t ssaaPixCap = 0;                         // SSAA flagged-pixel list (<= W * H entries)
-	uint32_t* work = nullptr;     // 256 words: [1] SSAA queue head, [3] probe queue head, [8] SSAA list mode, [9] flagged pixels, [128 + 16 q] pass-1 queue head of XCD q
-	unsigned long long* counters = nullptr;
-	uint32_t* orderWork = nullptr;
+	DevArray<float> frames; size_t framesArea = 0;
+	DevArray<uint32_t> tileCost, items; size_t tileCap = 0;   // per-tile pass-1 cost, SSAA scan array (2 tiles + 1, then scan scratch), both good for tileCap tiles
+	DevArray<uint32_t> ssaaPixels;                            // SSAA flagged-pixel list (<= W * H entries)
+	DevArray<uint32_t> work;      // 256 words: [1] SSAA queue head, [3] probe queue head, [8] SSAA list mode, [9] flagged pixels, [128 + 16 q] pass-1 queue head of XCD q
+	DevArray<unsigned long long> counters;
+	DevArray<uint32_t> orderWork;
 	int blocksPass1 = 0, blocksSsaa = 0, blocksFrame = 0;
 	// rtx_render_frame: dependency counters (ready, sobel), flags, SSAA item queue, control words
-	uint32_t* tileDeps = nullptr; unsigned long long* tileFlags = nullptr; uint8_t* tileClass = nullptr; size_t depCap = 0;
-	unsigned long long* ssaaQueue = nullptr; size_t queueCap = 0;
-	unsigned long long* frameCtl = nullptr;
+	DevArray<uint32_t> tileDeps; DevArray<unsigned long long> tileFlags; DevArray<uint8_t> tileClass;
+	DevArray<unsigned long long> ssaaQueue;
+	DevArray<unsigned long long> frameCtl;
 	uint32_t epoch = 0;
 	// pass-1 tile queues (buildTileList): rebuilt when the view, the row range or the row ownership changes
 	std::vector<float> meshBounds;        // 6 floats per mesh: the root box
 	struct TileQueues {
 		std::vector<uint32_t> key;        // what the list was built for (view, row range, row ownership)
-		uint32_t* list = nullptr; size_t cap = 0;   // the queues in geometric order (ordered by cost: rtx_scene::orderedList)
-		uint8_t* need = nullptr; size_t needCap = 0; uint32_t listed = 0;
+		uint32_t* list = nullptr;         // the queues in geometric order (ordered by cost: rtx_scene::orderedList); this entry's part of listSlab
+		uint8_t* need = nullptr; uint32_t listed = 0;      // (need, countExpect: this entry's part of needSlab)
 		uint32_t* countExpect = nullptr; bool needValid = false;          // listed tiles by index % 64 (the frame kernel's completion counters)   // rtx_render_frame: listed tiles in each tile's 3x3 neighbourhood
 		bool costValid = false;           // tileCost holds the costs of a launch with this key
 		uint64_t lastUse = 0;
@@ -183,7 +175,13 @@ struct rtx_scene {
 		uint32_t frameSamples[2] = { 0, 0 };
 		uint32_t framesSeen = 0, generation = 0;
 		bool fusedGaveUp = false;         // the single launch once ended with an error for this view: three launches from then on
-		hipStream_t builtOn = nullptr; hipEvent_t builtEv = nullptr;      // the stream rtxTileListKernel wrote the list on, and its completion
+		hipStream_t builtOn = nullptr; Event builtEv;      // the stream rtxTileListKernel wrote the list on, and its completion
+		// the entry is about to hold another list, or its view's geometry has changed: what was measured on it no longer applies
+		void forget()
+		{
+			key.clear(); costValid = false;
+			frameMs[0] = frameMs[1] = -1.f; frameSamples[0] = frameSamples[1] = 0; framesSeen = 0; generation++; fusedGaveUp = false;
+		}
 	};
 	// the last frame rendered in one launch (rtx_frame_status renders it again in three if the launch gave up)
 	// (only while nothing it depends on has changed: the view and the row ownership it was rendered with are part of it, and
@@ -193,22 +191,22 @@ struct rtx_scene {
 	LastFused lastFused;
 	uint32_t framesRecovered = 0;
 	// rtx_render_ac: per-pixel counts when the caller passes none, and the frame's maximum
-	uint32_t* acCounts = nullptr; size_t acCap = 0;
-	uint32_t* acMax = nullptr;
+	DevArray<uint32_t> acCounts, acMax;
 	// rtx_trace_rays: sort keys (in, out) and the order of up to rayCap rays, the sort's scratch, queue heads + key box (rtxRayInitKernel);
 	// blocks per CU of the hit kernel launched for culling off / on (0: not asked yet)
-	uint32_t* rayKeys = nullptr; uint32_t* rayOrder = nullptr; void* raySortTemp = nullptr; size_t rayCap = 0, raySortBytes = 0;
-	uint32_t* rayWork = nullptr;
+	DevArray<uint32_t> rayKeys, rayOrder; size_t rayCap = 0;      // (rayKeys: 2 rayCap keys, rayOrder: rayCap)
+	DevArray<char> raySortTemp;
+	DevArray<uint32_t> rayWork;
 	int rayHitBlocks[2] = { 0, 0 };
 	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
 	struct MeshLeaves { const float* boxes; uint32_t n; };      // 8 floats per non-empty leaf: true box lo, hi, reference count, -
 	std::vector<MeshLeaves> meshLeaves;
-	uint32_t* costGrid = nullptr; size_t costGridCap = 0;
-	uint8_t* needSlab = nullptr; size_t needStride = 0;           // rtx_render_frame in one launch: neighbour counts + completion counters of the cached lists
-	uint32_t* listSlab = nullptr; size_t listStride = 0;         // the buffers of the 16 cached tile lists: ONE allocation (a hipMalloc per new view cost the host 3 ms)
-	uint32_t* orderedList = nullptr; size_t orderedCap = 0;      // the tile list of the next launch in the order of rtxTileOrderKernel
+	DevArray<uint32_t> costGrid;
+	DevArray<uint8_t> needSlab; size_t needStride = 0;           // rtx_render_frame in one launch: neighbour counts + completion counters of the cached lists
+	DevArray<uint32_t> listSlab; size_t listStride = 0;          // the buffers of the 16 cached tile lists: ONE allocation (a hipMalloc per new view cost the host 3 ms)
+	DevArray<uint32_t> orderedList;                              // the tile list of the next launch in the order of rtxTileOrderKernel
 	bool costsUsable = false;
 	// source copies of the prune records (rtxd::PruneRec, rtx_source.hip): per mesh the copies' base, the reference arrays and the
 	// slots' reference ranges; the point lights that have a copy; what the copies were last built for
@@ -227,17 +225,18 @@ struct rtx_scene {
 	// device (ADVICE r3 A5 / VERDICT r4 item 2).  The legacy null stream orders itself against the caller's blocking streams; for a non-blocking render
 	// stream the two events below carry the order both ways: the preparation waits for the last render call, the next render call for the preparation.
 	hipStream_t lastRenderStream = nullptr; bool rendered = false;
-	hipEvent_t evRenderDone = nullptr, evPrepDone = nullptr; bool prepRecorded = false; hipStream_t prepSeenBy = nullptr;
+	Event evPrepDone; bool prepRecorded = false; hipStream_t prepSeenBy = nullptr;
 	// every distinct non-null stream a render call was made on since the last preparation (pass 1 on A with the quantiser on B, two frames in flight:
 	// ADVICE r5): the preparation waits for each of them, and each waits for the preparation (prepSeen)
-	struct RenderStream { hipStream_t st = nullptr; hipEvent_t done = nullptr; bool active = false, prepSeen = false; };
+	struct RenderStream { hipStream_t st = nullptr; Event done; bool active = false, prepSeen = false; };
 	std::vector<RenderStream> renderStreams;
 	// tile-list plans travel through a ring of pinned host buffers read by rtxTileListKernel (no staging copy, no synchronisation)
-	struct PlanSlot { uint32_t* host = nullptr; uint32_t* dev = nullptr; size_t capWords = 0; hipEvent_t done = nullptr; bool used = false, shared = false; };
-	uint32_t* planRingBase = nullptr;
+	// (a slot is an eighth of planRingBase until a plan outgrows it: from then on it is the slot's own allocation)
+	struct PlanSlot { uint32_t* host = nullptr; uint32_t* dev = nullptr; size_t capWords = 0; PinnedArray<uint32_t> own; Event done; bool used = false; };
+	PinnedArray<uint32_t> planRingBase;
 	PlanSlot planRing[8]; unsigned planNext = 0;
 	bool verifyLists = false;             // knob verify_lists: every list built on the device is read back and compared with the host's construction (tests)
-	struct FrameProbe { hipEvent_t a = nullptr, b = nullptr; int mode = -1; size_t queue = 0; uint32_t generation = 0; bool pending = false, refresh = false; };
+	struct FrameProbe { Event a, b; int mode = -1; size_t queue = 0; uint32_t generation = 0; bool pending = false, refresh = false; };
 	FrameProbe probes[8];
 	unsigned probeNext = 0;
 	int lastFrameMode = -1, frameModeForced = -1;
@@ -250,7 +249,7 @@ struct rtx_scene {
 	// HIP-event pairs around every launch of {pass 1, sobel, ssaa} since the last rtx_kernel_time_reset
 	// By default only the most recent pair is kept (rtx_last_kernel_ms); rtx_kernel_time_reset starts accumulating
 	// pairs for rtx_kernel_time_stats, up to kMaxTimedLaunches per kernel (later launches overwrite the last pair).
-	std::vector<hipEvent_t> evPool[5];      // pass 1, sobel, ssaa, whole frame (rtx_render_frame), its single kernel
+	std::vector<Event> evPool[5];      // pass 1, sobel, ssaa, whole frame (rtx_render_frame), its single kernel
 	size_t evUsed[5] = { 0, 0, 0, 0, 0 };
 	bool evCollect = false;
 };
@@ -316,31 +315,90 @@ constexpr size_t kMaxTimedLaunches = 4096;
 constexpr uint32_t kSsaaSpreadSlots = 1u << 20;
 constexpr size_t kFrameCtlBytes = 256 * 64;      // the frame kernel's control block (FC_* in rtx_kernels.hip), every word on its own line
 
+// The variant of a launch: constants of the scene and the view, so that no kernel carries another's code.  The mesh kernels exist per
+// (box test of the prune records, culling mode, PLAIN); scenes without meshes and the instrumented launches have one kernel each.
+struct Variant { bool analytic, stats, boxes, cull, plain; };
+Variant variantOf(const rtx_scene* s)
+{
+	return { s->analytic, s->stats, s->boxPrune, (s->params.view.flags & RTX_FLAG_BACKFACE_CULL) != 0, s->plain };
+}
+
+// The kernel of each family for a variant.  (The families order their template parameters differently; the third flag of
+// dispatchVariant is PLAIN, the occlusion kernel's ORDER, or nothing at all for the hit kernel.)
+typedef void (*FrameKernel)(const Params);
+FrameKernel pass1Kernel(const Variant& v)
+{
+	if (v.stats) return rtxPass1Kernel<true>;
+	if (v.analytic) return rtxPass1Kernel<false, false>;
+	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> FrameKernel { return rtxPass1Kernel<false, true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+FrameKernel ssaaKernel(const Variant& v)
+{
+	if (v.stats) return rtxSsaaKernel<true>;
+	if (v.analytic) return rtxSsaaKernel<false, false>;
+	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> FrameKernel { return rtxSsaaKernel<false, true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+FrameKernel frameKernel(const Variant& v)      // (rtx_render_frame has no instrumented variant)
+{
+	if (v.analytic) return rtxFrameKernel<false>;
+	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> FrameKernel { return rtxFrameKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+typedef void (*RayKernel)(const Params, const uint32_t*, float*);
+RayKernel rayHitKernel(const Variant& v)
+{
+	if (v.analytic) return rtxRayHitKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayKernel { return rtxRayHitKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+RayKernel rayColourKernel(const Variant& v)
+{
+	if (v.analytic) return rtxRayColourKernel<false, true, -1, false>;
+	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> RayKernel { return rtxRayColourKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+// (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
+typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
+OccludedKernel rayOccludedKernel(const Variant& v, bool sceneOrder)
+{
+	if (v.analytic) return rtxRayOccludedKernel<false, true, -1, true>;
+	return dispatchVariant(v.boxes, v.cull, sceneOrder, [](auto b, auto c, auto ord) -> OccludedKernel { return rtxRayOccludedKernel<true, decltype(b)::value, decltype(c)::value, decltype(ord)::value>; });
+}
+
+// Blocks of `kernel` (256 threads) a CU holds at once, asked once: perCU = 0 means not asked yet.
+int askBlocksPerCU(int& perCU, const void* kernel)
+{
+	if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, 0)); perCU = std::max(perCU, 1); }
+	return RTX_OK;
+}
+
+// ... and of the whole device, at most `knobPerCU` per CU when that knob is set
+int residentBlocks(const rtx_scene* s, FrameKernel kernel, int knobPerCU, int* blocks)
+{
+	int b = 0;
+	const int rc = askBlocksPerCU(b, (const void*)kernel);
+	if (rc) return rc;
+	if (knobPerCU >= 1 && knobPerCU < b) b = knobPerCU;
+	*blocks = b * s->numCUs;
+	return RTX_OK;
+}
+
 int ensureWork(rtx_scene* s)
 {
 	HIPCHK(hipSetDevice(s->device));
 	if (!s->work) {
-		HIPCHK(hipMalloc((void**)&s->work, 256 * sizeof(uint32_t)));
+		HIPCHK(s->work.reserve(256));
 		HIPCHK(hipMemset(s->work, 0, 256 * sizeof(uint32_t)));
-		HIPCHK(hipMalloc((void**)&s->orderWork, 8 * 32 * 32 * sizeof(uint32_t)));      // rtxTileOrderKernel: entries per (queue, block, class)
-		HIPCHK(hipMalloc((void**)&s->counters, 16 * sizeof(unsigned long long)));
+		HIPCHK(s->orderWork.reserve(8 * 32 * 32));      // rtxTileOrderKernel: entries per (queue, block, class)
+		HIPCHK(s->counters.reserve(16));
 		HIPCHK(hipMemset(s->counters, 0, 16 * sizeof(unsigned long long)));
-		int b = 0;
-		// (a PLAIN scene's pass-1 kernels may hold more blocks per CU than the general ones: RTX_WAVES_PLAIN)
-		if (s->plain) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rtxPass1Kernel<false, true, true, 1, true>, 256, 0));
-		else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rtxPass1Kernel<false>, 256, 0));
-		if (b < 1) b = 1;
-		if (s->knobs.pass1BlocksPerCU >= 1 && s->knobs.pass1BlocksPerCU < b) b = s->knobs.pass1BlocksPerCU;
-		s->blocksPass1 = b * s->numCUs;
-		HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rtxSsaaKernel<false>, 256, 0));
-		if (b < 1) b = 1;
-		if (s->knobs.ssaaBlocksPerCU >= 1 && s->knobs.ssaaBlocksPerCU < b) b = s->knobs.ssaaBlocksPerCU;
-		s->blocksSsaa = b * s->numCUs;
-		if (s->analytic) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rtxFrameKernel<false>, 256, 0));
-		else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rtxFrameKernel<true>, 256, 0));
-		if (b < 1) b = 1;
-		if (s->knobs.frameBlocksPerCU >= 1 && s->knobs.frameBlocksPerCU < b) b = s->knobs.frameBlocksPerCU;
-		s->blocksFrame = b * s->numCUs;
+		// The occupancy is asked of the mesh kernels with the box test and culling, whatever variant the scene launches: PLAIN counts for
+		// pass 1 only (a PLAIN scene's pass-1 kernels may hold more blocks per CU than the general ones: RTX_WAVES_PLAIN), a scene without
+		// meshes for the frame kernel only.
+		Variant v = { false, false, true, true, s->plain };
+		int rc;
+		if ((rc = residentBlocks(s, pass1Kernel(v), s->knobs.pass1BlocksPerCU, &s->blocksPass1))) return rc;
+		v.plain = false;
+		if ((rc = residentBlocks(s, ssaaKernel(v), s->knobs.ssaaBlocksPerCU, &s->blocksSsaa))) return rc;
+		v.analytic = s->analytic;
+		if ((rc = residentBlocks(s, frameKernel(v), s->knobs.frameBlocksPerCU, &s->blocksFrame))) return rc;
 	}
 	const int blocks = std::max(s->blocksFrame, s->blocksPass1 > s->blocksSsaa ? s->blocksPass1 : s->blocksSsaa);
 	const uint32_t totalLanes = (uint32_t)blocks * 256u;
@@ -349,31 +407,20 @@ int ensureWork(rtx_scene* s)
 	const size_t area = (size_t)(slots < 1 ? 1 : slots) * kFrameFields * sizeof(float) * totalLanes;
 	const size_t need = 2 * area;
 	s->framesArea = area / sizeof(float);
-	if (need > s->framesBytes) {
-		if (s->frames) HIPCHK(hipFree(s->frames));
-		s->frames = nullptr; s->framesBytes = 0;
-		HIPCHK(hipMalloc((void**)&s->frames, need));
-		s->framesBytes = need;
-	}
+	HIPCHK(s->frames.reserve(need / sizeof(float)));
 	const uint32_t txFull = (s->params.view.width + 7) / 8, tyFull = (s->params.view.height + 7) / 8;
 	const size_t tiles = (size_t)txFull * tyFull;
 	if (tiles > s->tileCap) {
-		if (s->tileCost) { HIPCHK(hipFree(s->tileCost)); HIPCHK(hipFree(s->items)); }
-		s->tileCost = nullptr; s->items = nullptr; s->tileCap = 0;
-		HIPCHK(hipMalloc((void**)&s->tileCost, 2 * tiles * sizeof(uint32_t)));      // pass-1 cost of every tile; its slowest SSAA item (rtxSsaaKernel)
-		HIPCHK(hipMalloc((void**)&s->items, (tiles * 2 + 1 + tiles / 256 + 1024) * sizeof(uint32_t)));
+		s->tileCap = 0;      // (until both are in place)
+		HIPCHK(s->tileCost.reserve(2 * tiles));      // pass-1 cost of every tile; its slowest SSAA item (rtxSsaaKernel)
+		HIPCHK(s->items.reserve(tiles * 2 + 1 + tiles / 256 + 1024));
 		HIPCHK(hipMemset(s->tileCost, 0, 2 * tiles * sizeof(uint32_t)));
 		s->tileCap = tiles;
 	}
 	// every tile's pixels padded to whole waves, plus kSsaaSpreadSlots for the tiles that get 4-pixel waves (a slot budget
 	// enforced on the device by rtxSsaaCountKernel: a tile over the budget is packed normally)
 	const size_t pixels = tiles * 64 + kSsaaSpreadSlots;
-	if (pixels > s->ssaaPixCap) {
-		if (s->ssaaPixels) HIPCHK(hipFree(s->ssaaPixels));
-		s->ssaaPixels = nullptr; s->ssaaPixCap = 0;
-		HIPCHK(hipMalloc((void**)&s->ssaaPixels, pixels * sizeof(uint32_t)));
-		s->ssaaPixCap = pixels;
-	}
+	HIPCHK(s->ssaaPixels.reserve(pixels));
 	s->params.tileCost = s->tileCost;
 	s->params.tilesXFull = txFull;
 	s->params.frames = s->frames;
@@ -390,7 +437,7 @@ int prepBegin(rtx_scene* s)
 {
 	for (auto& rs : s->renderStreams) {
 		if (!rs.active) continue;
-		if (!rs.done) HIPCHK(hipEventCreateWithFlags(&rs.done, hipEventDisableTiming));
+		HIPCHK(rs.done.create(hipEventDisableTiming));
 		// (a stream the caller has destroyed since is reported as an invalid handle: nothing of it can still be running)
 		if (hipEventRecord(rs.done, rs.st) == hipSuccess) HIPCHK(hipStreamWaitEvent(nullptr, rs.done, 0));
 		else (void)hipGetLastError();
@@ -400,7 +447,7 @@ int prepBegin(rtx_scene* s)
 }
 int prepEnd(rtx_scene* s)
 {
-	if (!s->evPrepDone) HIPCHK(hipEventCreateWithFlags(&s->evPrepDone, hipEventDisableTiming));
+	HIPCHK(s->evPrepDone.create(hipEventDisableTiming));
 	HIPCHK(hipEventRecord(s->evPrepDone, nullptr));
 	s->prepRecorded = true; s->prepSeenBy = nullptr;
 	for (auto& rs : s->renderStreams) rs.prepSeen = false;
@@ -482,12 +529,7 @@ int estimateCosts(rtx_scene* s)
 	const uint32_t txFull = (v.width + 7) / 8, tyFull = (v.height + 7) / 8;
 	const uint32_t gridW = (txFull + 1) / 2, gridH = (tyFull + 1) / 2;
 	const size_t cells = (size_t)gridW * gridH;
-	if (cells > s->costGridCap) {
-		if (s->costGrid) HIPCHK(hipFree(s->costGrid));
-		s->costGrid = nullptr; s->costGridCap = 0;
-		HIPCHK(hipMalloc((void**)&s->costGrid, 2 * cells * sizeof(uint32_t)));
-		s->costGridCap = cells;
-	}
+	HIPCHK(s->costGrid.reserve(2 * cells));
 	HIPCHK(hipMemsetAsync(s->costGrid, 0, 2 * cells * sizeof(uint32_t), nullptr));
 	// the camera's splat and the leaves' shadows on the planes, per point / distant light (rtxCostSplatKernel): one launch per set of leaves
 	SplatSources src;
@@ -518,15 +560,14 @@ int estimateCosts(rtx_scene* s)
 }
 
 // Records an event on `st`; events come in (start, stop) pairs per launch.
-
 int stamp(rtx_scene* s, int which, hipStream_t st)
 {
 	if ((s->evUsed[which] & 1) == 0 && s->evUsed[which] >= 2 && (!s->evCollect || s->evUsed[which] >= 2 * kMaxTimedLaunches))
 		s->evUsed[which] -= 2;          // start of a launch: recycle the previous pair
 	if (s->evUsed[which] == s->evPool[which].size()) {
-		hipEvent_t e;
-		HIPCHK(hipEventCreate(&e));
-		s->evPool[which].push_back(e);
+		Event e;
+		HIPCHK(e.create());
+		s->evPool[which].push_back(std::move(e));
 	}
 	HIPCHK(hipEventRecord(s->evPool[which][s->evUsed[which]++], st));
 	return RTX_OK;
@@ -736,8 +777,9 @@ int flattenMesh(const rtx_mesh& m, bool pruneWanted, FlatMesh& out)
 
 // The geometry of mesh `mi` as rtx_scene_create uploads it: the flattened tree (flattenMesh), the leaf boxes of the cost estimate, the wide nodes,
 // the prune blocks and their source copies, the leaf references, the bundle-splitting terms.  Fills those fields of dm, the mesh's source
-// record, its leaves and its root box; every allocation goes to `owned`.  rtx_scene_update_mesh (rtx_edit.hip) runs it again on new triangles.
-int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, std::vector<void*>& owned, Mesh& dm, rtx_scene::SrcMesh& sm,
+// record, its leaves and its root box; every allocation goes to `owned` (counted as scene data, but for the sources' scratch).
+// rtx_scene_update_mesh (rtx_edit.hip) does the same on the device for new triangles (deviceMeshGeometry, rtx_flatten.hip).
+int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, DevBag& owned, Mesh& dm, rtx_scene::SrcMesh& sm,
                        rtx_scene::MeshLeaves& leaves, float bounds[6])
 {
 	FlatMesh flat;
@@ -761,8 +803,7 @@ int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nL
 		makeRef(m, r, refA[r], refB[r], refC[r]);
 	}
 	for (int c = 0; c < 6; c++) bounds[c] = m.n_nodes ? m.node_bounds[c] : 0.0f;
-	int rc;
-	if ((rc = upload(owned, nodes.data(), nodes.size(), &dm.nodes))) return rc;
+	HIPCHK(owned.upload(nodes.data(), nodes.size(), &dm.nodes));
 	{
 		// for the first-frame cost estimate: the TRUE box of every non-empty leaf's triangles and its reference count
 		std::vector<float> lb;
@@ -777,10 +818,10 @@ int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nL
 			lb.insert(lb.end(), { lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], (float)m.leaf_count[i], 0.0f });
 		}
 		const float* dev = nullptr;
-		if ((rc = upload(owned, lb.data(), lb.size(), &dev))) return rc;
+		HIPCHK(owned.upload(lb.data(), lb.size(), &dev));
 		leaves = { dev, (uint32_t)(lb.size() / 8) };
 	}
-	if ((rc = upload(owned, wide.data(), wide.size(), &dm.wide))) return rc;
+	HIPCHK(owned.upload(wide.data(), wide.size(), &dm.wide));
 	dm.nWide = (uint32_t)wide.size();
 	// prune blocks: copy 0 (any ray) followed by the source copies (rtxd::PruneRec: the camera's, the point lights'), all
 	// equal to copy 0 until buildSources patches their P
@@ -788,9 +829,7 @@ int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nL
 	const uint32_t nCopies = (s->knobs.sources && !prune.empty()) ? 2u + std::min<uint32_t>(nLights, kMaxSrcLights) : 1u;
 	if (!prune.empty()) {
 		PruneBlock* pb = nullptr;
-		if (hipMalloc((void**)&pb, (size_t)nCopies * prune.size() * sizeof(PruneBlock)) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (prune blocks)"));
-		owned.push_back(pb);
-		gUploadedBytes += (size_t)nCopies * prune.size() * sizeof(PruneBlock);
+		if (owned.alloc(&pb, (size_t)nCopies * prune.size() * sizeof(PruneBlock)) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (prune blocks)"));
 		for (uint32_t c = 0; c < nCopies; c++)
 			if (hipMemcpy(pb + (size_t)c * prune.size(), prune.data(), prune.size() * sizeof(PruneBlock), hipMemcpyHostToDevice) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMemcpy (prune blocks)"));
 		dm.prune = pb;
@@ -799,14 +838,13 @@ int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nL
 	dm.vmax = vmaxMesh;
 	dm.rootRec = rootRec;
 	if (!(vmaxMesh < 0x1p40f)) { dm.prune = nullptr; dm.rootRec.h[0] = dm.rootRec.h[1] = dm.rootRec.h[2] = INFINITY; }      // (huge or non-finite coordinates: nothing is pruned)
-	if ((rc = upload(owned, refA.data(), refA.size(), &dm.refA))) return rc;
-	if ((rc = upload(owned, refB.data(), refB.size(), &dm.refB))) return rc;
-	if ((rc = upload(owned, refC.data(), refC.size(), &dm.refC))) return rc;
+	HIPCHK(owned.upload(refA.data(), refA.size(), &dm.refA));
+	HIPCHK(owned.upload(refB.data(), refB.size(), &dm.refB));
+	HIPCHK(owned.upload(refC.data(), refC.size(), &dm.refC));
 	if (sm.base && vmaxMesh < 0x1p40f && m.n_refs) {
 		sm.nRefs = m.n_refs; sm.refA = dm.refA; sm.refB = dm.refB; sm.refC = dm.refC; sm.vmax = vmaxMesh; sm.meshIndex = mi;
-		if ((rc = upload(owned, flat.slotRange.data(), flat.slotRange.size(), &sm.slotRange))) return rc;
-		if (hipMalloc((void**)&sm.refP, ((size_t)m.n_refs + m.n_refs / 64 + 2) * sizeof(float)) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (source scratch)"));
-		owned.push_back(sm.refP);
+		HIPCHK(owned.upload(flat.slotRange.data(), flat.slotRange.size(), &sm.slotRange));
+		if (owned.alloc(&sm.refP, ((size_t)m.n_refs + m.n_refs / 64 + 2) * sizeof(float), false) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (source scratch)"));
 		sm.blockP = sm.refP + m.n_refs;
 	}
 	else sm.base = nullptr;
@@ -849,6 +887,29 @@ void meshObjectRecord(const rtx_scene* s, Object& d, const Mesh& dm, const rtx_s
 	d.pruneBoxes = (dm.prune && std::isfinite(dm.rootRec.P) && dm.rootRec.P < 1.0f / 216.0f) ? 1u : 0u;
 }
 
+// The spheres' and planes' share of what preparing a view reads (rtx_scene_create; again after rtx_scene_set_object, rtx_edit.hip): the planes the
+// cost estimate casts shadows on, the longest plane normal a shadow ray's origin is offset along and, returned, the spheres' entry of the estimate.
+std::vector<float> analyticEstimate(rtx_scene* s, const rtx_object* objects, size_t n)
+{
+	std::vector<float> sb;
+	s->estPlanes.clear();
+	s->srcNmax = 1.0f;
+	for (size_t i = 0; i < n; i++) {
+		const rtx_object& o = objects[i];
+		if (o.type == RTX_OBJ_PLANE) {
+			s->estPlanes.push_back({ { o.pos[0], o.pos[1], o.pos[2], o.normal[0], o.normal[1], o.normal[2] } });
+			const double nl = std::sqrt((double)o.normal[0] * o.normal[0] + (double)o.normal[1] * o.normal[1] + (double)o.normal[2] * o.normal[2]);
+			if (!(nl <= 1e30)) s->srcNmax = INFINITY; else s->srcNmax = std::max(s->srcNmax, (float)(nl * 1.000001));
+		}
+		// spheres take part in the first-frame cost estimate like leaves: a mirror or a glass ball is where the deep recursions start
+		if (o.type != RTX_OBJ_SPHERE || !(o.radius2 > 0) || !std::isfinite(o.radius2)) continue;
+		const float r = std::sqrt(o.radius2), w = (o.material == 1 || o.material == 2) ? 4000.0f : 300.0f;
+		sb.insert(sb.end(), { o.pos[0] - r, o.pos[1] - r, o.pos[2] - r, o.pos[0] + r, o.pos[1] + r, o.pos[2] + r, w, 0.0f });
+	}
+	s->params.srcNmax2 = s->srcNmax * s->srcNmax * 1.00001f;
+	return sb;
+}
+
 } // namespace
 
 extern "C" {
@@ -877,43 +938,40 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 	hipDeviceProp_t prop;
 	HIPCHK(hipGetDeviceProperties(&prop, device));
 
-	rtx_scene* s = new rtx_scene;
+	// (a scene that cannot be completed is destroyed on the way out)
+	std::unique_ptr<rtx_scene, void (*)(rtx_scene*)> hold(new rtx_scene, rtx_scene_destroy);
+	rtx_scene* s = hold.get();
 	readKnobs(s->knobs);
 	s->tileQueues.reserve(16);
-	gUploadedBytes = 0;
 	s->device = device;
 	s->numCUs = prop.multiProcessorCount;
 	memset(&s->params, 0, sizeof(Params));
-	auto bail = [&](int code) { rtx_scene_destroy(s); return code; };
 
 	// meshes: nodes -> 32-byte records, leaf references -> (v0, e1, e2, tri) in three parallel arrays
 	std::vector<Mesh> meshes(desc->n_meshes);
-	s->meshOwned.resize(desc->n_meshes); s->meshBytes.assign(desc->n_meshes, 0);
+	s->meshOwned.resize(desc->n_meshes);
 	for (uint32_t mi = 0; mi < desc->n_meshes; mi++) {
 		const rtx_mesh& m = desc->meshes[mi];
 		if (!m.node_bounds || !m.node_skip || !m.leaf_begin || !m.leaf_count || (m.n_refs && !m.refs) || (m.n_tris && (!m.tri_pos || !m.tri_nrm || !m.tri_uv)))
-			return bail(fail(RTX_ERR_ARG, "mesh arrays missing"));
-		if (m.normal_map && !m.tri_tb) return bail(fail(RTX_ERR_ARG, "normal map without tangents"));
+			return fail(RTX_ERR_ARG, "mesh arrays missing");
+		if (m.normal_map && !m.tri_tb) return fail(RTX_ERR_ARG, "normal map without tangents");
 		Mesh& dm = meshes[mi];
 		memset(&dm, 0, sizeof(dm));
 		rtx_scene::SrcMesh sm;
 		rtx_scene::MeshLeaves leaves{ nullptr, 0 };
 		float bounds[6];
-		const size_t bytes0 = gUploadedBytes;
+		// (the mesh's own allocations are what rtx_scene_update_mesh replaces; uv and maps stay for the scene's life)
 		int rc;
-		if ((rc = uploadMeshGeometry(s, m, mi, desc->n_lights, s->meshOwned[mi], dm, sm, leaves, bounds))) return bail(rc);
+		if ((rc = uploadMeshGeometry(s, m, mi, desc->n_lights, s->meshOwned[mi], dm, sm, leaves, bounds))) return rc;
 		s->meshBounds.insert(s->meshBounds.end(), bounds, bounds + 6);
 		s->meshLeaves.push_back(leaves);
 		s->srcMeshes.push_back(sm);
-		if ((rc = upload(s->meshOwned[mi], m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm))) return bail(rc);
-		const size_t bytesUv = gUploadedBytes;
-		if ((rc = upload(s->owned, m.tri_uv, (size_t)m.n_tris * 6, &dm.uv))) return bail(rc);
-		const size_t bytesTb = gUploadedBytes;
-		if ((rc = upload(s->meshOwned[mi], m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb))) return bail(rc);
-		s->meshBytes[mi] = (bytesUv - bytes0) + (gUploadedBytes - bytesTb);
-		if ((rc = upload(s->owned, m.diffuse_map, (size_t)m.diffuse_w * m.diffuse_h * 3, &dm.diffuse))) return bail(rc);
-		if ((rc = upload(s->owned, m.normal_map, (size_t)m.normal_w * m.normal_h * 3, &dm.normal))) return bail(rc);
-		if ((rc = upload(s->owned, m.specular_map, (size_t)m.specular_w * m.specular_h, &dm.specular))) return bail(rc);
+		HIPCHK(s->meshOwned[mi].upload(m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm));
+		HIPCHK(s->owned.upload(m.tri_uv, (size_t)m.n_tris * 6, &dm.uv));
+		HIPCHK(s->meshOwned[mi].upload(m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb));
+		HIPCHK(s->owned.upload(m.diffuse_map, (size_t)m.diffuse_w * m.diffuse_h * 3, &dm.diffuse));
+		HIPCHK(s->owned.upload(m.normal_map, (size_t)m.normal_w * m.normal_h * 3, &dm.normal));
+		HIPCHK(s->owned.upload(m.specular_map, (size_t)m.specular_w * m.specular_h, &dm.specular));
 		dm.dW = m.diffuse_w; dm.dH = m.diffuse_h; dm.nW = m.normal_w; dm.nH = m.normal_h; dm.sW = m.specular_w; dm.sH = m.specular_h;
 	}
 	std::vector<Object> objs(desc->n_objects);
@@ -921,39 +979,21 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		const rtx_object& o = desc->objects[i];
 		Object& d = objs[i];
 		memset(&d, 0, sizeof(d));
-		if (o.type < RTX_OBJ_SPHERE || o.type > RTX_OBJ_MESH) return bail(fail(RTX_ERR_ARG, "bad object type"));
-		if (o.material < 0 || o.material > 3) return bail(fail(RTX_ERR_ARG, "bad material"));
-		if (o.type == RTX_OBJ_MESH && (o.mesh < 0 || (uint32_t)o.mesh >= desc->n_meshes)) return bail(fail(RTX_ERR_ARG, "bad mesh index"));
+		if (o.type < RTX_OBJ_SPHERE || o.type > RTX_OBJ_MESH) return fail(RTX_ERR_ARG, "bad object type");
+		if (o.material < 0 || o.material > 3) return fail(RTX_ERR_ARG, "bad material");
+		if (o.type == RTX_OBJ_MESH && (o.mesh < 0 || (uint32_t)o.mesh >= desc->n_meshes)) return fail(RTX_ERR_ARG, "bad mesh index");
 		if (o.type == RTX_OBJ_MESH) s->analytic = false;
 		if (o.material != 0) s->plain = false;
-		if (o.type == RTX_OBJ_PLANE) {
-			s->estPlanes.push_back({ { o.pos[0], o.pos[1], o.pos[2], o.normal[0], o.normal[1], o.normal[2] } });
-			const double nl = std::sqrt((double)o.normal[0] * o.normal[0] + (double)o.normal[1] * o.normal[1] + (double)o.normal[2] * o.normal[2]);
-			if (!(nl <= 1e30)) s->srcNmax = INFINITY; else s->srcNmax = std::max(s->srcNmax, (float)(nl * 1.000001));
-		}
 		d.type = o.type; d.material = o.material;
 		memcpy(d.pos, o.pos, 12); memcpy(d.color, o.color, 12); memcpy(d.normal, o.normal, 12);
 		d.ior = o.ior; d.ambient = o.ambient; d.diffuse = o.diffuse; d.specular = o.specular; d.nSpecular = o.n_specular;
 		d.r2 = o.radius2; d.mesh = o.mesh;
-		if (o.type == RTX_OBJ_MESH) {
-			const Mesh& dm = meshes[o.mesh];
-			meshObjectRecord(s, d, dm, s->srcMeshes[o.mesh]);
-			if (d.pruneBoxes && s->knobs.pruneBoxes != 0) s->boxPrune = true;
-			if (s->knobs.pruneBoxes > 0 && dm.prune) s->boxPrune = true;
-		}
+		if (o.type == RTX_OBJ_MESH) meshObjectRecord(s, d, meshes[o.mesh], s->srcMeshes[o.mesh]);
 	}
 	{
-		// spheres take part in the first-frame cost estimate like leaves: a mirror or a glass ball is where the deep recursions start
-		std::vector<float> sb;
-		for (uint32_t i = 0; i < desc->n_objects; i++) {
-			const rtx_object& o = desc->objects[i];
-			if (o.type != RTX_OBJ_SPHERE || !(o.radius2 > 0) || !std::isfinite(o.radius2)) continue;
-			const float r = std::sqrt(o.radius2), w = (o.material == 1 || o.material == 2) ? 4000.0f : 300.0f;
-			sb.insert(sb.end(), { o.pos[0] - r, o.pos[1] - r, o.pos[2] - r, o.pos[0] + r, o.pos[1] + r, o.pos[2] + r, w, 0.0f });
-		}
+		const std::vector<float> sb = analyticEstimate(s, desc->objects, desc->n_objects);
 		const float* dev = nullptr;
-		int rc0;
-		if ((rc0 = upload(s->owned, sb.data(), sb.size(), &dev))) return bail(rc0);
+		HIPCHK(s->owned.upload(sb.data(), sb.size(), &dev));
 		if (!sb.empty()) s->meshLeaves.push_back({ dev, (uint32_t)(sb.size() / 8) });
 	}
 	std::vector<Light> lights(desc->n_lights);
@@ -961,7 +1001,7 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		const rtx_light& l = desc->lights[i];
 		Light& d = lights[i];
 		memset(&d, 0, sizeof(d));
-		if (l.type < RTX_LIGHT_DISTANT || l.type > RTX_LIGHT_AREA) return bail(fail(RTX_ERR_ARG, "bad light type"));
+		if (l.type < RTX_LIGHT_DISTANT || l.type > RTX_LIGHT_AREA) return fail(RTX_ERR_ARG, "bad light type");
 		d.type = l.type; memcpy(d.color, l.color, 12); d.intensity = l.intensity;
 		memcpy(d.dir, l.dir, 12); memcpy(d.pos, l.pos, 12);
 		d.nPoints = l.n_points;
@@ -973,35 +1013,33 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		else if (l.type == RTX_LIGHT_AREA) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f + 4.0f * (float)std::min<uint32_t>(l.n_points, 4096u) } });
 		if (l.type == RTX_LIGHT_AREA) s->plain = false;
 		if (l.type == RTX_LIGHT_AREA) {
-			if (!l.points || l.n_points == 0) return bail(fail(RTX_ERR_ARG, "area light without sample points"));
-			int rc;
-			if ((rc = upload(s->owned, l.points, (size_t)l.n_points * 3, &d.points))) return bail(rc);
+			if (!l.points || l.n_points == 0) return fail(RTX_ERR_ARG, "area light without sample points");
+			HIPCHK(s->owned.upload(l.points, (size_t)l.n_points * 3, &d.points));
 		}
 	}
 	int rc;
-	if ((rc = upload(s->owned, meshes.data(), meshes.size(), &s->params.meshes))) return bail(rc);
-	if ((rc = upload(s->owned, objs.data(), objs.size(), &s->params.objects))) return bail(rc);
+	HIPCHK(s->owned.upload(meshes.data(), meshes.size(), &s->params.meshes));
+	HIPCHK(s->owned.upload(objs.data(), objs.size(), &s->params.objects));
 	s->meshRecs = meshes; s->objectRecs = objs;
+	chooseBoxPrune(s);
 	s->objectDescs.assign(desc->objects, desc->objects + desc->n_objects);
-	if ((rc = upload(s->owned, lights.data(), lights.size(), &s->params.lights))) return bail(rc);
+	HIPCHK(s->owned.upload(lights.data(), lights.size(), &s->params.lights));
 	s->params.nObjects = desc->n_objects; s->params.nLights = desc->n_lights;
 	s->params.nSrcLights = s->knobs.sources ? std::min<uint32_t>(desc->n_lights, kMaxSrcLights) : 0u;
-	s->params.srcNmax2 = s->srcNmax * s->srcNmax * 1.00001f;      // (srcNmax is final here: every object has been looked at)
 	if (desc->sky_w && desc->sky_h && desc->sky[0]) {
 		const float* faces[6];
 		for (int k = 0; k < 6; k++) {
-			if (!desc->sky[k]) return bail(fail(RTX_ERR_ARG, "skybox face missing"));
-			if ((rc = upload(s->owned, desc->sky[k], (size_t)desc->sky_w * desc->sky_h * 3, &faces[k]))) return bail(rc);
+			if (!desc->sky[k]) return fail(RTX_ERR_ARG, "skybox face missing");
+			HIPCHK(s->owned.upload(desc->sky[k], (size_t)desc->sky_w * desc->sky_h * 3, &faces[k]));
 		}
-		if ((rc = upload(s->owned, faces, 6, &s->params.sky))) return bail(rc);
+		HIPCHK(s->owned.upload(faces, 6, &s->params.sky));
 		s->params.skyW = desc->sky_w; s->params.skyH = desc->sky_h;
 	}
-	if ((rc = setView(s, &desc->view))) return bail(rc);
-	if ((rc = ensureWork(s))) return bail(rc);
-	if ((rc = prepareView(s))) return bail(rc);
-	if ((rc = prepEnd(s))) return bail(rc);
-	s->sceneBytes = gUploadedBytes;
-	*out = s;
+	if ((rc = setView(s, &desc->view))) return rc;
+	if ((rc = ensureWork(s))) return rc;
+	if ((rc = prepareView(s))) return rc;
+	if ((rc = prepEnd(s))) return rc;
+	*out = hold.release();
 	return RTX_OK;
 }
 
@@ -1010,38 +1048,6 @@ void rtx_scene_destroy(rtx_scene* s)
 	if (!s) return;
 	(void)hipSetDevice(s->device);
 	(void)hipDeviceSynchronize();
-	for (void* p : s->owned) (void)hipFree(p);
-	for (auto& v : s->meshOwned) for (void* p : v) (void)hipFree(p);
-	if (s->sphereLeafDev) (void)hipFree(s->sphereLeafDev);
-	if (s->flatScratch) (void)hipFree(s->flatScratch);
-	if (s->frames) (void)hipFree(s->frames);
-	if (s->tileCost) { (void)hipFree(s->tileCost); (void)hipFree(s->items); }
-	if (s->needSlab) (void)hipFree(s->needSlab);
-	if (s->listSlab) (void)hipFree(s->listSlab);
-	if (s->tileDeps) (void)hipFree(s->tileDeps);
-	if (s->tileFlags) (void)hipFree(s->tileFlags);
-	if (s->tileClass) (void)hipFree(s->tileClass);
-	for (auto& pr : s->probes) { if (pr.a) (void)hipEventDestroy(pr.a); if (pr.b) (void)hipEventDestroy(pr.b); }
-	for (auto& q : s->tileQueues) if (q.builtEv) (void)hipEventDestroy(q.builtEv);
-	for (auto& rs : s->renderStreams) if (rs.done) (void)hipEventDestroy(rs.done);
-	for (auto& sl : s->planRing) { if (sl.done) (void)hipEventDestroy(sl.done); if (sl.host && !sl.shared) (void)hipHostFree(sl.host); }
-	if (s->planRingBase) (void)hipHostFree(s->planRingBase);
-	if (s->evRenderDone) (void)hipEventDestroy(s->evRenderDone);
-	if (s->evPrepDone) (void)hipEventDestroy(s->evPrepDone);
-	if (s->ssaaQueue) (void)hipFree(s->ssaaQueue);
-	if (s->costGrid) (void)hipFree(s->costGrid);
-	if (s->orderedList) (void)hipFree(s->orderedList);
-	if (s->frameCtl) (void)hipFree(s->frameCtl);
-	if (s->ssaaPixels) (void)hipFree(s->ssaaPixels);
-	if (s->acCounts) (void)hipFree(s->acCounts);
-	if (s->acMax) (void)hipFree(s->acMax);
-	if (s->rayKeys) { (void)hipFree(s->rayKeys); (void)hipFree(s->rayOrder); }
-	if (s->raySortTemp) (void)hipFree(s->raySortTemp);
-	if (s->rayWork) (void)hipFree(s->rayWork);
-	if (s->work) {
-		(void)hipFree(s->work); (void)hipFree(s->counters); (void)hipFree(s->orderWork);
-		for (int i = 0; i < 5; i++) for (hipEvent_t e : s->evPool[i]) (void)hipEventDestroy(e);
-	}
 	delete s;
 }
 
@@ -1116,8 +1122,7 @@ int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t ti
 	if (s->tileQueues.size() < 16) s->tileQueues.emplace_back();
 	rtx_scene::TileQueues* e = &s->tileQueues[0];
 	for (auto& q : s->tileQueues) { if (!q.list) { e = &q; break; } if (q.lastUse < e->lastUse) e = &q; }
-	e->costValid = false; e->key.clear();
-	e->frameMs[0] = e->frameMs[1] = -1.f; e->frameSamples[0] = e->frameSamples[1] = 0; e->framesSeen = 0; e->generation++; e->fusedGaveUp = false;
+	e->forget();
 	const uint32_t H = p.view.height;
 	auto rowOwnedH = [&](uint32_t y) { return p.bandH == 0 || (y / p.bandH) % p.nParts == p.part; };
 	auto rowRenderedH = [&](uint32_t y) {
@@ -1178,23 +1183,18 @@ int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t ti
 	const size_t frameWords = 16 + (size_t)((p.view.width + 7) / 8) * ((p.view.height + 7) / 8);
 	if (std::max(listWords, frameWords) > s->listStride) {
 		HIPCHK(hipDeviceSynchronize());      // (growing: an earlier launch may still be reading the buffer that is freed)
-		if (s->listSlab) HIPCHK(hipFree(s->listSlab));
-		s->listSlab = nullptr; s->listStride = 0;
+		s->listStride = 0;
 		for (auto& q : s->tileQueues) { q.list = nullptr; q.key.clear(); q.costValid = false; }      // every cached list lived in the old slab
 		const size_t stride = (std::max(listWords, frameWords) + 4095) & ~(size_t)4095;
-		HIPCHK(hipMalloc((void**)&s->listSlab, 16 * stride * sizeof(uint32_t)));
+		HIPCHK(s->listSlab.reserve(16 * stride));
 		s->listStride = stride;
 	}
 	e->list = s->listSlab + (size_t)(e - s->tileQueues.data()) * s->listStride;
-	e->cap = s->listStride;
 	// the ordered copy, where every tile may be listed in sixteen parts: ONE buffer per scene, shared by the cached lists (the
 	// launch that consumes it follows the ordering kernels on the same stream)
-	if (16 * std::max(listWords, frameWords) > s->orderedCap) {
+	if (16 * std::max(listWords, frameWords) > s->orderedList.capacity()) {
 		HIPCHK(hipDeviceSynchronize());
-		if (s->orderedList) HIPCHK(hipFree(s->orderedList));
-		s->orderedList = nullptr; s->orderedCap = 0;
-		HIPCHK(hipMalloc((void**)&s->orderedList, 16 * std::max(listWords, frameWords) * sizeof(uint32_t)));
-		s->orderedCap = 16 * std::max(listWords, frameWords);
+		HIPCHK(s->orderedList.reserve(16 * std::max(listWords, frameWords)));
 	}
 	// The plan goes through a ring of pinned host buffers the kernel reads directly; a slot is taken again eight lists later (its event says whether the
 	// kernel that read it has run: it has, unless eight views were set without the device getting a turn).  The list that is recycled may still be read
@@ -1204,34 +1204,29 @@ int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t ti
 		if (!s->planRing[0].host) {
 			// all eight slots in one pinned allocation, on first use (rtx_scene_create: not on the path of a new view), each good for 2 048 tile rows
 			const size_t each = 16 + 4 * 2048;
-			uint32_t* hostAll = nullptr; uint32_t* devAll = nullptr;
-			HIPCHK(hipHostMalloc((void**)&hostAll, 8 * each * sizeof(uint32_t), hipHostMallocMapped));
-			HIPCHK(hipHostGetDevicePointer((void**)&devAll, hostAll, 0));
+			HIPCHK(s->planRingBase.reserve(8 * each));
 			for (int k = 0; k < 8; k++) {
-				s->planRingBase = hostAll;
-				s->planRing[k].host = hostAll + k * each; s->planRing[k].dev = devAll + k * each; s->planRing[k].capWords = each; s->planRing[k].shared = true;
-				HIPCHK(hipEventCreateWithFlags(&s->planRing[k].done, hipEventDisableTiming));
+				s->planRing[k].host = s->planRingBase.host() + k * each; s->planRing[k].dev = s->planRingBase.dev() + k * each; s->planRing[k].capWords = each;
+				HIPCHK(s->planRing[k].done.create(hipEventDisableTiming));
 			}
 		}
 		rtx_scene::PlanSlot& slot = s->planRing[s->planNext++ & 7u];
 		if (slot.used) HIPCHK(hipEventSynchronize(slot.done));
 		if (plan.size() > slot.capWords) {
-			if (slot.shared) { slot.host = nullptr; slot.shared = false; }      // (a slot of the common allocation is simply left behind: freed with slot 0)
-			if (slot.host) HIPCHK(hipHostFree(slot.host));
-			slot.host = nullptr; slot.capWords = 0;
+			// (its part of the common allocation is simply left behind)
+			slot.host = slot.dev = nullptr; slot.capWords = 0;
 			const size_t want = std::max<size_t>(plan.size(), 16 + 4 * 1100);
-			HIPCHK(hipHostMalloc((void**)&slot.host, want * sizeof(uint32_t), hipHostMallocMapped));
-			HIPCHK(hipHostGetDevicePointer((void**)&slot.dev, slot.host, 0));
-			slot.capWords = want;
+			HIPCHK(slot.own.reserve(want));
+			slot.host = slot.own.host(); slot.dev = slot.own.dev(); slot.capWords = want;
 		}
-		if (!slot.done) HIPCHK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+		HIPCHK(slot.done.create(hipEventDisableTiming));
 		memcpy(slot.host, plan.data(), plan.size() * sizeof(uint32_t));
 		const uint32_t cols = std::max(std::max(tilesX, nStrips), 16u);
 		hipLaunchKernelGGL(rtxTileListKernel, dim3((cols + 255) / 256, std::max(tilesY, 1u)), dim3(256), 0, st, (const uint32_t*)slot.dev, tilesX, nStrips, in0, in1, sIn0, sIn1, e->list);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(slot.done, st));
 		slot.used = true;
-		if (!e->builtEv) HIPCHK(hipEventCreateWithFlags(&e->builtEv, hipEventDisableTiming));
+		HIPCHK(e->builtEv.create(hipEventDisableTiming));
 		HIPCHK(hipEventRecord(e->builtEv, st));
 		e->builtOn = st;
 	}
@@ -1261,8 +1256,6 @@ int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t ti
 		HIPCHK(hipMemcpy(got.data(), e->list, listWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
 		if (want != got) return fail(RTX_ERR_DEVICE, "buildTileList: the list written on the device differs from the host's construction");
 	}
-	const std::vector<uint32_t>& list = plan;      // (only its size is used below)
-	(void)list;
 	e->listed = (uint32_t)(listWords - 16);
 	e->needValid = false;      // (computed on the device when the single launch first uses this list: renderFrameFused)
 	e->key = key;
@@ -1274,29 +1267,25 @@ int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t ti
 // Buffers of the single-launch frame (renderFrameFused): dependency counters, flags, the 64 SSAA item queues, the control block.
 int ensureFrameBuffers(rtx_scene* s, size_t tiles, size_t* perQueueOut)
 {
-	if (tiles > s->depCap) {
+	// (the three grow together; each keeps its own capacity, so a call that fails half-way leaves nothing behind that a later one would not see)
+	if (tiles > s->tileClass.capacity() || 4 * tiles > s->tileDeps.capacity() || tiles > s->tileFlags.capacity()) {
 		HIPCHK(hipDeviceSynchronize());
-		if (s->tileDeps) { HIPCHK(hipFree(s->tileDeps)); HIPCHK(hipFree(s->tileFlags)); HIPCHK(hipFree(s->tileClass)); }
-		s->tileDeps = nullptr; s->tileFlags = nullptr; s->tileClass = nullptr; s->depCap = 0;
-		HIPCHK(hipMalloc((void**)&s->tileClass, tiles));
-		HIPCHK(hipMalloc((void**)&s->tileDeps, 4 * tiles * sizeof(uint32_t)));      // pass-1 count, Sobel count, quarter costs, quarter count
-		HIPCHK(hipMalloc((void**)&s->tileFlags, tiles * sizeof(unsigned long long)));
-		s->depCap = tiles;
+		HIPCHK(s->tileClass.reserve(tiles));
+		HIPCHK(s->tileDeps.reserve(4 * tiles));      // pass-1 count, Sobel count, quarter costs, quarter count
+		HIPCHK(s->tileFlags.reserve(tiles));
 	}
 	// 64 queues; in all up to 4 items per tile (16 flagged pixels each) plus the budget of extra items for tiles that get
 	// 4-pixel items.  The items are dealt round the queues, so each holds about 1/64 of them: twice that, and some.
 	const size_t perQueue = s->knobs.frameQueueCap ? s->knobs.frameQueueCap : 2 * ((4 * tiles + kSsaaSpreadSlots / 16) / 64) + 256;
 	if (tiles >= (1u << 24)) return fail(RTX_ERR_ARG, "frame too large for rtx_render_frame");
-	if (64 * perQueue != s->queueCap) {
+	if (64 * perQueue != s->ssaaQueue.capacity()) {      // (exactly the size the kernel is told: a smaller frame shrinks it)
 		HIPCHK(hipDeviceSynchronize());
-		if (s->ssaaQueue) HIPCHK(hipFree(s->ssaaQueue));
-		s->ssaaQueue = nullptr; s->queueCap = 0;
-		HIPCHK(hipMalloc((void**)&s->ssaaQueue, 64 * perQueue * sizeof(unsigned long long)));
+		s->ssaaQueue.reset();
+		HIPCHK(s->ssaaQueue.reserve(64 * perQueue));
 		HIPCHK(hipMemset(s->ssaaQueue, 0, 64 * perQueue * sizeof(unsigned long long)));
-		s->queueCap = 64 * perQueue;
 	}
 	if (!s->frameCtl) {
-		HIPCHK(hipMalloc((void**)&s->frameCtl, kFrameCtlBytes));
+		HIPCHK(s->frameCtl.reserve(kFrameCtlBytes / sizeof(unsigned long long)));
 		HIPCHK(hipMemset(s->frameCtl, 0, kFrameCtlBytes));      // (rtxFrameClearKernel keeps an error word it finds)
 	}
 	*perQueueOut = perQueue;
@@ -1329,21 +1318,6 @@ int prepareView(rtx_scene* s)
 
 } // namespace
 
-
-// The mesh kernels exist per (box test of the prune records, culling mode, PLAIN): constants of the scene / the view, so that no kernel carries another's code.
-#define RTX_LAUNCH_MESH_KERNEL(K, PRE, blocks_, st_, p_)                                                                        \
-	do {                                                                                                                       \
-		const bool cullOn_ = ((p_).view.flags & RTX_FLAG_BACKFACE_CULL) != 0, box_ = s->boxPrune, plain_ = s->plain;            \
-		if (plain_) {                                                                                                          \
-			if (cullOn_) { if (box_) hipLaunchKernelGGL((K<PRE true, 1, true>), dim3(blocks_), dim3(256), 0, st_, p_); else hipLaunchKernelGGL((K<PRE false, 1, true>), dim3(blocks_), dim3(256), 0, st_, p_); } \
-			else { if (box_) hipLaunchKernelGGL((K<PRE true, 0, true>), dim3(blocks_), dim3(256), 0, st_, p_); else hipLaunchKernelGGL((K<PRE false, 0, true>), dim3(blocks_), dim3(256), 0, st_, p_); }        \
-		}                                                                                                                      \
-		else {                                                                                                                 \
-			if (cullOn_) { if (box_) hipLaunchKernelGGL((K<PRE true, 1>), dim3(blocks_), dim3(256), 0, st_, p_); else hipLaunchKernelGGL((K<PRE false, 1>), dim3(blocks_), dim3(256), 0, st_, p_); } \
-			else { if (box_) hipLaunchKernelGGL((K<PRE true, 0>), dim3(blocks_), dim3(256), 0, st_, p_); else hipLaunchKernelGGL((K<PRE false, 0>), dim3(blocks_), dim3(256), 0, st_, p_); }        \
-		}                                                                                                                      \
-	} while (0)
-#define RTX_COMMA ,
 
 namespace {
 
@@ -1439,9 +1413,7 @@ int rtx_render_pass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb
 	const uint32_t wavesNeeded = (p.nTiles + 3) / 4;
 	if (blocks > wavesNeeded) blocks = wavesNeeded ? wavesNeeded : 1;
 	if ((rc = stamp(s, 0, st))) return rc;
-	if (s->stats) hipLaunchKernelGGL(rtxPass1Kernel<true>, dim3(blocks), dim3(256), 0, st, p);
-	else if (s->analytic) hipLaunchKernelGGL((rtxPass1Kernel<false, false>), dim3(blocks), dim3(256), 0, st, p);
-	else RTX_LAUNCH_MESH_KERNEL(rtxPass1Kernel, false RTX_COMMA true RTX_COMMA, blocks, st, p);
+	hipLaunchKernelGGL(pass1Kernel(variantOf(s)), dim3(blocks), dim3(256), 0, st, p);
 	HIPCHK(hipGetLastError());
 	if ((rc = stamp(s, 0, st))) return rc;
 	return RTX_OK;
@@ -1485,18 +1457,16 @@ static int renderFrameFused(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, fl
 		// (the 16 cached lists share one allocation: per entry `needStride` bytes of neighbour counts, then 66 counters)
 		if (tiles > s->needStride) {
 			HIPCHK(hipDeviceSynchronize());
-			if (s->needSlab) HIPCHK(hipFree(s->needSlab));
-			s->needSlab = nullptr; s->needStride = 0;
+			s->needStride = 0;
 			for (auto& q : s->tileQueues) { q.need = nullptr; q.countExpect = nullptr; q.needValid = false; }
 			const size_t stride = (tiles + 4095) & ~(size_t)4095;
-			HIPCHK(hipMalloc((void**)&s->needSlab, 16 * (stride + 512)));
+			HIPCHK(s->needSlab.reserve(16 * (stride + 512)));
 			s->needStride = stride;
 		}
 		{
 			const size_t idx = (size_t)(tq - s->tileQueues.data());
 			tq->need = s->needSlab + idx * (s->needStride + 512);
 			tq->countExpect = (uint32_t*)(tq->need + s->needStride);
-			tq->needCap = s->needStride;
 		}
 		HIPCHK(hipMemsetAsync(s->tileClass, 0, tiles, st));      // (scratch here: the marks; the classes are written later)
 		HIPCHK(hipMemsetAsync(tq->countExpect, 0, 66 * sizeof(uint32_t), st));
@@ -1510,14 +1480,14 @@ static int renderFrameFused(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, fl
 	p.tileReady = s->tileDeps; p.tileSobel = s->tileDeps + tiles;
 	p.tileNeed = tq->need; p.tileFlags = s->tileFlags;
 	p.ssaaQueue = s->ssaaQueue; p.frameCtl = s->frameCtl;
-	p.listedTiles = tq->listed; p.epoch = s->epoch; p.queueCap = (uint32_t)perQueue; p.veryBudget = kSsaaSpreadSlots / 16;
+	p.listedTiles = tq->listed; p.epoch = s->epoch; p.queueCap = (uint32_t)perQueue;
 	p.countExpect = tq->countExpect;
 	p.heavyTicks = s->knobs.heavyTicks;
 	p.veryBudget = s->knobs.spreadSlots / 16;
 	{
 		const size_t most = std::max<size_t>(4 * tiles, maskInClear ? maskBytes : 0);
 		hipLaunchKernelGGL(rtxFrameClearKernel, dim3((unsigned)std::min<size_t>((most + 255) / 256, 2048)), dim3(256), 0, st, s->work, s->tileDeps, 4 * tiles,
-		                   (uint32_t*)s->frameCtl, (uint32_t)(kFrameCtlBytes / 4), (uint32_t)FC_ERROR, maskInClear ? mask_dev + (size_t)rowBegin * W : nullptr, maskInClear ? maskBytes : 0);
+		                   (uint32_t*)s->frameCtl.get(), (uint32_t)(kFrameCtlBytes / 4), (uint32_t)FC_ERROR, maskInClear ? mask_dev + (size_t)rowBegin * W : nullptr, maskInClear ? maskBytes : 0);
 	}
 	p.tileList = tq->list;
 	p.splitLimits = s->work + 18;
@@ -1539,8 +1509,7 @@ static int renderFrameFused(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, fl
 	const uint32_t wavesNeeded = p.nTiles;       // (blocks: quarters of slow tiles and SSAA items want waves too)
 	if (blocks > wavesNeeded) blocks = wavesNeeded ? wavesNeeded : 1;
 	if ((rc = stamp(s, 4, st))) return rc;
-	if (s->analytic) hipLaunchKernelGGL(rtxFrameKernel<false>, dim3(blocks), dim3(256), 0, st, p);
-	else RTX_LAUNCH_MESH_KERNEL(rtxFrameKernel, true RTX_COMMA, blocks, st, p);
+	hipLaunchKernelGGL(frameKernel(variantOf(s)), dim3(blocks), dim3(256), 0, st, p);
 	HIPCHK(hipGetLastError());
 	if ((rc = stamp(s, 4, st))) return rc;
 	return RTX_OK;
@@ -1640,7 +1609,7 @@ int rtx_render_frame(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb
 	rtx_scene::FrameProbe* pr = nullptr;
 	if (probing) {
 		pr = &s->probes[s->probeNext++ & 7u];
-		if (!pr->a) { HIPCHK(hipEventCreate(&pr->a)); HIPCHK(hipEventCreate(&pr->b)); }
+		HIPCHK(pr->a.create()); HIPCHK(pr->b.create());
 		pr->pending = false;
 		HIPCHK(hipEventRecord(pr->a, st));
 	}
@@ -1699,9 +1668,10 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 int rtx_kernel_variant(rtx_scene* s, uint32_t* bits)
 {
 	if (!s || !bits) return fail(RTX_ERR_ARG, "scene/bits is NULL");
-	// the fields RTX_LAUNCH_MESH_KERNEL, rayHitKernel and rayColourKernel read at launch
-	*bits = (s->boxPrune ? RTX_VARIANT_BOXES : 0u) | (s->plain ? RTX_VARIANT_PLAIN : 0u) | (s->analytic ? RTX_VARIANT_ANALYTIC : 0u) |
-	        (s->stats ? RTX_VARIANT_STATS : 0u) | ((s->params.view.flags & RTX_FLAG_BACKFACE_CULL) ? RTX_VARIANT_CULL : 0u);
+	// the very value the kernel of every family is chosen by at launch (pass1Kernel ... rayOccludedKernel)
+	const Variant v = variantOf(s);
+	*bits = (v.boxes ? RTX_VARIANT_BOXES : 0u) | (v.plain ? RTX_VARIANT_PLAIN : 0u) | (v.analytic ? RTX_VARIANT_ANALYTIC : 0u) |
+	        (v.stats ? RTX_VARIANT_STATS : 0u) | (v.cull ? RTX_VARIANT_CULL : 0u);
 	return RTX_OK;
 }
 
@@ -1762,7 +1732,7 @@ int rtx_frame_status(rtx_scene* s, uint32_t* status)
 #endif
 	// the error word of the last frame, or the one an earlier frame left since the last call (kept by rtxFrameClearKernel)
 	uint32_t err = 0, earlier = 0;
-	HIPCHK(hipMemcpy(&err, (const uint32_t*)s->frameCtl + FC_ERROR, sizeof(err), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(&err, (const uint32_t*)s->frameCtl.get() + FC_ERROR, sizeof(err), hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(&earlier, s->work + 24, sizeof(earlier), hipMemcpyDeviceToHost));
 	if (earlier) HIPCHK(hipMemset(s->work + 24, 0, sizeof(uint32_t)));
 	const bool lastFrameFailed = err != 0;
@@ -1772,7 +1742,7 @@ int rtx_frame_status(rtx_scene* s, uint32_t* status)
 	// The single launch gave up (1: queue entry never written, 2: work never completed, 3: SSAA queue overflow): its frame is
 	// incomplete.  The reference's Scene::render cannot deliver a partial frame (scene.cpp:595-606), so the frame is rendered
 	// again here, in three launches, into the same buffers, and the view stays with three launches.  status = the error | 0x100.
-	HIPCHK(hipMemset((uint32_t*)s->frameCtl + FC_ERROR, 0, sizeof(uint32_t)));
+	HIPCHK(hipMemset((uint32_t*)s->frameCtl.get() + FC_ERROR, 0, sizeof(uint32_t)));
 	const rtx_scene::LastFused lf = s->lastFused;
 	s->lastFused.valid = false;
 	if (lf.queue < s->tileQueues.size() && s->tileQueues[lf.queue].generation == lf.generation) s->tileQueues[lf.queue].fusedGaveUp = true;
@@ -1834,11 +1804,10 @@ int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, ui
 	p.workCounter = s->work + 1;
 	p.ssaaMask = mask_dev;
 	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.nTiles = (uint32_t)s->tileCap >= p.tilesXFull * ((H + 7) / 8) ? p.tilesXFull * ((H + 7) / 8) : 0;
+	p.nTiles = p.tilesXFull * ((H + 7) / 8);
 	p.ssaaScan = s->items;
 	p.frames = s->frames + s->framesArea;
 	p.ssaaPixels = s->ssaaPixels;
-	if (p.nTiles == 0 || p.view.width > 0xffffu || p.view.height > 0xffffu) return fail(RTX_ERR_ARG, "frame too large for the SSAA pixel list");
 	// flagged pixels -> one packed list; tiles on which pass 1 spent more than 0.25 ms go first (wall clock = 100 MHz)
 	const uint32_t heavyTicks = s->knobs.heavyTicks, spreadSlots = s->knobs.spreadSlots;
 	const uint32_t scanN = 2 * p.nTiles + 1;
@@ -1868,9 +1837,7 @@ int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, ui
 	hipLaunchKernelGGL(rtxSsaaScatterKernel, dim3((p.nTiles + 255) / 256), dim3(256), 0, st, p, s->items, mode, s->ssaaPixels);
 	HIPCHK(hipGetLastError());
 	s->ssaaListTiles = p.nTiles; s->ssaaListHeavy = heavyTicks; s->ssaaListSpread = spreadSlots;
-	if (s->stats) hipLaunchKernelGGL(rtxSsaaKernel<true>, dim3(s->blocksSsaa), dim3(256), 0, st, p);
-	else if (s->analytic) hipLaunchKernelGGL((rtxSsaaKernel<false, false>), dim3(s->blocksSsaa), dim3(256), 0, st, p);
-	else RTX_LAUNCH_MESH_KERNEL(rtxSsaaKernel, false RTX_COMMA true RTX_COMMA, s->blocksSsaa, st, p);
+	hipLaunchKernelGGL(ssaaKernel(variantOf(s)), dim3(s->blocksSsaa), dim3(256), 0, st, p);
 	HIPCHK(hipGetLastError());
 	if ((rc = stamp(s, 2, st))) return rc;
 	return RTX_OK;
@@ -1897,17 +1864,17 @@ int rtx_render_frame_host(rtx_scene* s, int with_ssaa, float* fb_host)
 	HIPCHK(hipSetDevice(s->device));
 	const uint32_t W = s->params.view.width, H = s->params.view.height;
 	const size_t bytes = (size_t)W * H * 3 * sizeof(float);
-	DevBuf fb, mask;
-	HIPCHK(hipMalloc(&fb.p, bytes));
-	HIPCHK(hipMemset(fb.p, 0, bytes));                 // new Vec3f[H*W] is zero-initialised (scene.cpp:599)
-	int rc = rtx_render_pass1(s, 0, H, (float*)fb.p, nullptr);
+	DevArray<float> fb; DevArray<uint8_t> mask;
+	HIPCHK(fb.reserve((size_t)W * H * 3));
+	HIPCHK(hipMemset(fb, 0, bytes));                 // new Vec3f[H*W] is zero-initialised (scene.cpp:599)
+	int rc = rtx_render_pass1(s, 0, H, fb, nullptr);
 	if (rc) return rc;
 	if (with_ssaa) {
-		HIPCHK(hipMalloc(&mask.p, (size_t)W * H));
-		if ((rc = rtx_sobel(s, (const float*)fb.p, 0, H, (uint8_t*)mask.p, nullptr))) return rc;
-		if ((rc = rtx_render_ssaa(s, (const uint8_t*)mask.p, 0, H, (float*)fb.p, nullptr))) return rc;
+		HIPCHK(mask.reserve((size_t)W * H));
+		if ((rc = rtx_sobel(s, fb, 0, H, mask, nullptr))) return rc;
+		if ((rc = rtx_render_ssaa(s, mask, 0, H, fb, nullptr))) return rc;
 	}
-	HIPCHK(hipMemcpy(fb_host, fb.p, bytes, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(fb_host, fb, bytes, hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
 
@@ -1923,15 +1890,12 @@ int rtx_render_ac(rtx_scene* s, float* fb_dev, uint32_t* counts_dev, void* strea
 	const size_t px = (size_t)W * H;
 	const size_t waves = (size_t)((W + 7) / 8) * ((H + 7) / 8);
 	if (waves >= (1ull << 32)) return fail(RTX_ERR_ARG, "frame too large");
-	if (!s->acMax) HIPCHK(hipMalloc((void**)&s->acMax, sizeof(uint32_t)));
+	HIPCHK(s->acMax.reserve(1));
 	uint32_t* counts = counts_dev;
 	if (!counts) {
-		if (s->acCap < px) {
+		if (s->acCounts.capacity() < px) {
 			HIPCHK(hipDeviceSynchronize());
-			if (s->acCounts) HIPCHK(hipFree(s->acCounts));
-			s->acCounts = nullptr; s->acCap = 0;
-			HIPCHK(hipMalloc((void**)&s->acCounts, px * sizeof(uint32_t)));
-			s->acCap = px;
+			HIPCHK(s->acCounts.reserve(px));
 		}
 		counts = s->acCounts;
 	}
@@ -2058,7 +2022,15 @@ int rtx_kernel_time_stats(rtx_scene* s, int which, uint32_t* launches, double* t
 int rtx_scene_bytes(rtx_scene* s, size_t* bytes)
 {
 	if (!s || !bytes) return fail(RTX_ERR_ARG, "scene/bytes is NULL");
-	*bytes = s->sceneBytes;
+	*bytes = s->owned.bytes();
+	for (const DevBag& m : s->meshOwned) *bytes += m.bytes();
+	return RTX_OK;
+}
+
+int rtx_live_device_memory(size_t* allocations, size_t* bytes)
+{
+	if (allocations) *allocations = rtxown::gLiveAllocations.load();
+	if (bytes) *bytes = rtxown::gLiveBytes.load();
 	return RTX_OK;
 }
 
@@ -2182,21 +2154,21 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 	if (n == 0) return RTX_OK;
 	int rc = ensureWork(s);
 	if (rc) return rc;
-	DevBuf dr, dh, dc;
-	HIPCHK(hipMalloc(&dr.p, (size_t)n * 24)); HIPCHK(hipMalloc(&dh.p, (size_t)n * 32)); HIPCHK(hipMalloc(&dc.p, (size_t)n * 12));
-	HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * 24, hipMemcpyHostToDevice));
+	DevArray<float> dr, dh, dc;
+	HIPCHK(dr.reserve((size_t)n * 6)); HIPCHK(dh.reserve((size_t)n * 8)); HIPCHK(dc.reserve((size_t)n * 3));
+	HIPCHK(hipMemcpy(dr, rays, (size_t)n * 24, hipMemcpyHostToDevice));
 	HIPCHK(hipMemset(s->work + 3, 0, sizeof(uint32_t)));
 	Params p = s->params;
 	p.workCounter = s->work + 3;
-	p.probeRays = (const float*)dr.p; p.probeHits = (float*)dh.p; p.probeColours = (float*)dc.p; p.nProbe = n;
+	p.probeRays = dr; p.probeHits = dh; p.probeColours = dc; p.nProbe = n;
 	uint32_t blocks = (uint32_t)s->blocksPass1;
 	const uint32_t need = ((n + 63) / 64 + 3) / 4;
 	if (blocks > need) blocks = need;
 	if (showNormals(s)) hipLaunchKernelGGL(rtxNormalsKernel, dim3(need), dim3(256), 0, nullptr, p, 2);
 	else hipLaunchKernelGGL(rtxProbeKernel, dim3(blocks), dim3(256), 0, nullptr, p);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(colours, dc.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(hits, dh, (size_t)n * 32, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(colours, dc, (size_t)n * 12, hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
 
@@ -2213,55 +2185,18 @@ constexpr uint32_t kOccludedReorderMin = kTraceReorderMin;
 // in case a smaller n ever needed more.)
 int ensureRayScratch(rtx_scene* s, uint32_t n, bool reorder, hipStream_t st)
 {
-	if (!s->rayWork) HIPCHK(hipMalloc((void**)&s->rayWork, 64 * sizeof(uint32_t)));
+	HIPCHK(s->rayWork.reserve(64));
 	if (!reorder) return RTX_OK;
 	if (n > s->rayCap) {
-		if (s->rayKeys) { HIPCHK(hipFree(s->rayKeys)); HIPCHK(hipFree(s->rayOrder)); }
-		s->rayKeys = s->rayOrder = nullptr; s->rayCap = 0;
-		HIPCHK(hipMalloc((void**)&s->rayKeys, 2 * (size_t)n * sizeof(uint32_t)));
-		HIPCHK(hipMalloc((void**)&s->rayOrder, (size_t)n * sizeof(uint32_t)));
+		s->rayCap = 0;      // (until both are in place)
+		HIPCHK(s->rayKeys.reserve(2 * (size_t)n));
+		HIPCHK(s->rayOrder.reserve(n));
 		s->rayCap = n;
 	}
 	size_t bytes = 0;
 	HIPCHK(rtxSortRayKeys(nullptr, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
-	if (bytes > s->raySortBytes) {
-		if (s->raySortTemp) HIPCHK(hipFree(s->raySortTemp));
-		s->raySortTemp = nullptr; s->raySortBytes = 0;
-		HIPCHK(hipMalloc(&s->raySortTemp, bytes));
-		s->raySortBytes = bytes;
-	}
+	HIPCHK(s->raySortTemp.reserve(bytes));
 	return RTX_OK;
-}
-
-// the kernels of the scene's kind (as RTX_LAUNCH_MESH_KERNEL picks them for pass 1)
-typedef void (*RayKernel)(const Params, const uint32_t*, float*);
-RayKernel rayHitKernel(const rtx_scene* s, bool cull)
-{
-	if (s->analytic) return rtxRayHitKernel<false, true, -1>;
-	if (cull) return s->boxPrune ? rtxRayHitKernel<true, true, 1> : rtxRayHitKernel<true, false, 1>;
-	return s->boxPrune ? rtxRayHitKernel<true, true, 0> : rtxRayHitKernel<true, false, 0>;
-}
-RayKernel rayColourKernel(const rtx_scene* s, bool cull)
-{
-	if (s->analytic) return rtxRayColourKernel<false, true, -1, false>;
-	if (s->plain) {
-		if (cull) return s->boxPrune ? rtxRayColourKernel<true, true, 1, true> : rtxRayColourKernel<true, false, 1, true>;
-		return s->boxPrune ? rtxRayColourKernel<true, true, 0, true> : rtxRayColourKernel<true, false, 0, true>;
-	}
-	if (cull) return s->boxPrune ? rtxRayColourKernel<true, true, 1, false> : rtxRayColourKernel<true, false, 1, false>;
-	return s->boxPrune ? rtxRayColourKernel<true, true, 0, false> : rtxRayColourKernel<true, false, 0, false>;
-}
-// (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
-typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
-OccludedKernel rayOccludedKernel(const rtx_scene* s, bool cull, bool sceneOrder)
-{
-	if (s->analytic) return rtxRayOccludedKernel<false, true, -1, true>;
-	if (sceneOrder) {
-		if (cull) return s->boxPrune ? rtxRayOccludedKernel<true, true, 1, true> : rtxRayOccludedKernel<true, false, 1, true>;
-		return s->boxPrune ? rtxRayOccludedKernel<true, true, 0, true> : rtxRayOccludedKernel<true, false, 0, true>;
-	}
-	if (cull) return s->boxPrune ? rtxRayOccludedKernel<true, true, 1, false> : rtxRayOccludedKernel<true, false, 1, false>;
-	return s->boxPrune ? rtxRayOccludedKernel<true, true, 0, false> : rtxRayOccludedKernel<true, false, 0, false>;
 }
 
 // The order of n rays grouped by key (rtx_rays.hip: box, key with the coherence check, stable sort), queued on st after rtxRayInitKernel:
@@ -2277,9 +2212,27 @@ int groupRays(rtx_scene* s, const Params& p, const float* rays_dev, uint32_t n, 
 	// (by default the caller's order is kept where it is already as coherent: rtxRayKeyKernel; trace_reorder = 1 always sorts)
 	hipLaunchKernelGGL(rtxRayKeyKernel, dim3(groups), dim3(256), 0, st, rays_dev, n, ax, (const uint32_t*)(s->rayWork + 32), (const double*)spread,
 	                   s->knobs.traceOriginFirst, s->knobs.traceReorder < 0 ? 1 : 0, s->rayKeys);
-	size_t bytes = s->raySortBytes;
-	HIPCHK(rtxSortRayKeys(s->raySortTemp, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
+	size_t bytes = s->raySortTemp.capacity();
+	HIPCHK(rtxSortRayKeys(s->raySortTemp.get(), &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
 	*order = s->rayOrder;
+	return RTX_OK;
+}
+
+// What rtx_trace_rays and rtx_occluded_rays do before their own launches: the scene's work buffers, the order against the preparation, the
+// decision to group the rays (from reorderMin rays on, unless the knob trace_reorder says always / never) and, if so, their order.
+// p: the argument block of the launches to come.
+int beginRays(rtx_scene* s, uint32_t n, const float* rays_dev, uint32_t reorderMin, hipStream_t st, Params& p, const uint32_t** order)
+{
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	if ((rc = renderOn(s, st))) return rc;
+	const bool reorder = s->knobs.traceReorder < 0 ? n >= reorderMin : s->knobs.traceReorder != 0;
+	if ((rc = ensureRayScratch(s, n, reorder, st))) return rc;
+	p = s->params;
+	p.probeRays = rays_dev; p.nProbe = n;
+	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork.get());
+	*order = nullptr;
+	if (reorder && (rc = groupRays(s, p, rays_dev, n, st, order))) return rc;
 	return RTX_OK;
 }
 
@@ -2293,19 +2246,12 @@ int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_
 	if (n == 0) return RTX_OK;
 	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
 	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
-	int rc = ensureWork(s);
-	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
-	if ((rc = renderOn(s, st))) return rc;
-	const bool reorder = s->knobs.traceReorder < 0 ? n >= kTraceReorderMin : s->knobs.traceReorder != 0;
-	if ((rc = ensureRayScratch(s, n, reorder, st))) return rc;
-	Params p = s->params;
-	p.probeRays = rays_dev; p.nProbe = n;
-	const uint32_t waves = (n + 63) / 64;
-	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork);
+	Params p;
 	const uint32_t* order = nullptr;
-	if (reorder && (rc = groupRays(s, p, rays_dev, n, st, &order))) return rc;
-	const bool cull = (p.view.flags & RTX_FLAG_BACKFACE_CULL) != 0;
+	if (int rc = beginRays(s, n, rays_dev, kTraceReorderMin, st, p, &order)) return rc;
+	const uint32_t waves = (n + 63) / 64;
+	const Variant v = variantOf(s);
 	if (showNormals(s)) {
 		p.workCounter = s->rayWork;
 		const uint32_t blocks = std::min<uint32_t>((uint32_t)s->blocksPass1, (waves + 3) / 4);
@@ -2313,9 +2259,9 @@ int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_
 	}
 	else {
 		if (hits_dev) {
-			const RayKernel k = rayHitKernel(s, cull);
-			int& perCU = s->rayHitBlocks[cull ? 1 : 0];
-			if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k, 256, 0)); perCU = std::max(perCU, 1); }
+			const RayKernel k = rayHitKernel(v);
+			int& perCU = s->rayHitBlocks[v.cull ? 1 : 0];
+			if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
 			p.workCounter = s->rayWork;
 			const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
 			hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, hits_dev);
@@ -2324,7 +2270,7 @@ int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_
 			// (the recursion frames of the pass-1 area hold blocksPass1 blocks)
 			p.workCounter = s->rayWork + 16;
 			const uint32_t blocks = std::min<uint32_t>((uint32_t)s->blocksPass1, (waves + 3) / 4);
-			hipLaunchKernelGGL(rayColourKernel(s, cull), dim3(blocks), dim3(256), 0, st, p, order, colours_dev);
+			hipLaunchKernelGGL(rayColourKernel(v), dim3(blocks), dim3(256), 0, st, p, order, colours_dev);
 		}
 	}
 	HIPCHK(hipGetLastError());
@@ -2339,22 +2285,15 @@ int rtx_occluded_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const flo
 	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
 	if (!occluded_dev) return fail(RTX_ERR_ARG, "rtx_occluded_rays: no output (occluded is NULL)");
 	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
-	int rc = ensureWork(s);
-	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
-	if ((rc = renderOn(s, st))) return rc;
-	const bool reorder = s->knobs.traceReorder < 0 ? n >= kOccludedReorderMin : s->knobs.traceReorder != 0;
-	if ((rc = ensureRayScratch(s, n, reorder, st))) return rc;
-	Params p = s->params;
-	p.probeRays = rays_dev; p.nProbe = n;
-	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork);
+	Params p;
 	const uint32_t* order = nullptr;
-	if (reorder && (rc = groupRays(s, p, rays_dev, n, st, &order))) return rc;
-	const bool cull = (p.view.flags & RTX_FLAG_BACKFACE_CULL) != 0;
+	if (int rc = beginRays(s, n, rays_dev, kOccludedReorderMin, st, p, &order)) return rc;
+	const Variant v = variantOf(s);
 	const bool sceneOrder = s->knobs.occludedSceneOrder != 0;
-	const OccludedKernel k = rayOccludedKernel(s, cull, sceneOrder);
-	int& perCU = s->rayOccludedBlocks[cull ? 1 : 0][sceneOrder ? 1 : 0];
-	if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k, 256, 0)); perCU = std::max(perCU, 1); }
+	const OccludedKernel k = rayOccludedKernel(v, sceneOrder);
+	int& perCU = s->rayOccludedBlocks[v.cull ? 1 : 0][sceneOrder ? 1 : 0];
+	if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
 	p.workCounter = s->rayWork;
 	const uint32_t waves = (n + 63) / 64;
 	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
@@ -2369,15 +2308,15 @@ int rtx_math_probe(int device, int op, uint32_t n, const float* x, const float* 
 	int cnt = 0;
 	if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(RTX_ERR_NO_DEVICE, "no HIP device visible");
 	HIPCHK(hipSetDevice(device));
-	DevBuf dx, dy, dout;
+	DevArray<float> dx, dy, dout;
 	const size_t bytes = (size_t)n * sizeof(float);
-	HIPCHK(hipMalloc(&dx.p, bytes)); HIPCHK(hipMalloc(&dy.p, bytes)); HIPCHK(hipMalloc(&dout.p, bytes));
-	HIPCHK(hipMemcpy(dx.p, x, bytes, hipMemcpyHostToDevice));
-	if (y) HIPCHK(hipMemcpy(dy.p, y, bytes, hipMemcpyHostToDevice));
-	else HIPCHK(hipMemset(dy.p, 0, bytes));
-	hipLaunchKernelGGL(rtxMathProbeKernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, n, (const float*)dx.p, (const float*)dy.p, (float*)dout.p);
+	HIPCHK(dx.reserve(n)); HIPCHK(dy.reserve(n)); HIPCHK(dout.reserve(n));
+	HIPCHK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
+	if (y) HIPCHK(hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice));
+	else HIPCHK(hipMemset(dy, 0, bytes));
+	hipLaunchKernelGGL(rtxMathProbeKernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, n, (const float*)dx, (const float*)dy, dout.get());
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
 
@@ -2387,14 +2326,14 @@ int rtx_vec_probe(int device, int op, uint32_t n, const float* a, const float* b
 	int cnt = 0;
 	if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(RTX_ERR_NO_DEVICE, "no HIP device visible");
 	HIPCHK(hipSetDevice(device));
-	DevBuf da, db, dout;
+	DevArray<float> da, db, dout;
 	const size_t bytes = (size_t)n * 3 * sizeof(float);
-	HIPCHK(hipMalloc(&da.p, bytes)); HIPCHK(hipMalloc(&dout.p, bytes));
-	HIPCHK(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
-	if (b) { HIPCHK(hipMalloc(&db.p, bytes)); HIPCHK(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice)); }
-	hipLaunchKernelGGL(rtxVecProbeKernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, n, (const float*)da.p, (const float*)db.p, ior, (float*)dout.p);
+	HIPCHK(da.reserve((size_t)n * 3)); HIPCHK(dout.reserve((size_t)n * 3));
+	HIPCHK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
+	if (b) { HIPCHK(db.reserve((size_t)n * 3)); HIPCHK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); }
+	hipLaunchKernelGGL(rtxVecProbeKernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, n, (const float*)da, (const float*)db, ior, dout.get());
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
 

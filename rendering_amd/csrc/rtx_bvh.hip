@@ -677,7 +677,7 @@ struct rtx_bvh {
 	uint32_t nNodes = 0, nRefs = 0, maxDepth = 0, launches = 0;
 	float buildMs = 0;
 	bool queued = false;         // built by the single persistent launch (bvhq) -- else level by level (bvhb)
-	void* slab = nullptr;        // bvhq: the five arrays below are one allocation
+	DevBag mem;                  // what backs the five arrays below: one allocation (bvhq) or five
 	float* bounds = nullptr; int32_t* skip = nullptr; int32_t* leafBegin = nullptr; int32_t* leafCount = nullptr; uint32_t* refs = nullptr;
 };
 
@@ -722,21 +722,18 @@ int buildQueued(const float* tri_pos_dev, uint32_t n_tris, const float* root_lo,
 	// (mode 2, tests: pools far too small -- the launches must notice, say so and leave the build to the level-by-level path)
 	const uint32_t nodeCap = (gBvhBuildMode == 2 ? 64u : std::max<uint32_t>(2 * n_tris, 1024)) + slack + 64;
 	const unsigned long long idCap = std::min<unsigned long long>(32ull * n_tris + (1ull << 20), (1ull << 32) - 64);      // (ids of ALL levels: 27 levels x 2.6 n at the headline; three arrays)
-	std::vector<void*> scratch;
-	struct Cleanup { std::vector<void*>& v; ~Cleanup() { for (void* p : v) (void)hipFree(p); } } cleanup{ scratch };
-	auto dalloc = [&](void** p, size_t bytes) -> hipError_t { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 256)); if (e == hipSuccess) scratch.push_back(*p); return e; };
+	DevArray<char> scratch;
 	float* dPos = nullptr; float* dExt = nullptr; QNode* dNodes = nullptr; uint32_t* dIds = nullptr; Ctl* dCtl = nullptr;
 	// (one allocation for everything transient: positions, extents, node pool, id pool, control block)
 	const size_t szPos = ((size_t)n_tris * 9 * 4 + 255) & ~(size_t)255, szExt = ((size_t)n_tris * 6 * 4 + 255) & ~(size_t)255;
 	const size_t szNodes = (size_t)nodeCap * sizeof(QNode), szIds = (size_t)idCap * 4, szCtl = 256;      // (szIds: each of the three pools)
-	char* base = nullptr;
-	if (dalloc((void**)&base, szPos + szExt + szNodes + 3 * szIds + szCtl) != hipSuccess) { (void)hipGetLastError(); return RTX_OK; }      // (not enough memory for the pools: level by level)
+	if (scratch.reserve(szPos + szExt + szNodes + 3 * szIds + szCtl) != hipSuccess) { (void)hipGetLastError(); return RTX_OK; }      // (not enough memory for the pools: level by level)
+	char* base = scratch;
 	dNodes = (QNode*)base; dIds = (uint32_t*)(base + szNodes); float* dLo = (float*)(base + szNodes + szIds); float* dHi = (float*)(base + szNodes + 2 * szIds);
 	dCtl = (Ctl*)(base + szNodes + 3 * szIds); dPos = (float*)(base + szNodes + 3 * szIds + szCtl); dExt = (float*)((char*)dPos + szPos);
 	hipStream_t st = nullptr;
-	hipEvent_t ev0, ev1;
-	HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
-	struct EvCleanup { hipEvent_t a, b; ~EvCleanup() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evCleanup{ ev0, ev1 };
+	Event ev0, ev1;
+	HIPCHK(ev0.create()); HIPCHK(ev1.create());
 	if (n_tris) HIPCHK(hipMemcpyAsync(dPos, tri_pos_dev, (size_t)n_tris * 9 * sizeof(float), hipMemcpyDeviceToDevice, st));
 	uint32_t launches = 0;
 	HIPCHK(hipEventRecord(ev0, st));
@@ -756,9 +753,10 @@ int buildQueued(const float* tri_pos_dev, uint32_t n_tris, const float* root_lo,
 	b->device = device; b->nNodes = ctl.nodes; b->nRefs = ctl.refs; b->queued = true;
 	const size_t nN = b->nNodes, nR = std::max<uint32_t>(b->nRefs, 1);
 	const size_t oSkip = (nN * 6 * 4 + 255) & ~(size_t)255, oLb = oSkip + ((nN * 4 + 255) & ~(size_t)255), oLc = oLb + ((nN * 4 + 255) & ~(size_t)255), oRefs = oLc + ((nN * 4 + 255) & ~(size_t)255);
-	if (hipMalloc(&b->slab, oRefs + nR * 4) != hipSuccess) { (void)hipGetLastError(); delete b; return fail(RTX_ERR_DEVICE, "out of device memory for the acceleration structure"); }
-	b->bounds = (float*)b->slab; b->skip = (int32_t*)((char*)b->slab + oSkip); b->leafBegin = (int32_t*)((char*)b->slab + oLb); b->leafCount = (int32_t*)((char*)b->slab + oLc);
-	b->refs = (uint32_t*)((char*)b->slab + oRefs);
+	char* slab = nullptr;
+	if (b->mem.alloc(&slab, oRefs + nR * 4) != hipSuccess) { (void)hipGetLastError(); delete b; return fail(RTX_ERR_DEVICE, "out of device memory for the acceleration structure"); }
+	b->bounds = (float*)slab; b->skip = (int32_t*)(slab + oSkip); b->leafBegin = (int32_t*)(slab + oLb); b->leafCount = (int32_t*)(slab + oLc);
+	b->refs = (uint32_t*)(slab + oRefs);
 	hipLaunchKernelGGL(finishKernel, dim3(gridFor(b->nNodes)), dim3(256), 0, st, (const QNode*)dNodes, b->nNodes, (const uint32_t*)dIds, dCtl, b->bounds, b->skip, b->leafBegin, b->leafCount, b->refs);
 	launches++;
 	uint32_t maxDepth = 0;
@@ -812,27 +810,23 @@ int rtxBvhBuildDevice(const float* tri_pos_dev, uint32_t n_tris, const float* ro
 
 	// bump arena over a few large slabs (one hipMalloc per ~27 levels x 8 buffers would dominate the wall time);
 	// everything in it is freed on every exit path
-	std::vector<void*> scratch;
-	struct Cleanup { std::vector<void*>& v; ~Cleanup() { for (void* p : v) (void)hipFree(p); } } cleanup{ scratch };
+	DevBag scratch;
 	char* slab = nullptr; size_t slabLeft = 0;
 	const size_t slabBytes = std::max<size_t>((size_t)32 << 20, (size_t)n_tris * 160);
 	auto dalloc = [&](void** p, size_t bytes) -> hipError_t {
 		bytes = (std::max<size_t>(bytes, 4) + 255) & ~(size_t)255;
 		if (bytes > slabLeft) {
 			const size_t sz = std::max(slabBytes, bytes);
-			void* q = nullptr;
-			hipError_t e = hipMalloc(&q, sz);
+			const hipError_t e = scratch.alloc(&slab, sz);
 			if (e != hipSuccess) return e;
-			scratch.push_back(q);
-			slab = (char*)q; slabLeft = sz;
+			slabLeft = sz;
 		}
 		*p = slab; slab += bytes; slabLeft -= bytes;
 		return hipSuccess;
 	};
 	hipStream_t st = nullptr;
-	hipEvent_t ev0, ev1;
-	HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
-	struct EvCleanup { hipEvent_t a, b; ~EvCleanup() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evCleanup{ ev0, ev1 };
+	Event ev0, ev1;
+	HIPCHK(ev0.create()); HIPCHK(ev1.create());
 
 	float* dPos = nullptr; float* dExt = nullptr;
 	HIPCHK(dalloc((void**)&dPos, (size_t)n_tris * 9 * sizeof(float)));
@@ -944,9 +938,9 @@ int rtxBvhBuildDevice(const float* tri_pos_dev, uint32_t n_tris, const float* ro
 	rtx_bvh* b = new rtx_bvh();
 	b->device = device; b->nNodes = root.subNodes; b->nRefs = root.subRefs; b->maxDepth = (uint32_t)levels.size();
 	auto bailOut = [&](int code) { rtx_bvh_destroy(b); return code; };
-	if (hipMalloc((void**)&b->bounds, (size_t)b->nNodes * 6 * sizeof(float)) != hipSuccess || hipMalloc((void**)&b->skip, (size_t)b->nNodes * 4) != hipSuccess ||
-	    hipMalloc((void**)&b->leafBegin, (size_t)b->nNodes * 4) != hipSuccess || hipMalloc((void**)&b->leafCount, (size_t)b->nNodes * 4) != hipSuccess ||
-	    hipMalloc((void**)&b->refs, (size_t)std::max<uint32_t>(b->nRefs, 1) * 4) != hipSuccess)
+	if (b->mem.alloc(&b->bounds, (size_t)b->nNodes * 6 * sizeof(float)) != hipSuccess || b->mem.alloc(&b->skip, (size_t)b->nNodes * 4) != hipSuccess ||
+	    b->mem.alloc(&b->leafBegin, (size_t)b->nNodes * 4) != hipSuccess || b->mem.alloc(&b->leafCount, (size_t)b->nNodes * 4) != hipSuccess ||
+	    b->mem.alloc(&b->refs, (size_t)std::max<uint32_t>(b->nRefs, 1) * 4) != hipSuccess)
 		return bailOut(fail(RTX_ERR_DEVICE, "out of device memory for the acceleration structure"));
 	for (size_t l = 0; l < levels.size(); l++) {
 		const BvhLevel& L = levels[l];
@@ -970,14 +964,12 @@ int rtx_bvh_build(const float* tri_pos, uint32_t n_tris, const float* root_lo, c
 	int rc = checkBuildArgs(tri_pos, n_tris, root_lo, root_hi, device, out);
 	if (rc) return rc;
 	// the host triangles in device memory once; the build reads them from there
-	float* dTris = nullptr;
+	DevArray<float> dTris;
 	if (n_tris) {
-		HIPCHK(hipMalloc((void**)&dTris, (size_t)n_tris * 9 * sizeof(float)));
-		if (hipMemcpy(dTris, tri_pos, (size_t)n_tris * 9 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dTris); return fail(RTX_ERR_DEVICE, "hipMemcpy (triangles)"); }
+		HIPCHK(dTris.reserve((size_t)n_tris * 9));
+		if (hipMemcpy(dTris, tri_pos, (size_t)n_tris * 9 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(RTX_ERR_DEVICE, "hipMemcpy (triangles)");
 	}
-	rc = rtxBvhBuildDevice(dTris, n_tris, root_lo, root_hi, ac_penalty, device, out);
-	if (dTris) (void)hipFree(dTris);
-	return rc;
+	return rtxBvhBuildDevice(dTris, n_tris, root_lo, root_hi, ac_penalty, device, out);
 }
 
 int rtx_bvh_build_mode(int mode) { if (mode < 0 || mode > 2) return fail(RTX_ERR_ARG, "rtx_bvh_build_mode: 0, 1 or 2"); gBvhBuildMode = mode; return RTX_OK; }
@@ -1015,12 +1007,6 @@ void rtx_bvh_destroy(rtx_bvh* b)
 {
 	if (!b) return;
 	(void)hipSetDevice(b->device);
-	if (b->slab) { (void)hipFree(b->slab); delete b; return; }
-	if (b->bounds) (void)hipFree(b->bounds);
-	if (b->skip) (void)hipFree(b->skip);
-	if (b->leafBegin) (void)hipFree(b->leafBegin);
-	if (b->leafCount) (void)hipFree(b->leafCount);
-	if (b->refs) (void)hipFree(b->refs);
 	delete b;
 }
 

@@ -50,7 +50,7 @@ int loadRccl()
 struct rtx_comm {
 	ncclComm_t comm = nullptr;
 	int nRanks = 1, rank = 0, device = 0;
-	int* flag = nullptr;      // one device word for rtx_comm_agree
+	DevArray<int> flag;       // one device word for rtx_comm_agree
 };
 
 extern "C" {
@@ -99,7 +99,7 @@ int rtx_comm_create(const void* id128, int n_ranks, int rank, int device, rtx_co
 	c->nRanks = n_ranks; c->rank = rank; c->device = device;
 	ncclResult_t r = gRccl.commInitRank(&c->comm, n_ranks, id, rank);
 	if (r != ncclSuccess) { delete c; return fail(RTX_ERR_DEVICE, std::string("ncclCommInitRank: ") + gRccl.errorString(r)); }
-	if (hipMalloc((void**)&c->flag, sizeof(int)) != hipSuccess) { (void)gRccl.commDestroy(c->comm); delete c; return fail(RTX_ERR_DEVICE, "hipMalloc"); }
+	if (c->flag.reserve(1) != hipSuccess) { (void)gRccl.commDestroy(c->comm); delete c; return fail(RTX_ERR_DEVICE, "hipMalloc"); }
 	*out = c;
 	return RTX_OK;
 }
@@ -108,7 +108,6 @@ void rtx_comm_destroy(rtx_comm* c)
 {
 	if (!c) return;
 	if (c->comm && gRccl.commDestroy) (void)gRccl.commDestroy(c->comm);
-	if (c->flag) (void)hipFree(c->flag);
 	delete c;
 }
 
@@ -132,7 +131,7 @@ int rtx_comm_agree(rtx_comm* c, int ok, int* all_ok, void* stream)
 	hipStream_t st = (hipStream_t)stream;
 	const int mine = ok ? 1 : 0;
 	HIPCHK(hipMemcpyAsync(c->flag, &mine, sizeof(int), hipMemcpyHostToDevice, st));
-	NCCLCHK(gRccl.allReduce(c->flag, c->flag, 1, ncclInt, ncclMin, c->comm, st));
+	NCCLCHK(gRccl.allReduce(c->flag.get(), c->flag.get(), 1, ncclInt, ncclMin, c->comm, st));
 	int all = 0;
 	HIPCHK(hipMemcpyAsync(&all, c->flag, sizeof(int), hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));

@@ -27,34 +27,19 @@ int editBegin(rtx_scene* s, void* stream)
 	return RTX_OK;
 }
 
-// The spheres' and planes' share of the derived state (rtx_scene_create's loops over the descriptions): the spheres' entry of the
-// cost estimate, the planes the estimate casts shadows on, and the longest plane normal a shadow ray's origin is offset along.
+// The spheres' and planes' share of the derived state, from the current descriptions (analyticEstimate, rtx_api.hip).
 int refreshAnalytic(rtx_scene* s)
 {
-	std::vector<float> sb;
-	s->estPlanes.clear();
-	s->srcNmax = 1.0f;
-	for (const rtx_object& o : s->objectDescs) {
-		if (o.type == RTX_OBJ_PLANE) {
-			s->estPlanes.push_back({ { o.pos[0], o.pos[1], o.pos[2], o.normal[0], o.normal[1], o.normal[2] } });
-			const double nl = std::sqrt((double)o.normal[0] * o.normal[0] + (double)o.normal[1] * o.normal[1] + (double)o.normal[2] * o.normal[2]);
-			if (!(nl <= 1e30)) s->srcNmax = INFINITY; else s->srcNmax = std::max(s->srcNmax, (float)(nl * 1.000001));
-		}
-		if (o.type != RTX_OBJ_SPHERE || !(o.radius2 > 0) || !std::isfinite(o.radius2)) continue;
-		const float r = std::sqrt(o.radius2), w = (o.material == 1 || o.material == 2) ? 4000.0f : 300.0f;
-		sb.insert(sb.end(), { o.pos[0] - r, o.pos[1] - r, o.pos[2] - r, o.pos[0] + r, o.pos[1] + r, o.pos[2] + r, w, 0.0f });
-	}
-	s->params.srcNmax2 = s->srcNmax * s->srcNmax * 1.00001f;
+	const std::vector<float> sb = analyticEstimate(s, s->objectDescs.data(), s->objectDescs.size());
 	// (the meshes' entries come first, one per mesh; the spheres' is the one after them when there is any)
-	void* dev = nullptr;
+	DevArray<float> dev;
 	if (!sb.empty()) {
-		HIPCHK(hipMalloc(&dev, sb.size() * sizeof(float)));
-		if (hipMemcpy(dev, sb.data(), sb.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dev); return fail(RTX_ERR_DEVICE, "hipMemcpy (sphere leaves)"); }
+		HIPCHK(dev.reserve(sb.size()));
+		if (hipMemcpy(dev, sb.data(), sb.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(RTX_ERR_DEVICE, "hipMemcpy (sphere leaves)");
 	}
 	s->meshLeaves.resize(s->meshRecs.size());
-	if (s->sphereLeafDev) (void)hipFree(s->sphereLeafDev);
-	s->sphereLeafDev = dev;
-	if (dev) s->meshLeaves.push_back({ (const float*)dev, (uint32_t)(sb.size() / 8) });
+	s->sphereLeafDev = std::move(dev);
+	if (s->sphereLeafDev) s->meshLeaves.push_back({ s->sphereLeafDev.get(), (uint32_t)(sb.size() / 8) });
 	return RTX_OK;
 }
 
@@ -64,10 +49,7 @@ int refreshAnalytic(rtx_scene* s)
 int refreshView(rtx_scene* s)
 {
 	s->srcCamBuilt = false; s->srcLightsBuilt = false;
-	for (auto& q : s->tileQueues) {
-		q.key.clear(); q.costValid = false; q.lastUse = 0;
-		q.frameMs[0] = q.frameMs[1] = -1.f; q.frameSamples[0] = q.frameSamples[1] = 0; q.framesSeen = 0; q.generation++; q.fusedGaveUp = false;
-	}
+	for (auto& q : s->tileQueues) { q.forget(); q.lastUse = 0; }
 	s->lastFrameQueue = ~(size_t)0;
 	s->viewSerial++;
 	s->lastFused.valid = false;
@@ -123,7 +105,7 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	// 1. the reference's builder on the device, from the caller's triangles
 	rtx_bvh* b = nullptr;
 	if ((rc = rtxBvhBuildDevice(tri_pos_dev, nt, root_lo, root_hi, ac_penalty, s->device, &b))) return rc;
-	struct Hold { rtx_bvh* b; ~Hold() { rtx_bvh_destroy(b); } } hold{ b };
+	const std::unique_ptr<rtx_bvh, void (*)(rtx_bvh*)> hold(b, rtx_bvh_destroy);
 	const double t1 = wallMs();
 
 	// 2. the flatten on the device (rtx_flatten.hip): node records, wide nodes, prune blocks and their copies, leaf references, leaf boxes
@@ -134,24 +116,10 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	rtx_scene::SrcMesh sm;
 	rtx_scene::MeshLeaves leaves{ nullptr, 0 };
 	float box[6];
-	std::vector<void*> owned;
-	struct Drop { std::vector<void*>& v; bool keep = false; ~Drop() { if (!keep) for (void* p : v) (void)hipFree(p); } } drop{ owned };
-	gUploadedBytes = 0;
+	DevBag owned;      // (dropped with everything in it unless the edit goes through)
 	if ((rc = deviceMeshGeometry(s, b, tri_pos_dev, nt, mesh, (uint32_t)s->srcLightPos.size(), owned, dm, sm, leaves, box))) return rc;
-	auto copyDev = [&](const float* src, size_t count, const float** out) -> int {
-		*out = nullptr;
-		if (!src || count == 0) return RTX_OK;
-		void* d = nullptr;
-		HIPCHK(hipMalloc(&d, count * sizeof(float)));
-		owned.push_back(d);
-		gUploadedBytes += count * sizeof(float);
-		HIPCHK(hipMemcpy(d, src, count * sizeof(float), hipMemcpyDeviceToDevice));
-		*out = (const float*)d;
-		return RTX_OK;
-	};
-	if ((rc = copyDev(tri_nrm_dev, (size_t)nt * 9, &dm.nrm))) return rc;
-	if ((rc = copyDev(old.tb ? tri_tb_dev : nullptr, (size_t)nt * 6, &dm.tb))) return rc;
-	const size_t bytes = gUploadedBytes;
+	HIPCHK(owned.copyFrom(tri_nrm_dev, (size_t)nt * 9, &dm.nrm));
+	HIPCHK(owned.copyFrom(old.tb ? tri_tb_dev : nullptr, (size_t)nt * 6, &dm.tb));
 	// the objects of this mesh with their derived fields; then everything is in place on the host and goes up in two copies
 	std::vector<Object> objs = s->objectRecs;
 	const std::vector<float> oldBounds(s->meshBounds.begin() + (size_t)mesh * 6, s->meshBounds.begin() + (size_t)mesh * 6 + 6);
@@ -166,11 +134,8 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 		(void)hipMemcpy((Object*)s->params.objects, s->objectRecs.data(), s->objectRecs.size() * sizeof(Object), hipMemcpyHostToDevice);
 		return fail(RTX_ERR_DEVICE, "rtx_scene_update_mesh: the records could not be uploaded");
 	}
-	drop.keep = true;
-	for (void* p : s->meshOwned[mesh]) (void)hipFree(p);
 	s->meshOwned[mesh].swap(owned);
-	s->sceneBytes = s->sceneBytes - s->meshBytes[mesh] + bytes;
-	s->meshBytes[mesh] = bytes;
+	owned.clear();      // (the old geometry)
 	s->meshRecs[mesh] = dm; s->objectRecs.swap(objs);
 	s->meshLeaves[mesh] = leaves; s->srcMeshes[mesh] = sm;
 	chooseBoxPrune(s);

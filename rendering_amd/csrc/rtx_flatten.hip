@@ -344,32 +344,21 @@ namespace {
 inline unsigned blocksFor(size_t n) { return n ? (unsigned)((n + 255) / 256) : 1u; }
 
 // uploadMeshGeometry (rtx_api.hip) on the device: the tree of `b` (device builder) and the triangles at pos_dev (n_tris x 9, device) of mesh mi.
-// Fills the same fields of dm, sm, leaves and the root box; every allocation that stays goes to `owned`, its bytes to gUploadedBytes.
-int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uint32_t nTris, uint32_t mi, uint32_t nLights, std::vector<void*>& owned,
+// Fills the same fields of dm, sm, leaves and the root box; every allocation that stays goes to `owned` (counted as scene data, but for the sources' scratch).
+int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uint32_t nTris, uint32_t mi, uint32_t nLights, DevBag& owned,
                        Mesh& dm, rtx_scene::SrcMesh& sm, rtx_scene::MeshLeaves& leaves, float bounds[6])
 {
 	using namespace rtxflat;
 	const uint32_t n = b->nNodes, nRefs = b->nRefs;
 	if (n == 0) return fail(RTX_ERR_DEVICE, "rtx_scene_update_mesh: the build left no nodes");
 	hipStream_t st = nullptr;
-	auto keep = [&](void** p, size_t bytes) -> int {
-		*p = nullptr;
-		HIPCHK(hipMalloc(p, std::max<size_t>(bytes, 4)));
-		owned.push_back(*p);
-		return RTX_OK;
-	};
 	// scratch: one allocation kept by the scene, grown when a tree needs more
 	const size_t scanTmp = n / 512 + 64;
 	const size_t szCtl = kCtlWords * 4, szU = ((size_t)n * 4 + 255) & ~(size_t)255;
 	const size_t szAgg = (size_t)n * sizeof(Agg), szBox = (size_t)n * 32, szTmp = scanTmp * 4;
 	const size_t need = szCtl + 7 * szU + szAgg + szBox + szTmp;
-	if (need > s->flatScratchBytes) {
-		if (s->flatScratch) (void)hipFree(s->flatScratch);
-		s->flatScratch = nullptr; s->flatScratchBytes = 0;
-		HIPCHK(hipMalloc(&s->flatScratch, need));
-		s->flatScratchBytes = need;
-	}
-	char* scratch = (char*)s->flatScratch;
+	HIPCHK(s->flatScratch.reserve(need));
+	char* scratch = s->flatScratch;
 	uint32_t* ctl = (uint32_t*)scratch;
 	uint32_t* parent = (uint32_t*)(scratch + szCtl);
 	uint32_t* depth = (uint32_t*)(scratch + szCtl + szU);
@@ -384,13 +373,12 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 	uint32_t launches = 0;
 
 	// node records, depths, the checks that decide whether a wide tree exists (flattenMesh: boxes regular, nested, not too deep for the stack)
-	const Node* nodes = nullptr;
+	Node* nodes = nullptr;
 	int rc;
-	if ((rc = keep((void**)&nodes, (size_t)n * sizeof(Node)))) return rc;
-	gUploadedBytes += (size_t)n * sizeof(Node);
+	HIPCHK(owned.alloc(&nodes, (size_t)n * sizeof(Node)));
 	HIPCHK(hipMemsetAsync(ctl, 0, szCtl, st));
 	HIPCHK(hipMemsetAsync(parent, 0xff, (size_t)n * 4, st));      // (kNone: a node no inner node names as its child)
-	hipLaunchKernelGGL(nodesKernel, dim3(blocksFor(n)), dim3(256), 0, st, b->bounds, b->skip, b->leafBegin, b->leafCount, n, (Node*)nodes, parent, ctl);
+	hipLaunchKernelGGL(nodesKernel, dim3(blocksFor(n)), dim3(256), 0, st, b->bounds, b->skip, b->leafBegin, b->leafCount, n, nodes, parent, ctl);
 	hipLaunchKernelGGL(depthKernel, dim3(blocksFor(n)), dim3(256), 0, st, nodes, (const uint32_t*)parent, n, depth, isRoot, ctl);
 	uint32_t c0[16];
 	HIPCHK(hipMemcpy(c0, ctl, sizeof(c0), hipMemcpyDeviceToHost));
@@ -403,13 +391,11 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 
 	// the wide tree
 	WideNode* wide = nullptr;
-	uint32_t* slotNode = nullptr;
+	DevArray<uint32_t> slotNode;      // (scratch: gone when this function returns)
 	if (nWide) {
-		if ((rc = keep((void**)&wide, (size_t)nWide * sizeof(WideNode)))) return rc;
-		gUploadedBytes += (size_t)nWide * sizeof(WideNode);
-		HIPCHK(hipMalloc((void**)&slotNode, (size_t)nWide * kWideSlots * 4));
+		HIPCHK(owned.alloc(&wide, (size_t)nWide * sizeof(WideNode)));
+		HIPCHK(slotNode.reserve((size_t)nWide * kWideSlots));
 	}
-	struct FreeSlots { uint32_t*& p; ~FreeSlots() { if (p) (void)hipFree(p); } } freeSlots{ slotNode };
 	if (nWide && !rootLeaf) {
 		HIPCHK(hipMemcpyAsync(rank, isRoot, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
 		if ((rc = scanExclusive(rank, n, tmp, st, launches))) return rc;
@@ -417,13 +403,13 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 		if ((rc = scanExclusive(count, nRoots, tmp, st, launches))) return rc;
 		hipLaunchKernelGGL(childIndexKernel, dim3(blocksFor(n)), dim3(256), 0, st, nodes, n, (const uint32_t*)isRoot, (const uint32_t*)rank, (const uint32_t*)count, wideOf);
 	}
-	if (nWide) hipLaunchKernelGGL(wideKernel, dim3(blocksFor(n)), dim3(256), 0, st, nodes, n, (const uint32_t*)isRoot, (const uint32_t*)wideOf, nWide, wide, slotNode);
+	if (nWide) hipLaunchKernelGGL(wideKernel, dim3(blocksFor(n)), dim3(256), 0, st, nodes, n, (const uint32_t*)isRoot, (const uint32_t*)wideOf, nWide, wide, slotNode.get());
 	dm.wide = wide; dm.nWide = nWide;
 
 	// leaf references, padded by one wave
 	RefA* ra = nullptr; RefB* rb = nullptr; RefC* rcr = nullptr;
 	const size_t nPad = (size_t)nRefs + 64;
-	if ((rc = keep((void**)&ra, nPad * sizeof(RefA))) || (rc = keep((void**)&rb, nPad * sizeof(RefB))) || (rc = keep((void**)&rcr, nPad * sizeof(RefC)))) return rc;
+	HIPCHK(owned.alloc(&ra, nPad * sizeof(RefA))); HIPCHK(owned.alloc(&rb, nPad * sizeof(RefB))); HIPCHK(owned.alloc(&rcr, nPad * sizeof(RefC)));
 	HIPCHK(hipMemsetAsync(ra, 0, nPad * sizeof(RefA), st)); HIPCHK(hipMemsetAsync(rb, 0, nPad * sizeof(RefB), st)); HIPCHK(hipMemsetAsync(rcr, 0, nPad * sizeof(RefC), st));
 	if (nRefs) hipLaunchKernelGGL(refsKernel, dim3(blocksFor(nRefs)), dim3(256), 0, st, (const uint32_t*)b->refs, nRefs, pos_dev, ra, rb, rcr);
 
@@ -451,8 +437,7 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 	const uint32_t nLeafBoxes = c1[4];
 	float* lb = nullptr;
 	if (nLeafBoxes) {
-		if ((rc = keep((void**)&lb, (size_t)nLeafBoxes * 32))) return rc;
-		gUploadedBytes += (size_t)nLeafBoxes * 32;
+		HIPCHK(owned.alloc(&lb, (size_t)nLeafBoxes * 32));
 		hipLaunchKernelGGL(leafCompactKernel, dim3(blocksFor(n)), dim3(256), 0, st, (const float*)box8, (const uint32_t*)flag, (const uint32_t*)at, n, lb, ctl);
 	}
 	leaves = { lb, nLeafBoxes };
@@ -466,30 +451,25 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 	// prune blocks: copy 0, then the source copies (equal to copy 0 until buildSources patches their P); the slots' reference ranges
 	sm = rtx_scene::SrcMesh();
 	dm.prune = nullptr;
-	uint32_t* slotRange = nullptr;
+	DevArray<uint32_t> slotRange;      // (scratch: copied where the source copies are used)
 	if (pruneOn) {
 		const uint32_t nCopies = s->knobs.sources ? 2u + std::min<uint32_t>(nLights, kMaxSrcLights) : 1u;
 		PruneBlock* pb = nullptr;
-		if ((rc = keep((void**)&pb, (size_t)nCopies * nWide * sizeof(PruneBlock)))) return rc;
-		gUploadedBytes += (size_t)nCopies * nWide * sizeof(PruneBlock);
-		HIPCHK(hipMalloc((void**)&slotRange, (size_t)nWide * kWideSlots * 2 * 4));
-		hipLaunchKernelGGL(pruneKernel, dim3(blocksFor((size_t)nWide * kWideSlots)), dim3(256), 0, st, (const uint32_t*)slotNode, nWide, (const Agg*)agg, pb, slotRange);
+		HIPCHK(owned.alloc(&pb, (size_t)nCopies * nWide * sizeof(PruneBlock)));
+		HIPCHK(slotRange.reserve((size_t)nWide * kWideSlots * 2));
+		hipLaunchKernelGGL(pruneKernel, dim3(blocksFor((size_t)nWide * kWideSlots)), dim3(256), 0, st, (const uint32_t*)slotNode, nWide, (const Agg*)agg, pb, slotRange.get());
 		for (uint32_t c = 1; c < nCopies; c++) HIPCHK(hipMemcpyAsync(pb + (size_t)c * nWide, pb, (size_t)nWide * sizeof(PruneBlock), hipMemcpyDeviceToDevice, st));
 		dm.prune = pb;
 		if (nCopies > 1) { sm.base = pb; sm.nWide = nWide; }
 	}
-	struct FreeRange { uint32_t*& p; bool kept = false; ~FreeRange() { if (p && !kept) (void)hipFree(p); } } freeRange{ slotRange };
 	dm.vmax = vmaxMesh;
 	dm.rootRec = rootRec;
 	if (!(vmaxMesh < 0x1p40f)) { dm.prune = nullptr; dm.rootRec.h[0] = dm.rootRec.h[1] = dm.rootRec.h[2] = INFINITY; }      // (huge or non-finite coordinates: nothing is pruned)
 	dm.nodes = nodes; dm.refA = ra; dm.refB = rb; dm.refC = rcr;
-	gUploadedBytes += nPad * (sizeof(RefA) + sizeof(RefB) + sizeof(RefC));
 	if (sm.base && vmaxMesh < 0x1p40f && nRefs) {
 		sm.nRefs = nRefs; sm.refA = ra; sm.refB = rb; sm.refC = rcr; sm.vmax = vmaxMesh; sm.meshIndex = mi;
-		owned.push_back(slotRange); freeRange.kept = true;
-		gUploadedBytes += (size_t)nWide * kWideSlots * 2 * 4;
-		sm.slotRange = slotRange;
-		if ((rc = keep((void**)&sm.refP, ((size_t)nRefs + nRefs / 64 + 2) * sizeof(float)))) return rc;
+		HIPCHK(owned.copyFrom(slotRange.get(), (size_t)nWide * kWideSlots * 2, &sm.slotRange));
+		HIPCHK(owned.alloc(&sm.refP, ((size_t)nRefs + nRefs / 64 + 2) * sizeof(float), false));
 		sm.blockP = sm.refP + nRefs;
 	}
 	else sm.base = nullptr;
@@ -509,7 +489,7 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 		dm.radius = (float)std::sqrt(rad);
 		if (!std::isfinite(dm.radius)) { dm.radius = 0; dm.fatRadius = INFINITY; }
 	}
-	// (everything queued above has finished before the scratch goes: hipFree waits for the device)
+	// (everything queued above has finished before the scratch goes)
 	HIPCHK(hipStreamSynchronize(st));
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
