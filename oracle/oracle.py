@@ -110,12 +110,13 @@ class OracleScene:
         lib().orc_set_flag(self.h, b"collectStatistics", 0)
         return r, out
 
-    def probe(self, rays):
+    def probe(self, rays, colours=True):
+        """(hit records n x 8, colours n x 3); colours=False skips the shading and returns None for them."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = rays.shape[0]
         out = np.zeros((n, 8), np.float32)
-        col = np.zeros((n, 3), np.float32)
-        lib().orc_probe(self.h, n, _p(rays), _p(out), _p(col))
+        col = np.zeros((n, 3), np.float32) if colours else None
+        lib().orc_probe(self.h, n, _p(rays), _p(out), _p(col) if colours else None)
         return out, col
 
     def skybox(self, d):

@@ -284,6 +284,7 @@ struct orc_scene {
 	std::string imageName = "out";
 	// options:: flags that matter on the hot path (options.h:23-37)
 	bool useBackfaceCulling = true, useSkybox = false, useTextures = true, collectStatistics = false;
+	bool showNormals = false;                      // the normals debug view (scene.cpp:771-772)
 	// camera (scene.h:52-66)
 	V3 camPos, camRot;
 	float fov = 60.0f;
@@ -665,8 +666,9 @@ void loadScene(orc_scene& sc, const std::string& path)
 			else if (k == "collectStatistics") sc.collectStatistics = parseNum<bool>(val);
 			else if (k == "useSkybox") sc.useSkybox = parseNum<bool>(val);
 			else if (k == "useTextures") sc.useTextures = parseNum<bool>(val);
+			else if (k == "showNormals") sc.showNormals = parseNum<bool>(val);
 			else if (k == "outputProgress" || k == "enableOutput" || k == "imageOutput" || k == "useAC" ||
-				k == "showAC" || k == "showNormals") (void)parseNum<bool>(val);   // not on the measured path
+				k == "showAC") (void)parseNum<bool>(val);   // not on the measured path
 			else if (k == "width") sc.width = parseNum<int>(val);
 			else if (k == "height") sc.height = parseNum<int>(val);
 			else if (k == "fov") sc.fov = parseNum<float>(val);
@@ -978,6 +980,7 @@ V3 castRay(const orc_scene& sc, const Ray& ray, int depth)          // scene.cpp
 	V2 tex; V3 N, hitColor;
 	V3 P = ray.o + ray.d * h.t;
 	surfaceData(o, P, h.tri, h.uv, N, tex);
+	if (sc.showNormals) return N / 2.0f + v3(0.5f, 0.5f, 0.5f);           // scene.cpp:771-772
 	if (o.type == OBJ_MESH && o.hasDiffuse)                            // objects.cpp:153-163
 		objColor = o.diffuseMap[(size_t)texel(o.dH, tex.y) * o.dW + texel(o.dW, tex.x)];
 	V3 diff, spec;
@@ -1300,6 +1303,7 @@ void orc_set_flag(orc_scene* s, const char* name, int v)
 {
 	if (!strcmp(name, "useBackfaceCulling")) s->useBackfaceCulling = v;
 	else if (!strcmp(name, "collectStatistics")) s->collectStatistics = v;
+	else if (!strcmp(name, "showNormals")) s->showNormals = v;
 }
 void orc_camera(orc_scene* s, float* scale, float* aspect, float* m16, float* pos3)
 {
@@ -1329,6 +1333,7 @@ void orc_probe(orc_scene* s, int n, const float* rays, float* out, float* colour
 		o[0] = hit ? 1.f : 0.f; o[1] = hit ? (float)h.obj : -1.f;
 		o[2] = (hit && s->objects[h.obj]->type == OBJ_MESH) ? (float)h.tri : -1.f;
 		o[3] = h.t; o[4] = h.uv.x; o[5] = h.uv.y; o[6] = 0; o[7] = 0;
+		if (!colour) continue;                       // (records only: an occlusion reference needs no shading)
 		V3 c = castRay(*s, r, 0);
 		colour[i * 3] = c.x; colour[i * 3 + 1] = c.y; colour[i * 3 + 2] = c.z;
 	}

@@ -10,6 +10,7 @@ import pytest
 
 from tests import ac_heatmap as A
 from tests.util_rays import probe_rays
+from tests.util_ulp import NORMAL_MAP_ULP, bits, ulp_diff
 from tools.make_golden_debug_views import HEATMAP, NORMALS, key, load
 
 pytestmark = pytest.mark.gpu
@@ -28,20 +29,7 @@ def gold():
     return g
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-# The reference normalises a normal-map texel IN PLACE at every sample (objects.cpp:148): a 1-ulp random walk whose state depends on
-# how often (and in which thread order) the texel was sampled before -- three pass 1s in one reference process differ from each other
-# in ~500 of cfg4's 19 200 pixels, by up to 32 ulp.  The device normalises the texel as loaded.  So where a normal map
-# shows, the view is pinned to within that walk; every other scene bit for bit.
-NORMAL_MAP_ULP = 64
-
-
-def ulp_diff(got, want):
-    a = bits(got).view(np.int32).astype(np.int64); b = bits(want).view(np.int32).astype(np.int64)
-    return np.abs(a - b).max(-1) if a.ndim > 1 else np.abs(a - b)
+# NORMAL_MAP_ULP: where a normal map shows, the view is pinned to within the reference's own walk (tests/util_ulp.py); every other scene bit for bit.
 
 
 def border_masked_diff(got, want, ulp=0):

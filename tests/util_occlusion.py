@@ -34,7 +34,7 @@ def opaque_probe(oracle, path, tmp_path, rays, culling=None, size=64):
     o = oracle.OracleScene(p, size, size)
     if culling is not None:
         oracle.lib().orc_set_flag(o.h, b"useBackfaceCulling", int(culling))
-    h, _ = o.probe(rays)
+    h, _ = o.probe(rays, colours=False)
     o.close()
     return h[:, 0] > 0, h[:, 3].astype(np.float32)
 
