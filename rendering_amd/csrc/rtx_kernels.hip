@@ -1780,6 +1780,112 @@ __device__ __forceinline__ V3 castRayWave(const Params& P0, bool valid, V3 o, V3
 	return PLAIN ? s.diff : s.col;      // (PLAIN: ST_RETURN is reached once, at depth 0, and the colour is kept in diff, which is parked with the rest: see advance)
 }
 
+// (castRayPlainWave parks P, N, objColor, diff, I and max(0, N . -L): sixteen floats per lane)
+constexpr int kParkFieldsPlainWave = 16;
+__device__ __forceinline__ float (*parkAreaPlainWave())[256]
+{
+	__shared__ float area[kParkFieldsPlainWave][256];
+	return area;
+}
+static_assert(RTX_WAVES_PLAIN < 6 || sizeof(leafBatch) + sizeof(wideStack) + sizeof(pruneUni) + kParkFieldsPlainWave * 1024 <= 27136,
+              "the PLAIN pass-1 kernel's LDS no longer fits six blocks per CU");
+
+// castRay for a wave of a PLAIN scene: every object Diffuse, every light a point or a distant light (rtx_scene_create checks; nothing can change either afterwards).
+// There the state machine above has no divergence to manage -- every valid lane casts its primary ray in round 0, every lane that hit something then visits lights
+// 0, 1, ... in the same rounds, a lane that missed has its sky colour, and nothing ever pushes a recursion frame -- so the rounds are written out: the primary
+// trace, then a loop over the lights on a SCALAR index.  The same float operations in the same order as advance() / consume() (scene.cpp:758-809); what changes is
+// which register holds a value and whether it is a vector or a scalar one: no state, depth, light index, material or request fields per lane, no selects between a
+// primary and a shadow request, and a primary walk whose set-up is compiled for shadow = false, one origin and tmax = FLT_MAX.
+// Parked around the primary trace: rd (and ro, when the rays do not start at the camera).  Around a shadow trace: P, N, objColor, diff, I and
+// m = max(0, N . -L) -- the only thing the accumulate needs of L.  A round in which no lane has a ray that can influence its pixel is not traced at all.
+// Used by the PLAIN pass-1 kernel and the PLAIN colour kernel of rtx_trace_rays.  The PLAIN SSAA and one-launch frame kernels keep castRayWave<.., PLAIN = true>: with the
+// second instance of the walk the SSAA launch was 2-4 % and the frame kernel 1.6 % slower (four waves per SIMD; profiles/plain_rounds_ab.txt).
+template <bool STATS, bool FEWRAYS = false, bool BOXES = true, bool CAM = true, int CULLK = -1>
+__device__ __forceinline__ V3 castRayPlainWave(const Params& P0, bool valid, V3 o, V3 d, uint32_t gl, Counts& cnt)
+{
+	static_assert(!STATS, "the instrumented kernels count moot rays and rounds: they keep the state machine (castRayWave)");
+	const uint32_t t = threadIdx.x;
+	float (*parked)[256] = parkAreaPlainWave();
+	Lane s;
+	s.diff = mk(0, 0, 0);      // (the value returned by a lane that is not valid)
+	if (freshParams(P0).view.maxDepth < 0) {                                                                   // scene.cpp:760
+		if (valid) s.diff = skyColor(freshParams(P0), d);
+		return s.diff;
+	}
+	// ---- the primary ray
+	Hit h;
+	parked[0][t] = d.x; parked[1][t] = d.y; parked[2][t] = d.z;
+	if (!CAM) { parked[3][t] = o.x; parked[4][t] = o.y; parked[5][t] = o.z; }
+	asm volatile("" ::: "memory");
+	traceWave<STATS, true, FEWRAYS, BOXES, CULLK>(freshParams(P0), valid, false, o, d, kFltMax, h, cnt, CAM ? 1u : 0u);
+	asm volatile("" ::: "memory");
+	const bool hit = h.obj >= 0;      // (a lane that is not valid took no part: no object)
+	{
+		const Params& P = freshParams(P0);
+		s.rd = mk(parked[0][t], parked[1][t], parked[2][t]);
+		// (CAM: the origin is view.camPos bit for bit -- primaryRay -- read again instead of kept across the walk)
+		s.ro = CAM ? mk(P.view.camPos[0], P.view.camPos[1], P.view.camPos[2]) : mk(parked[3][t], parked[4][t], parked[5][t]);
+		if (valid && !hit) s.diff = skyColor(P, s.rd);                                                        // scene.cpp:945
+		if (ballot(hit) == 0) return s.diff;
+		s.P = s.N = s.objColor = mk(0, 0, 0);
+		if (hit) shadePrimary(P, s, h);      // (diff = 0)
+	}
+	// ---- the lights, in order: Diffuse, scene.cpp:780-809
+	for (uint32_t li = 0; li < uni(freshParams(P0).nLights); li = uni(li + 1)) {
+		V3 I; float m;
+		{
+			const Params& P = freshParams(P0);
+			const u32x16 w = sload16(P.lights + li);
+			const int lt = (int)w[0];
+			const V3 lcolor = mk(F(w[1]), F(w[2]), F(w[3])); const float lint = F(w[4]);
+			V3 L; float dist;
+			if (lt == 1) {                 // DistantLight::illuminate, lights.cpp:18-23
+				L = mk(F(w[5]), F(w[6]), F(w[7]));
+				I = lcolor * lint;
+				dist = kFltMax;
+			}
+			else {                         // PointLight::illuminate, lights.cpp:32-38  (light types are 1 .. 3, and a PLAIN scene has no area light)
+				const V3 lp = mk(F(w[8]), F(w[9]), F(w[10]));
+				const V3 Lv = s.P - lp;
+				I = lcolor * attenuation(lint, len2(Lv));
+				L = normalized(Lv);
+				dist = length(s.P - lp);
+			}
+			const V3 nL = -L;
+			// the only use of the shadow ray is  vis * max(0, N . -L)  with vis in {0, 1}: when the max is +0 (surface turned away from the light, or NaN)
+			// the product is the same +0 for either answer -- the ray cannot influence the pixel ("moot") and is not walked
+			m = fmaxRef(0.f, dot(s.N, nL));
+			const bool active = hit && !(m == 0.f);
+			h.obj = -1;
+			if (ballot(active) != 0) {
+				// (a light's source copy was derived for shadow-ray origins within srcNmax |bias| of the surface: a shading normal longer than the host
+				// looked at, or NaN, falls back to copy 0 instead of pruning with too small a sigma)
+				const uint32_t src = (lt == 2 && li < P.nSrcLights && len2(s.N) <= P.srcNmax2) ? 2u + li : 0u;
+				const V3 so = s.P + s.N * P.view.bias;      // Ray{P + N*bias, -L, ShadowRay} (scene.cpp:787)
+				parked[0][t] = s.P.x; parked[1][t] = s.P.y; parked[2][t] = s.P.z;
+				parked[3][t] = s.N.x; parked[4][t] = s.N.y; parked[5][t] = s.N.z;
+				parked[6][t] = s.objColor.x; parked[7][t] = s.objColor.y; parked[8][t] = s.objColor.z;
+				parked[9][t] = s.diff.x; parked[10][t] = s.diff.y; parked[11][t] = s.diff.z;
+				parked[12][t] = I.x; parked[13][t] = I.y; parked[14][t] = I.z;
+				parked[15][t] = m;
+				asm volatile("" ::: "memory");
+				traceWave<STATS, true, FEWRAYS, BOXES, CULLK>(freshParams(P0), active, true, so, nL, dist, h, cnt, src);
+				asm volatile("" ::: "memory");
+				s.P = mk(parked[0][t], parked[1][t], parked[2][t]);
+				s.N = mk(parked[3][t], parked[4][t], parked[5][t]);
+				s.objColor = mk(parked[6][t], parked[7][t], parked[8][t]);
+				s.diff = mk(parked[9][t], parked[10][t], parked[11][t]);
+				I = mk(parked[12][t], parked[13][t], parked[14][t]);
+				m = parked[15][t];
+			}
+		}
+		const float vis = (h.obj < 0) ? 1.0f : 0.0f;       // bool vis = !trace(...)
+		const float c = vis * m;
+		if (hit) s.diff = s.diff + I * c;                                                                       // scene.cpp:788
+	}
+	return hit ? s.objColor * s.diff : s.diff;                                                                  // scene.cpp:808
+}
+
 // Row ownership for the pixel-sharded multi-GPU path (bands of bandH rows dealt round-robin to nParts devices).
 __device__ __forceinline__ bool rowOwned(uint32_t bandH, uint32_t nParts, uint32_t part, uint32_t y)
 {
@@ -1884,7 +1990,9 @@ __global__ void __launch_bounds__(256, MESH ? (PLAIN ? RTX_WAVES_PLAIN : RTX_WAV
 			else
 			if (sload1(Pa.tileCost + ty * Pa.tilesXFull + tx) > RTX_PRIO_TICKS) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
 			const unsigned long long t0 = wall_clock64();
-			const V3 c = castRayWave<STATS, MESH, false, BOXES, true, CULLK, PLAIN>(Pa, valid, o, d, gl, cnt);
+			V3 c;
+			if constexpr (PLAIN) c = castRayPlainWave<STATS, false, BOXES, true, CULLK>(Pa, valid, o, d, gl, cnt);
+			else c = castRayWave<STATS, MESH, false, BOXES, true, CULLK, PLAIN>(Pa, valid, o, d, gl, cnt);
 			const unsigned long long dt = wall_clock64() - t0;
 			RTX_TRACE_ONLY(dbgEnd = t0 + dt; dbgBusy += dt;)
 			uint32_t tileWas = tile;

@@ -261,7 +261,9 @@ __global__ void __launch_bounds__(256, MESH ? (PLAIN ? RTX_WAVES_PLAIN : RTX_WAV
 		const bool valid = k < P.nProbe;
 		uint32_t i; V3 o, d;
 		loadRay(P, order, k, valid, i, o, d);
-		const V3 c = castRayWave<false, MESH, false, BOXES, false, CULLK, PLAIN>(P, valid, o, d, gl, cnt);
+		V3 c;
+		if constexpr (PLAIN) c = castRayPlainWave<false, false, BOXES, false, CULLK>(P, valid, o, d, gl, cnt);
+		else c = castRayWave<false, MESH, false, BOXES, false, CULLK, PLAIN>(P, valid, o, d, gl, cnt);
 		if (valid) { float* pc = colours + (size_t)i * 3; pc[0] = c.x; pc[1] = c.y; pc[2] = c.z; }
 	}
 }
