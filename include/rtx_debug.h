@@ -104,6 +104,16 @@ int rtx_scene_mesh_read(rtx_scene* scene, uint32_t mesh, uint32_t* counts2, floa
                         int32_t* leaf_count, uint32_t* refs);
 int rtx_scene_mesh_flat_read(rtx_scene* scene, uint32_t mesh, uint32_t* n_wide, void* wide_out, void* prune_out, uint32_t cap_wide, float* root_rec8);
 int rtx_scene_edit_times(rtx_scene* scene, float* ms4);
+/* rtx_scene_lights_read: the light records as the device holds them, in the rtx_light layout with points = NULL -- the sample points of the
+ * area lights follow one another in points_out, in light order, 3 n_points floats each.  *n_lights / *n_point_floats: what there is;
+ * lights_out / points_out (either may be NULL) are written up to cap_lights records / when all the points fit cap_point_floats.
+ * rtx_scene_mesh_prune_copy_read: copy `copy` of mesh `mesh`'s prune blocks (0 the one any ray uses, 1 the camera's, 2 + l point light
+ * l's; rtx_mesh_flatten_probe's prune layout, up to cap_wide records); *n_copies = the copies the mesh holds (0: no prune blocks), with
+ * prune_out == NULL only the counts.  Both synchronise the device. */
+int rtx_scene_lights_read(rtx_scene* scene, uint32_t* n_lights, rtx_light* lights_out, uint32_t cap_lights, size_t* n_point_floats,
+                          float* points_out, size_t cap_point_floats);
+int rtx_scene_mesh_prune_copy_read(rtx_scene* scene, uint32_t mesh, uint32_t copy, uint32_t* n_copies, uint32_t* n_wide, void* prune_out,
+                                   uint32_t cap_wide);
 
 /* Device allocations this library holds at the moment, in this process, and their bytes: everything behind scenes, acceleration structures and
  * communicators, scratch of calls in progress included (not the caller's own buffers).  Back where it was once everything created since has been

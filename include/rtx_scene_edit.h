@@ -1,8 +1,9 @@
-/* Editing a live scene: objects of a scene created by rtx_scene_create move between frames.  An extension of the C ABI
+/* Editing a live scene: objects of a scene created by rtx_scene_create move between frames and its lights change
+ * (DESIGN.md 3.9).  An extension of the C ABI
  * in rtx.h -- the reference has no edit API; moving an object there means editing its [object] block and loading the file again, and a
  * scene edited here renders, bit for bit, what a scene created from the edited description renders.
  *
- * Ordering: both calls may synchronise with the device.  They wait for everything queued on the scene (every stream a render call was
+ * Ordering: every call here may synchronise with the device.  They wait for everything queued on the scene (every stream a render call was
  * made on, and `stream`, where the caller produced the triangles); renders queued before an edit see the old scene, renders queued
  * after it the new one, and the caller's buffers may be reused once the call returns.  Row ownership, counters and the frame mode stay
  * as they are.  A refused argument (RTX_ERR_ARG) leaves the scene as it was; after RTX_ERR_DEVICE an edit may be partly applied, and the
@@ -27,6 +28,15 @@ int rtx_scene_set_object(rtx_scene* scene, uint32_t index, const rtx_object* obj
 int rtx_scene_update_mesh(rtx_scene* scene, uint32_t mesh, const float* tri_pos_dev, const float* tri_nrm_dev,
                           const float* tri_tb_dev, const float root_lo[3], const float root_hi[3], int32_t ac_penalty,
                           void* stream);
+
+/* Replace the scene's lights by the n_lights records of `lights` (host memory, copied during the call, like the lights of
+ * rtx_scene_create's description; n_lights == 0 is legal).  One call covers a light moved, recoloured, dimmed, of another type or
+ * another number of sample points at its index, added or removed.  Refused (RTX_ERR_ARG): NULL lights with n_lights > 0, a type that
+ * is no RTX_LIGHT_*, an area light with points == NULL or n_points == 0.  Afterwards the device holds what rtx_scene_create would
+ * have uploaded and prepared for the same description with these lights: the records and sample points (the old ones are freed;
+ * rtx_scene_bytes reports a fresh scene's number), the source copies of every mesh's prune records -- laid out again when
+ * min(n_lights, 6) changes --, the kernel family (RTX_VARIANT_PLAIN holds while no light is an area light), the cost estimate. */
+int rtx_scene_set_lights(rtx_scene* scene, uint32_t n_lights, const rtx_light* lights);
 
 #ifdef __cplusplus
 }

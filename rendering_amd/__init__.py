@@ -40,10 +40,11 @@ RTX_SYMBOLS = [
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
     "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read", "rtx_live_device_memory",
+    "rtx_scene_lights_read", "rtx_scene_mesh_prune_copy_read",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
-RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh"]
+RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh", "rtx_scene_set_lights"]
 
 # the extension of include/rtx_query.h: queries on a loaded scene that render nothing (not part of the drop-in boundary)
 RTX_QUERY_SYMBOLS = ["rtx_occluded_rays"]
@@ -150,6 +151,13 @@ def load():
     rtx.rtx_kernel_variant.argtypes = [vp, C.POINTER(C.c_uint32)]
     rtx.rtx_ssaa_list_read.argtypes = [vp, vp, vp, C.c_size_t]
     rtx.rtx_live_device_memory.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    rtx.rtx_scene_set_lights.argtypes = [vp, C.c_uint32, vp]
+    rtx.rtx_scene_lights_read.argtypes = [vp, C.POINTER(C.c_uint32), vp, C.c_uint32, C.POINTER(C.c_size_t), vp, C.c_size_t]
+    rtx.rtx_scene_mesh_prune_copy_read.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.c_uint32]
+    host.rah_light_type.argtypes = [vp, i32]
+    host.rah_light_set.argtypes = [vp, i32] + [vp] * 8
+    host.rah_light_add.argtypes = [vp, i32] + [vp] * 8
+    host.rah_light_remove.argtypes = [vp, i32]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -295,6 +303,19 @@ class Comm:
         if self.h:
             self.rtx.rtx_comm_destroy(self.h)
             self.h = C.c_void_p()
+
+
+class RtxLight(C.Structure):
+    """rtx_light (include/rtx.h)"""
+    _fields_ = [("type", C.c_int32), ("color", C.c_float * 3), ("intensity", C.c_float), ("dir", C.c_float * 3), ("pos", C.c_float * 3),
+                ("n_points", C.c_uint32), ("points", C.c_void_p)]
+
+
+# the keys of a [light] block per type, in rah_light_set's argument order, and the values each takes
+LIGHT_TYPES = {"distant": 1, "point": 2, "area": 3}
+LIGHT_KEYS = {"distant": ("direction", "color", "intensity"), "point": ("position", "color", "intensity"),
+              "area": ("pos", "i", "j", "samples", "color", "intensity")}
+_LIGHT_ARGS = ("color", "intensity", "direction", "position", "pos", "i", "j", "samples")
 
 
 class _RtxMesh(C.Structure):
@@ -479,6 +500,62 @@ class Scene:
         ptr = lambda k: _np_ptr(arrs[k]) if k in arrs else None
         if self.host.rah_object_move(self.h, index, ptr("pos"), ptr("rot"), ptr("size"), ptr("radius"), ptr("normal")) != 0:
             raise RtxError("move_object: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    def light_type(self, index):
+        """"distant", "point" or "area": the type of light `index` (scene-file order)."""
+        if not 0 <= index < self.n_lights:
+            raise ValueError("light_type: light index %d out of range (%d lights)" % (index, self.n_lights))
+        return {v: k for k, v in LIGHT_TYPES.items()}[self.host.rah_light_type(self.h, index)]
+
+    @staticmethod
+    def _light_args(who, kind, keys):
+        """The arguments of rah_light_set / rah_light_add for `keys` of a light of type `kind` (ValueError: a key the type does not have, a
+        wrong number of values); the arrays are returned with them to keep them alive."""
+        bad = [k for k in keys if k not in LIGHT_KEYS[kind]]
+        if bad:
+            raise ValueError("%s: a %s light has no key %s (it takes %s)" % (who, kind, ", ".join(bad), ", ".join(LIGHT_KEYS[kind])))
+        arrs = {}
+        for k, v in keys.items():
+            want = 1 if k in ("intensity", "samples") else 3
+            a = np.ascontiguousarray(np.asarray(v, np.int32 if k == "samples" else np.float32).reshape(-1))
+            if a.size != want:
+                raise ValueError("%s: %s takes %d value%s, got %d" % (who, k, want, "" if want == 1 else "s", a.size))
+            if k == "samples" and a[0] != np.asarray(v).reshape(-1)[0]:
+                raise ValueError("%s: samples must be a whole number, got %r" % (who, v))
+            arrs[k] = a
+        return [_np_ptr(arrs[k]) if k in arrs else None for k in _LIGHT_ARGS], arrs
+
+    def set_light(self, index, **keys):
+        """Light `index` (scene-file order) as its [light] block would load with these keys set; a key not given keeps its value.  A point
+        light takes position / color / intensity, a distant light direction / color / intensity, an area light pos / i / j / samples /
+        color / intensity (its sample points are made again when pos, i, j or samples change); any other key, a wrong number of values or
+        a bad index raises ValueError and nothing changes.  With a live GPU scene the device's lights are replaced (rtx_scene_set_lights):
+        renders queued before the call see the old lights, later ones the new."""
+        if not 0 <= index < self.n_lights:
+            raise ValueError("set_light: light index %d out of range (%d lights)" % (index, self.n_lights))
+        args, _keep = self._light_args("set_light", self.light_type(index), keys)
+        if self.host.rah_light_set(self.h, index, *args) != 0:
+            raise RtxError("set_light: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    def add_light(self, type, **keys):
+        """A new light of `type` ("point", "distant", "area") after the last one, as a new [light] block with these keys would load (absent
+        keys: the loader's defaults); returns its index.  Keys and errors as for set_light."""
+        if type not in LIGHT_TYPES:
+            raise ValueError("add_light: unknown light type %r (point, distant, area)" % (type,))
+        args, _keep = self._light_args("add_light", type, keys)
+        index = self.host.rah_light_add(self.h, LIGHT_TYPES[type], *args)
+        if index < 0:
+            raise RtxError("add_light: %s" % self.host.rah_last_error().decode(errors="replace"))
+        self._dims()
+        return index
+
+    def remove_light(self, index):
+        """Removes light `index` (its [light] block deleted); the lights after it move up by one."""
+        if not 0 <= index < self.n_lights:
+            raise ValueError("remove_light: light index %d out of range (%d lights)" % (index, self.n_lights))
+        if self.host.rah_light_remove(self.h, index) != 0:
+            raise RtxError("remove_light: %s" % self.host.rah_last_error().decode(errors="replace"))
+        self._dims()
 
     # ---- GPU ------------------------------------------------------------------------------------
     def gpu(self):
@@ -712,6 +789,34 @@ class Scene:
         wide = np.zeros((n.value, S, 8), np.float32); prune = np.zeros((n.value, 2 * S, 8), np.float32)
         _check(self.rtx.rtx_scene_mesh_flat_read(g, mesh, C.byref(n), _np_ptr(wide), _np_ptr(prune), n.value, _np_ptr(root)), "rtx_scene_mesh_flat_read")
         return wide, prune[:, 0:S], prune[:, S:2 * S], root
+
+    def device_lights(self):
+        """The lights as the device holds them (rtx_scene_lights_read): (records, points) -- a structured array with the fields of
+        rtx_light but the pointer (type, color, intensity, dir, pos, n_points) and the area lights' sample points one after the other,
+        float32 (n, 3)."""
+        g = self.gpu()
+        n, nf = C.c_uint32(0), C.c_size_t(0)
+        _check(self.rtx.rtx_scene_lights_read(g, C.byref(n), None, 0, C.byref(nf), None, 0), "rtx_scene_lights_read")
+        raw = (RtxLight * max(n.value, 1))()
+        pts = np.zeros(nf.value, np.float32)
+        _check(self.rtx.rtx_scene_lights_read(g, C.byref(n), raw, n.value, C.byref(nf), _np_ptr(pts), pts.size), "rtx_scene_lights_read")
+        recs = np.zeros(n.value, [("type", np.int32), ("color", np.float32, 3), ("intensity", np.float32), ("dir", np.float32, 3),
+                                  ("pos", np.float32, 3), ("n_points", np.uint32)])
+        for i in range(n.value):
+            recs[i] = (raw[i].type, tuple(raw[i].color), raw[i].intensity, tuple(raw[i].dir), tuple(raw[i].pos), raw[i].n_points)
+        return recs, pts.reshape(-1, 3)
+
+    def device_prune_copies(self, mesh):
+        """Every copy of mesh `mesh`'s prune blocks as the device holds them (rtx_scene_mesh_prune_copy_read): float32 (copies, n_wide, 2 S, 8)
+        -- copy 0 the one any ray uses, 1 the camera's, 2 + l point light l's; S = rtx_wide_node_slots()."""
+        g = self.gpu()
+        nc, nw = C.c_uint32(0), C.c_uint32(0)
+        _check(self.rtx.rtx_scene_mesh_prune_copy_read(g, mesh, 0, C.byref(nc), C.byref(nw), None, 0), "rtx_scene_mesh_prune_copy_read")
+        S = int(self.rtx.rtx_wide_node_slots())
+        out = np.zeros((nc.value, nw.value, 2 * S, 8), np.float32)
+        for c in range(nc.value):
+            _check(self.rtx.rtx_scene_mesh_prune_copy_read(g, mesh, c, C.byref(nc), C.byref(nw), _np_ptr(out[c]), nw.value), "rtx_scene_mesh_prune_copy_read")
+        return out
 
     def edit_times(self):
         """Host wall ms of the last rtx_scene_update_mesh: {build, flatten (on the device, records swapped in), sources + estimate queued,

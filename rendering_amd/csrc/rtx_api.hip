@@ -134,6 +134,10 @@ struct rtx_scene {
 	// device allocations that live as long as the scene.  Their counted bytes, with the meshes', are the scene data resident in HBM
 	// (rtx_scene_bytes: nodes, leaf references, shading arrays, maps, skybox)
 	DevBag owned;
+	// the light records and the area lights' sample points: a bag of their own, replaced as a whole by rtx_scene_set_lights (rtx_edit.hip);
+	// the records as uploaded (points: device pointers)
+	DevBag lightsOwned;
+	std::vector<Light> lightRecs;
 	// the records as uploaded, kept for the edits (rtx_scene_set_object, rtx_scene_update_mesh: rtx_edit.hip): per mesh its device record and the
 	// allocations of its geometry, normals and tangents (replaced as a whole by rtx_scene_update_mesh); per object its record and its description
 	std::vector<Mesh> meshRecs;
@@ -210,7 +214,8 @@ struct rtx_scene {
 	bool costsUsable = false;
 	// source copies of the prune records (rtxd::PruneRec, rtx_source.hip): per mesh the copies' base, the reference arrays and the
 	// slots' reference ranges; the point lights that have a copy; what the copies were last built for
-	struct SrcMesh { PruneBlock* base = nullptr; uint32_t nWide = 0, nRefs = 0; const RefA* refA = nullptr; const RefB* refB = nullptr; const RefC* refC = nullptr;
+	// (pruneAlloc / pruneWide: the allocation of copy 0 and the source copies, whether or not the copies are used -- rtx_scene_set_lights lays it out again)
+	struct SrcMesh { PruneBlock* pruneAlloc = nullptr; uint32_t pruneWide = 0; PruneBlock* base = nullptr; uint32_t nWide = 0, nRefs = 0; const RefA* refA = nullptr; const RefB* refB = nullptr; const RefC* refC = nullptr;
 	                 const uint32_t* slotRange = nullptr; float* refP = nullptr; float* blockP = nullptr; float vmax = 0; uint32_t meshIndex = 0; };
 	std::vector<SrcMesh> srcMeshes;
 	std::vector<std::array<float, 4>> estLights;        // first-frame estimate: point lights (x, y, z, 2) and distant lights (direction, 1)
@@ -219,6 +224,7 @@ struct rtx_scene {
 	std::vector<uint8_t> srcLightIsPoint;
 	float srcNmax = 1.0f;                 // the longest shading normal a shadow ray's origin is offset along (planes keep theirs un-normalised)
 	float srcBuiltBias = -1.0f; bool srcLightsBuilt = false;
+	std::vector<uint8_t> srcLightFresh;   // after rtx_scene_set_lights, until the next buildSources: [l] != 0 -- light l's copy is still the one built for its position and srcBuiltBias
 	float srcBuiltCam[3] = { 0, 0, 0 }; bool srcCamBuilt = false;
 	// rtx_render_frame: event pairs around the last few frames, read back (without waiting) by later calls
 	// Preparing a view (source copies of the prune records, the cost estimate, the tile lists) is queued on the NULL stream and never waits for the
@@ -380,6 +386,20 @@ int residentBlocks(const rtx_scene* s, FrameKernel kernel, int knobPerCU, int* b
 	return RTX_OK;
 }
 
+// The grids of the persistent launches.  The occupancy is asked of the mesh kernels with the box test and culling, whatever variant the
+// scene launches: PLAIN counts for pass 1 only (a PLAIN scene's pass-1 kernels may hold more blocks per CU than the general ones:
+// RTX_WAVES_PLAIN), a scene without meshes for the frame kernel only.  Again when the kernel family changes (rtx_scene_set_lights).
+int askResidentBlocks(rtx_scene* s)
+{
+	Variant v = { false, false, true, true, s->plain };
+	int rc;
+	if ((rc = residentBlocks(s, pass1Kernel(v), s->knobs.pass1BlocksPerCU, &s->blocksPass1))) return rc;
+	v.plain = false;
+	if ((rc = residentBlocks(s, ssaaKernel(v), s->knobs.ssaaBlocksPerCU, &s->blocksSsaa))) return rc;
+	v.analytic = s->analytic;
+	return residentBlocks(s, frameKernel(v), s->knobs.frameBlocksPerCU, &s->blocksFrame);
+}
+
 int ensureWork(rtx_scene* s)
 {
 	HIPCHK(hipSetDevice(s->device));
@@ -389,16 +409,8 @@ int ensureWork(rtx_scene* s)
 		HIPCHK(s->orderWork.reserve(8 * 32 * 32));      // rtxTileOrderKernel: entries per (queue, block, class)
 		HIPCHK(s->counters.reserve(16));
 		HIPCHK(hipMemset(s->counters, 0, 16 * sizeof(unsigned long long)));
-		// The occupancy is asked of the mesh kernels with the box test and culling, whatever variant the scene launches: PLAIN counts for
-		// pass 1 only (a PLAIN scene's pass-1 kernels may hold more blocks per CU than the general ones: RTX_WAVES_PLAIN), a scene without
-		// meshes for the frame kernel only.
-		Variant v = { false, false, true, true, s->plain };
-		int rc;
-		if ((rc = residentBlocks(s, pass1Kernel(v), s->knobs.pass1BlocksPerCU, &s->blocksPass1))) return rc;
-		v.plain = false;
-		if ((rc = residentBlocks(s, ssaaKernel(v), s->knobs.ssaaBlocksPerCU, &s->blocksSsaa))) return rc;
-		v.analytic = s->analytic;
-		if ((rc = residentBlocks(s, frameKernel(v), s->knobs.frameBlocksPerCU, &s->blocksFrame))) return rc;
+		const int rc = askResidentBlocks(s);
+		if (rc) return rc;
 	}
 	const int blocks = std::max(s->blocksFrame, s->blocksPass1 > s->blocksSsaa ? s->blocksPass1 : s->blocksSsaa);
 	const uint32_t totalLanes = (uint32_t)blocks * 256u;
@@ -502,6 +514,7 @@ int buildSources(rtx_scene* s)
 		if (!lightsSame)
 			for (uint32_t l = 0; l < nLights; l++) {
 				if (!s->srcLightIsPoint[l]) continue;      // (its copy stays generic; the kernels never select it)
+				if (s->srcBuiltBias == v.bias && l < s->srcLightFresh.size() && s->srcLightFresh[l]) continue;      // (a light rtx_scene_set_lights left where it was)
 				// the line of a shadow ray -- orig = P + N bias, dir = -normalize(P - pos), both rounded (scene.cpp:787, lights.cpp:32-38) -- passes
 				// pos within |N| bias (1 + 2 u) + sqrt(3) u (3.01 |P|_inf + 2.01 |pos|_inf); |P|_inf <= vmax + kSrcAinfMax + |N| bias for the
 				// origins pruneAlive lets the copy serve.  Twice the rounding part for good measure.
@@ -513,6 +526,7 @@ int buildSources(rtx_scene* s)
 			}
 	}
 	HIPCHK(hipGetLastError());
+	s->srcLightFresh.clear();
 	if (failed) { s->srcCamBuilt = false; s->srcLightsBuilt = false; return fail(RTX_ERR_DEVICE, "buildSources: a source copy of the prune records could not be reset"); }
 	memcpy(s->srcBuiltCam, v.camPos, 12); s->srcCamBuilt = true;
 	s->srcBuiltBias = v.bias; s->srcLightsBuilt = true;
@@ -833,6 +847,7 @@ int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nL
 		for (uint32_t c = 0; c < nCopies; c++)
 			if (hipMemcpy(pb + (size_t)c * prune.size(), prune.data(), prune.size() * sizeof(PruneBlock), hipMemcpyHostToDevice) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMemcpy (prune blocks)"));
 		dm.prune = pb;
+		sm.pruneAlloc = pb; sm.pruneWide = (uint32_t)prune.size();
 		if (nCopies > 1) { sm.base = pb; sm.nWide = (uint32_t)prune.size(); }
 	}
 	dm.vmax = vmaxMesh;
@@ -885,6 +900,61 @@ void meshObjectRecord(const rtx_scene* s, Object& d, const Mesh& dm, const rtx_s
 	// The box test inflates a slot's true box by 216 dmax |orig - v0|_inf P (pruneAlive): with the origin about a mesh size away
 	// that is 216 P mesh sizes, so only meshes of small triangles gain from it; the plane test does not depend on P.
 	d.pruneBoxes = (dm.prune && std::isfinite(dm.rootRec.P) && dm.rootRec.P < 1.0f / 216.0f) ? 1u : 0u;
+}
+
+// The lights of a description, checked before anything is uploaded or replaced (rtx_scene_create, rtx_scene_set_lights).
+int checkLights(uint32_t n, const rtx_light* lights)
+{
+	if (n && !lights) return fail(RTX_ERR_ARG, "lights is NULL");
+	for (uint32_t i = 0; i < n; i++) {
+		const rtx_light& l = lights[i];
+		if (l.type < RTX_LIGHT_DISTANT || l.type > RTX_LIGHT_AREA) return fail(RTX_ERR_ARG, "bad light type");
+		if (l.type == RTX_LIGHT_AREA && (!l.points || l.n_points == 0)) return fail(RTX_ERR_ARG, "area light without sample points");
+	}
+	return RTX_OK;
+}
+
+// The light records and the area lights' sample points into `bag`: recs = the records as the device holds them, *dev = their array.
+int uploadLights(uint32_t n, const rtx_light* lights, DevBag& bag, std::vector<Light>& recs, const Light** dev)
+{
+	recs.resize(n);
+	for (uint32_t i = 0; i < n; i++) {
+		const rtx_light& l = lights[i];
+		Light& d = recs[i];
+		memset(&d, 0, sizeof(d));
+		d.type = l.type; memcpy(d.color, l.color, 12); d.intensity = l.intensity;
+		memcpy(d.dir, l.dir, 12); memcpy(d.pos, l.pos, 12);
+		d.nPoints = l.n_points;
+		if (l.type == RTX_LIGHT_AREA) HIPCHK(bag.upload(l.points, (size_t)l.n_points * 3, &d.points));
+	}
+	HIPCHK(bag.upload(recs.data(), recs.size(), dev));
+	return RTX_OK;
+}
+
+// What preparing a view and the launches read of the lights beside their records: the lights that have a source copy of the prune
+// records, the light terms of the first-frame estimate, the counts of the argument block.
+void deriveLights(rtx_scene* s, uint32_t n, const rtx_light* lights)
+{
+	s->srcLightPos.clear(); s->srcLightIsPoint.clear(); s->estLights.clear();
+	for (uint32_t i = 0; i < n; i++) {
+		const rtx_light& l = lights[i];
+		s->srcLightPos.push_back({ { l.pos[0], l.pos[1], l.pos[2] } });
+		s->srcLightIsPoint.push_back(l.type == RTX_LIGHT_POINT ? 1 : 0);
+		if (l.type == RTX_LIGHT_POINT) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f } });
+		else if (l.type == RTX_LIGHT_DISTANT) s->estLights.push_back({ { l.dir[0], l.dir[1], l.dir[2], 1.0f } });
+		// an area light casts n_points shadow rays per shaded point (scene.cpp:790-806) from about its centre: a point light whose shadow counts n_points times
+		else if (l.type == RTX_LIGHT_AREA) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f + 4.0f * (float)std::min<uint32_t>(l.n_points, 4096u) } });
+	}
+	s->params.nLights = n;
+	s->params.nSrcLights = s->knobs.sources ? std::min<uint32_t>(n, kMaxSrcLights) : 0u;
+}
+
+// The PLAIN kernel family holds while every object is Diffuse and no light an area light (over the current records).
+void choosePlain(rtx_scene* s)
+{
+	s->plain = true;
+	for (const Object& d : s->objectRecs) if (d.material != 0) s->plain = false;
+	for (const Light& l : s->lightRecs) if (l.type == RTX_LIGHT_AREA) s->plain = false;
 }
 
 // The spheres' and planes' share of what preparing a view reads (rtx_scene_create; again after rtx_scene_set_object, rtx_edit.hip): the planes the
@@ -983,7 +1053,6 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		if (o.material < 0 || o.material > 3) return fail(RTX_ERR_ARG, "bad material");
 		if (o.type == RTX_OBJ_MESH && (o.mesh < 0 || (uint32_t)o.mesh >= desc->n_meshes)) return fail(RTX_ERR_ARG, "bad mesh index");
 		if (o.type == RTX_OBJ_MESH) s->analytic = false;
-		if (o.material != 0) s->plain = false;
 		d.type = o.type; d.material = o.material;
 		memcpy(d.pos, o.pos, 12); memcpy(d.color, o.color, 12); memcpy(d.normal, o.normal, 12);
 		d.ior = o.ior; d.ambient = o.ambient; d.diffuse = o.diffuse; d.specular = o.specular; d.nSpecular = o.n_specular;
@@ -996,36 +1065,17 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		HIPCHK(s->owned.upload(sb.data(), sb.size(), &dev));
 		if (!sb.empty()) s->meshLeaves.push_back({ dev, (uint32_t)(sb.size() / 8) });
 	}
-	std::vector<Light> lights(desc->n_lights);
-	for (uint32_t i = 0; i < desc->n_lights; i++) {
-		const rtx_light& l = desc->lights[i];
-		Light& d = lights[i];
-		memset(&d, 0, sizeof(d));
-		if (l.type < RTX_LIGHT_DISTANT || l.type > RTX_LIGHT_AREA) return fail(RTX_ERR_ARG, "bad light type");
-		d.type = l.type; memcpy(d.color, l.color, 12); d.intensity = l.intensity;
-		memcpy(d.dir, l.dir, 12); memcpy(d.pos, l.pos, 12);
-		d.nPoints = l.n_points;
-		s->srcLightPos.push_back({ { l.pos[0], l.pos[1], l.pos[2] } });
-		s->srcLightIsPoint.push_back(l.type == RTX_LIGHT_POINT ? 1 : 0);
-		if (l.type == RTX_LIGHT_POINT) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f } });
-		else if (l.type == RTX_LIGHT_DISTANT) s->estLights.push_back({ { l.dir[0], l.dir[1], l.dir[2], 1.0f } });
-		// an area light casts n_points shadow rays per shaded point (scene.cpp:790-806) from about its centre: a point light whose shadow counts n_points times
-		else if (l.type == RTX_LIGHT_AREA) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f + 4.0f * (float)std::min<uint32_t>(l.n_points, 4096u) } });
-		if (l.type == RTX_LIGHT_AREA) s->plain = false;
-		if (l.type == RTX_LIGHT_AREA) {
-			if (!l.points || l.n_points == 0) return fail(RTX_ERR_ARG, "area light without sample points");
-			HIPCHK(s->owned.upload(l.points, (size_t)l.n_points * 3, &d.points));
-		}
-	}
 	int rc;
+	if ((rc = checkLights(desc->n_lights, desc->lights))) return rc;
 	HIPCHK(s->owned.upload(meshes.data(), meshes.size(), &s->params.meshes));
 	HIPCHK(s->owned.upload(objs.data(), objs.size(), &s->params.objects));
 	s->meshRecs = meshes; s->objectRecs = objs;
 	chooseBoxPrune(s);
 	s->objectDescs.assign(desc->objects, desc->objects + desc->n_objects);
-	HIPCHK(s->owned.upload(lights.data(), lights.size(), &s->params.lights));
-	s->params.nObjects = desc->n_objects; s->params.nLights = desc->n_lights;
-	s->params.nSrcLights = s->knobs.sources ? std::min<uint32_t>(desc->n_lights, kMaxSrcLights) : 0u;
+	if ((rc = uploadLights(desc->n_lights, desc->lights, s->lightsOwned, s->lightRecs, &s->params.lights))) return rc;
+	s->params.nObjects = desc->n_objects;
+	deriveLights(s, desc->n_lights, desc->lights);
+	choosePlain(s);
 	if (desc->sky_w && desc->sky_h && desc->sky[0]) {
 		const float* faces[6];
 		for (int k = 0; k < 6; k++) {
@@ -2022,7 +2072,7 @@ int rtx_kernel_time_stats(rtx_scene* s, int which, uint32_t* launches, double* t
 int rtx_scene_bytes(rtx_scene* s, size_t* bytes)
 {
 	if (!s || !bytes) return fail(RTX_ERR_ARG, "scene/bytes is NULL");
-	*bytes = s->owned.bytes();
+	*bytes = s->owned.bytes() + s->lightsOwned.bytes();
 	for (const DevBag& m : s->meshOwned) *bytes += m.bytes();
 	return RTX_OK;
 }

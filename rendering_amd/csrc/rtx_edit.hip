@@ -1,5 +1,5 @@
-// Editing a live scene (include/rtx_scene_edit.h): an object's record (rtx_scene_set_object) and a mesh's triangles
-// (rtx_scene_update_mesh).  A scene edited here holds what rtx_scene_create would have uploaded for the edited description: the mesh's
+// Editing a live scene (include/rtx_scene_edit.h): an object's record (rtx_scene_set_object), a mesh's triangles
+// (rtx_scene_update_mesh) and the lights (rtx_scene_set_lights).  A scene edited here holds what rtx_scene_create would have uploaded for the edited description: the mesh's
 // structure is built again on the device with the reference's builder (rtx_bvh.hip) and flattened with the very code the load runs
 // (flattenMesh / uploadMeshGeometry in rtx_api.hip); everything derived from the geometry that preparing a view reads is rebuilt.
 // Part of rtx_api.hip's translation unit (no kernel of its own).
@@ -48,7 +48,7 @@ int refreshAnalytic(rtx_scene* s)
 // root boxes) with the frame-mode measurements made on it, the frame kept for rtx_frame_status.
 int refreshView(rtx_scene* s)
 {
-	s->srcCamBuilt = false; s->srcLightsBuilt = false;
+	s->srcCamBuilt = false; s->srcLightsBuilt = false; s->srcLightFresh.clear();
 	for (auto& q : s->tileQueues) { q.forget(); q.lastUse = 0; }
 	s->lastFrameQueue = ~(size_t)0;
 	s->viewSerial++;
@@ -148,6 +148,104 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	return RTX_OK;
 }
 
+// The lights of a live scene replaced as a whole (include/rtx_scene_edit.h).  Everything rtx_scene_create derives from the
+// lights is derived again: their records and sample points (a bag of their own), the number of source copies per mesh, the copies of the
+// point lights, the kernel family, the light terms of the cost estimate.
+int rtx_scene_set_lights(rtx_scene* s, uint32_t n, const rtx_light* lights)
+{
+	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
+	int rc;
+	if ((rc = checkLights(n, lights))) return rc;
+	if ((rc = editBegin(s, nullptr))) return rc;
+
+	// 1. the new records and sample points, beside the old ones until everything that can fail has been done
+	DevBag bag;
+	std::vector<Light> recs;
+	const Light* dev = nullptr;
+	if ((rc = uploadLights(n, lights, bag, recs, &dev))) return rc;
+
+	// 2. the meshes' prune blocks when the number of lights with a source copy changes: copy 0 and the camera's copy are carried over
+	const uint32_t oldSrc = std::min<uint32_t>((uint32_t)s->srcLightPos.size(), kMaxSrcLights), newSrc = std::min<uint32_t>(n, kMaxSrcLights);
+	const bool relay = s->knobs.sources && oldSrc != newSrc;
+	std::vector<PruneBlock*> fresh(s->srcMeshes.size(), nullptr);
+	if (relay) {
+		bool ok = true;
+		for (size_t mi = 0; mi < s->srcMeshes.size() && ok; mi++) {
+			const rtx_scene::SrcMesh& sm = s->srcMeshes[mi];
+			if (!sm.pruneAlloc) continue;
+			const size_t one = (size_t)sm.pruneWide * sizeof(PruneBlock);
+			ok = s->meshOwned[mi].alloc(&fresh[mi], (2 + (size_t)newSrc) * one) == hipSuccess;
+			for (uint32_t c = 0; c < 2 + newSrc && ok; c++)      // (the lights' copies: generic until buildSources)
+				ok = hipMemcpy(fresh[mi] + (size_t)c * sm.pruneWide, sm.pruneAlloc + (size_t)(c == 1 ? 1 : 0) * sm.pruneWide, one, hipMemcpyDeviceToDevice) == hipSuccess;
+		}
+		if (!ok) {
+			for (size_t mi = 0; mi < fresh.size(); mi++) s->meshOwned[mi].drop(fresh[mi]);
+			return fail(RTX_ERR_DEVICE, "rtx_scene_set_lights: the prune blocks could not be laid out again");
+		}
+		std::vector<Mesh> meshes = s->meshRecs;
+		std::vector<Object> objs = s->objectRecs;
+		std::vector<rtx_scene::SrcMesh> sms = s->srcMeshes;
+		for (size_t mi = 0; mi < sms.size(); mi++) {
+			if (!fresh[mi]) continue;
+			if (meshes[mi].prune) meshes[mi].prune = fresh[mi];
+			if (sms[mi].base) sms[mi].base = fresh[mi];
+			sms[mi].pruneAlloc = fresh[mi];
+		}
+		for (Object& d : objs)
+			if (d.type == RTX_OBJ_MESH) meshObjectRecord(s, d, meshes[d.mesh], sms[d.mesh]);
+		if ((!meshes.empty() && hipMemcpy((Mesh*)s->params.meshes, meshes.data(), meshes.size() * sizeof(Mesh), hipMemcpyHostToDevice) != hipSuccess) ||
+		    (!objs.empty() && hipMemcpy((Object*)s->params.objects, objs.data(), objs.size() * sizeof(Object), hipMemcpyHostToDevice) != hipSuccess)) {
+			// (put the old records back: the scene stays as it was)
+			if (!meshes.empty()) (void)hipMemcpy((Mesh*)s->params.meshes, s->meshRecs.data(), meshes.size() * sizeof(Mesh), hipMemcpyHostToDevice);
+			if (!objs.empty()) (void)hipMemcpy((Object*)s->params.objects, s->objectRecs.data(), objs.size() * sizeof(Object), hipMemcpyHostToDevice);
+			for (size_t mi = 0; mi < fresh.size(); mi++) s->meshOwned[mi].drop(fresh[mi]);
+			return fail(RTX_ERR_DEVICE, "rtx_scene_set_lights: the records could not be uploaded");
+		}
+		for (size_t mi = 0; mi < sms.size(); mi++)
+			if (fresh[mi]) s->meshOwned[mi].drop(s->srcMeshes[mi].pruneAlloc);      // (the old blocks)
+		s->meshRecs.swap(meshes); s->objectRecs.swap(objs); s->srcMeshes.swap(sms);
+	}
+
+	// 3. which point lights keep their copy: same index, same position, built for the current bias, in blocks that stayed.  A copy whose
+	// light is no longer a point light goes back to copy 0's content, as after a load; buildSources builds the others.
+	std::vector<uint8_t> keep(newSrc, 0);
+	bool allKept = s->srcLightsBuilt;
+	for (uint32_t l = 0; l < newSrc && s->knobs.sources; l++) {
+		const bool point = lights[l].type == RTX_LIGHT_POINT;
+		keep[l] = !relay && s->srcLightsBuilt && point && s->srcLightIsPoint[l] && !memcmp(s->srcLightPos[l].data(), lights[l].pos, 12);
+		if (point && !keep[l]) allKept = false;
+		if (point || relay || !s->srcLightIsPoint[l]) continue;
+		for (const auto& sm : s->srcMeshes)
+			if (sm.base) HIPCHK(hipMemcpyAsync(sm.base + (size_t)(2 + l) * sm.nWide, sm.base, (size_t)sm.nWide * sizeof(PruneBlock), hipMemcpyDeviceToDevice, nullptr));
+	}
+
+	// 4. the new lights take the old ones' place (which are freed with `bag`: nothing queued reads them, editBegin)
+	s->lightsOwned.swap(bag);
+	s->lightRecs.swap(recs);
+	s->params.lights = dev;
+	deriveLights(s, n, lights);
+	s->srcLightFresh = keep; s->srcLightsBuilt = allKept;
+	if (allKept) s->srcLightFresh.clear();
+	s->lastFused.valid = false;
+	const bool wasPlain = s->plain;
+	choosePlain(s);
+	if (s->plain != wasPlain) {
+		// (another kernel family: pass 1's grid, and what was measured of the frame modes with the old one)
+		if ((rc = askResidentBlocks(s))) return rc;
+		for (auto& q : s->tileQueues) { q.frameMs[0] = q.frameMs[1] = -1.f; q.frameSamples[0] = q.frameSamples[1] = 0; q.framesSeen = 0; q.generation++; q.fusedGaveUp = false; }
+	}
+	if ((rc = ensureWork(s))) return rc;
+
+	// 5. The view's preparation again: the sources of the new point lights and the cost estimate.  What does not depend on the lights is
+	// kept -- the camera's source copy (built from the camera and the geometry), the cached tile lists (which tiles a launch lists and in
+	// which queue: the view, the row range, the row ownership and the meshes' root boxes) and, within a kernel family, the frame-mode
+	// measurements (they only choose between two ways of rendering the same pixels) -- so a light animation renders at a warm frame's
+	// cost.  No pixel depends on any of it: tile costs only order the work.
+	if ((rc = prepBegin(s))) return rc;
+	if ((rc = prepareView(s))) return rc;
+	return prepEnd(s);
+}
+
 // rtx_debug.h: the device's current tree of mesh `mesh` in the rtx_mesh layout (decoded from its node records and leaf references)
 int rtx_scene_mesh_read(rtx_scene* s, uint32_t mesh, uint32_t* counts2, float* node_bounds, int32_t* node_skip, int32_t* leaf_begin,
                         int32_t* leaf_count, uint32_t* refs)
@@ -195,6 +293,54 @@ int rtx_scene_mesh_flat_read(rtx_scene* s, uint32_t mesh, uint32_t* n_wide, void
 		if (dm.prune) HIPCHK(hipMemcpy(prune_out, dm.prune, n * sizeof(PruneBlock), hipMemcpyDeviceToHost));
 		else memset(prune_out, 0, n * sizeof(PruneBlock));
 	}
+	return RTX_OK;
+}
+
+// rtx_debug.h: the light records and the area lights' sample points as the device holds them
+int rtx_scene_lights_read(rtx_scene* s, uint32_t* n_lights, rtx_light* lights_out, uint32_t cap_lights, size_t* n_point_floats, float* points_out, size_t cap_point_floats)
+{
+	if (!s || !n_lights) return fail(RTX_ERR_ARG, "scene/n_lights is NULL");
+	const uint32_t n = s->params.nLights;
+	*n_lights = n;
+	if (n_point_floats) *n_point_floats = 0;
+	if (!n || (!lights_out && !n_point_floats && !points_out)) return RTX_OK;
+	HIPCHK(hipSetDevice(s->device));
+	HIPCHK(hipDeviceSynchronize());
+	std::vector<Light> recs(n);
+	HIPCHK(hipMemcpy(recs.data(), s->params.lights, n * sizeof(Light), hipMemcpyDeviceToHost));
+	size_t at = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const Light& d = recs[i];
+		if (lights_out && i < cap_lights) {
+			rtx_light& l = lights_out[i];
+			memset(&l, 0, sizeof(l));
+			l.type = d.type; memcpy(l.color, d.color, 12); l.intensity = d.intensity; memcpy(l.dir, d.dir, 12); memcpy(l.pos, d.pos, 12);
+			l.n_points = d.nPoints;      // (points stays NULL: the sample points follow one another in points_out, in light order)
+		}
+		if (d.type != RTX_LIGHT_AREA) continue;
+		const size_t nf = (size_t)d.nPoints * 3;
+		if (points_out && at + nf <= cap_point_floats && nf) HIPCHK(hipMemcpy(points_out + at, d.points, nf * sizeof(float), hipMemcpyDeviceToHost));
+		at += nf;
+	}
+	if (n_point_floats) *n_point_floats = at;
+	return RTX_OK;
+}
+
+// rtx_debug.h: copy `copy` of mesh `mesh`'s prune blocks (0 any ray, 1 the camera's, 2 + l point light l's)
+int rtx_scene_mesh_prune_copy_read(rtx_scene* s, uint32_t mesh, uint32_t copy, uint32_t* n_copies, uint32_t* n_wide, void* prune_out, uint32_t cap_wide)
+{
+	if (!s || !n_copies || !n_wide) return fail(RTX_ERR_ARG, "scene/n_copies/n_wide is NULL");
+	if (mesh >= s->srcMeshes.size()) return fail(RTX_ERR_ARG, "mesh index out of range");
+	const rtx_scene::SrcMesh& sm = s->srcMeshes[mesh];
+	*n_wide = sm.pruneWide;
+	*n_copies = !sm.pruneAlloc ? 0u : (s->knobs.sources ? 2u + std::min<uint32_t>((uint32_t)s->srcLightPos.size(), kMaxSrcLights) : 1u);
+	if (!prune_out) return RTX_OK;
+	if (copy >= *n_copies) return fail(RTX_ERR_ARG, "copy out of range");
+	const size_t nw = std::min<size_t>(cap_wide, sm.pruneWide);
+	if (!nw) return RTX_OK;
+	HIPCHK(hipSetDevice(s->device));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(prune_out, sm.pruneAlloc + (size_t)copy * sm.pruneWide, nw * sizeof(PruneBlock), hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
 

@@ -460,6 +460,7 @@ int deviceMeshGeometry(rtx_scene* s, const rtx_bvh* b, const float* pos_dev, uin
 		hipLaunchKernelGGL(pruneKernel, dim3(blocksFor((size_t)nWide * kWideSlots)), dim3(256), 0, st, (const uint32_t*)slotNode, nWide, (const Agg*)agg, pb, slotRange.get());
 		for (uint32_t c = 1; c < nCopies; c++) HIPCHK(hipMemcpyAsync(pb + (size_t)c * nWide, pb, (size_t)nWide * sizeof(PruneBlock), hipMemcpyDeviceToDevice, st));
 		dm.prune = pb;
+		sm.pruneAlloc = pb; sm.pruneWide = nWide;
 		if (nCopies > 1) { sm.base = pb; sm.nWide = nWide; }
 	}
 	dm.vmax = vmaxMesh;

@@ -65,6 +65,13 @@ public:
 	// count elements from host / device memory in an allocation of their own; *out = nullptr when there is nothing to copy
 	template <typename T> hipError_t upload(const T* host, size_t count, const T** out) { return copy(host, count, out, hipMemcpyHostToDevice); }
 	template <typename T> hipError_t copyFrom(const T* dev, size_t count, const T** out) { return copy(dev, count, out, hipMemcpyDeviceToDevice); }
+	// frees the one allocation that starts at p (counted: it was made with counted = true); false when the bag does not hold it
+	bool drop(const void* p, bool counted = true)
+	{
+		for (auto it = items_.begin(); p && it != items_.end(); ++it)
+			if (it->get() == p) { if (counted) bytes_ -= it->capacity(); items_.erase(it); return true; }
+		return false;
+	}
 	void swap(DevBag& o) noexcept { items_.swap(o.items_); std::swap(bytes_, o.bytes_); }
 	void clear() { items_.clear(); bytes_ = 0; }
 	size_t bytes() const { return bytes_; }

@@ -2,6 +2,7 @@
 // (rtx_kernels.hip: ST_NEXT_LIGHT); the host classes only carry the parameters.
 #pragma once
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "geometry.h"
@@ -38,3 +39,19 @@ public:
 	bool pointsCreated = false;
 	std::vector<Vec3f> points;
 };
+
+// The values of a [light] block's keys (NULL: the key is absent).  The .scene parser applies every key=value line of a block through
+// applyLightKeys, and so do the edits of a loaded scene (Scene::setLight / addLight): an edited light is the light its edited block loads.
+struct LightKeys {
+	const float *color = nullptr, *intensity = nullptr;                  // every type
+	const float *direction = nullptr;                                    // distant
+	const float *position = nullptr;                                     // point
+	const float *pos = nullptr, *i = nullptr, *j = nullptr;              // area
+	const int* samples = nullptr;
+};
+std::unique_ptr<Light> makeLight(const std::string& type);       // "distant" / "point" / "area" (the block's type= line); null otherwise
+std::unique_ptr<Light> cloneLight(const Light& light);
+const char* lightKeyRefused(LightType type, const LightKeys& keys);   // the first key given that the type does not have; NULL when all fit
+// Sets the given keys (all of which the type has).  An area light whose pos, i, j or samples change gets its sample points again
+// at the next setPoints().
+void applyLightKeys(Light& light, const LightKeys& keys);

@@ -81,6 +81,12 @@ public:
 	// without one the host structure is built again as the loader builds it.
 	void moveObject(size_t index, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3);
 	void moveObjectApply(size_t index, const float* pos3, const float* rot3, const float* size3, const float* radius1, const float* normal3, double (*now)());
+	// The lights edited as their [light] blocks would be (lights.h: the keys go through the code the parser applies them with; a key the
+	// type does not have is an error and nothing changes).  addLight appends -- a new block after the last one -- and returns the index.
+	// With a live GPU scene each ends in one rtx_scene_set_lights (include/rtx_scene_edit.h); if that fails the lights are put back.
+	void setLight(size_t index, const LightKeys& keys);
+	size_t addLight(const std::string& type, const LightKeys& keys);
+	void removeLight(size_t index);
 	void syncTrees();                          // meshes moved on the GPU: their `ac` read back from the device (done by every reader of `ac`)
 	// host wall ms of the last moveObject: {placement (Mesh::place), upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
 	double lastMoveMs[4] = { 0, 0, 0, 0 };
@@ -110,6 +116,7 @@ private:
 	void ssaaOnDevice();
 	void readTimes();
 	void renderAC();
+	void lightsToDevice();
 	rtx_scene* gpu_ = nullptr;
 	bool viewDirty_ = true;
 	std::unique_ptr<DeviceFrame> frame_;

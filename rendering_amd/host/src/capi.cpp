@@ -248,6 +248,58 @@ int rah_object_type(void* h, int obj)
 	return t == ObjectType::Sphere ? RTX_OBJ_SPHERE : t == ObjectType::Plane ? RTX_OBJ_PLANE : t == ObjectType::Mesh ? RTX_OBJ_MESH : -1;
 }
 
+// RTX_LIGHT_* of light `index` (-1: no such light)
+int rah_light_type(void* h, int index)
+{
+	Scene* s = (Scene*)h;
+	if (index < 0 || index >= (int)s->lights.size()) return -1;
+	const LightType t = s->lights[index]->type;
+	return t == LightType::DistantLight ? RTX_LIGHT_DISTANT : t == LightType::PointLight ? RTX_LIGHT_POINT : t == LightType::AreaLight ? RTX_LIGHT_AREA : -1;
+}
+
+namespace {
+LightKeys lightKeys(const float* color3, const float* intensity1, const float* direction3, const float* position3, const float* pos3, const float* i3,
+                    const float* j3, const int* samples1)
+{
+	LightKeys k;
+	k.color = color3; k.intensity = intensity1; k.direction = direction3; k.position = position3; k.pos = pos3; k.i = i3; k.j = j3; k.samples = samples1;
+	return k;
+}
+}
+
+// Light `index` as its [light] block would load with these keys set (Scene::setLight; NULL = unchanged): every type color3 / intensity1, a
+// distant light direction3, a point light position3, an area light pos3 / i3 / j3 / samples1.  0, or -1 with rah_last_error (bad index, a key
+// the type does not have, a device error): the scene is then as it was.
+int rah_light_set(void* h, int index, const float* color3, const float* intensity1, const float* direction3, const float* position3, const float* pos3,
+                  const float* i3, const float* j3, const int* samples1)
+{
+	return guarded<int>(-1, [&] {
+		if (index < 0) { noteError("setLight: light index out of range"); LOG_ERROR(); }
+		((Scene*)h)->setLight((size_t)index, lightKeys(color3, intensity1, direction3, position3, pos3, i3, j3, samples1));
+		return 0;
+	});
+}
+
+// A new light of RTX_LIGHT_* `type` after the last one, with the parser's defaults for absent keys (Scene::addLight): its index, or -1.
+int rah_light_add(void* h, int type, const float* color3, const float* intensity1, const float* direction3, const float* position3, const float* pos3,
+                  const float* i3, const float* j3, const int* samples1)
+{
+	return guarded<int>(-1, [&] {
+		const char* name = type == RTX_LIGHT_DISTANT ? "distant" : type == RTX_LIGHT_POINT ? "point" : type == RTX_LIGHT_AREA ? "area" : "?";
+		return (int)((Scene*)h)->addLight(name, lightKeys(color3, intensity1, direction3, position3, pos3, i3, j3, samples1));
+	});
+}
+
+// Removes light `index` (Scene::removeLight): 0, or -1 with rah_last_error.
+int rah_light_remove(void* h, int index)
+{
+	return guarded<int>(-1, [&] {
+		if (index < 0) { noteError("removeLight: light index out of range"); LOG_ERROR(); }
+		((Scene*)h)->removeLight((size_t)index);
+		return 0;
+	});
+}
+
 // host wall ms of the last rah_object_move: {placement, upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
 void rah_object_move_times(void* h, float* ms4)
 {

@@ -84,25 +84,26 @@ void parseOption(Scene& sc, const KeyValue& kv)
 	else std::cout << "Scene, unknown key: " << k << '\n';
 }
 
+// One key=value line of a [light] block: its values go through applyLightKeys (lights.h), as an edit's do (Scene::setLight).
 void parseLight(std::unique_ptr<Light>& light, const KeyValue& kv)
 {
 	const std::string& k = kv.key; const std::string& v = kv.value;
 	if (k == "type") {
-		if (v == "distant") light = std::make_unique<DistantLight>();
-		else if (v == "point") light = std::make_unique<PointLight>();
-		else if (v == "area") light = std::make_unique<AreaLight>();
+		if (auto made = makeLight(v)) light = std::move(made);
 		return;
 	}
 	if (!light) { std::cout << "Error, light type missing\n"; return; }
-	auto need = [&](LightType t) { if (light->type != t) LOG_ERROR(); };
-	if (k == "color") light->color = str3ToFloat(splitString(v, ','));
-	else if (k == "intensity") light->intensity = strToFloat(v);
-	else if (k == "direction") { need(LightType::DistantLight); static_cast<DistantLight&>(*light).dir = str3ToFloat(splitString(v, ',')); }
-	else if (k == "position") { need(LightType::PointLight); static_cast<PointLight&>(*light).pos = str3ToFloat(splitString(v, ',')); }
-	else if (k == "pos") { need(LightType::AreaLight); static_cast<AreaLight&>(*light).pos = str3ToFloat(splitString(v, ',')); }
-	else if (k == "i") { need(LightType::AreaLight); static_cast<AreaLight&>(*light).i = str3ToFloat(splitString(v, ',')); }
-	else if (k == "j") { need(LightType::AreaLight); static_cast<AreaLight&>(*light).j = str3ToFloat(splitString(v, ',')); }
-	else if (k == "samples") { need(LightType::AreaLight); static_cast<AreaLight&>(*light).samples = strToInt(v); }
+	LightKeys keys;
+	Vec3f v3;
+	float f = 0; int n = 0;
+	const float** vec = k == "color" ? &keys.color : k == "direction" ? &keys.direction : k == "position" ? &keys.position : k == "pos" ? &keys.pos
+	                    : k == "i" ? &keys.i : k == "j" ? &keys.j : nullptr;
+	if (vec) { v3 = str3ToFloat(splitString(v, ',')); *vec = &v3.x; }
+	else if (k == "intensity") { f = strToFloat(v); keys.intensity = &f; }
+	else if (k == "samples") { n = strToInt(v); keys.samples = &n; }
+	else return;
+	if (lightKeyRefused(light->type, keys)) LOG_ERROR();
+	applyLightKeys(*light, keys);
 }
 
 void parseObject(Scene& sc, std::unique_ptr<Object>& object, const KeyValue& kv)
@@ -382,6 +383,31 @@ void fillView(Scene& sc, rtx_view& v)
 	v.aspect = (sc.options.width) / (float)sc.options.height;                          // scene.cpp:448
 }
 
+// the lights' records in the description (an area light's sample points: AreaLight::setPoints, kept alive in `points`)
+void flattenLights(LightsVector& lights, std::vector<rtx_light>& out, std::vector<std::vector<float>>& points)
+{
+	out.clear(); points.clear();
+	for (auto& lp : lights) {
+		rtx_light rl{};
+		put3(rl.color, lp->color); rl.intensity = lp->intensity;
+		if (lp->type == LightType::DistantLight) { rl.type = RTX_LIGHT_DISTANT; put3(rl.dir, static_cast<DistantLight&>(*lp).dir); }
+		else if (lp->type == LightType::PointLight) { rl.type = RTX_LIGHT_POINT; put3(rl.pos, static_cast<PointLight&>(*lp).pos); }
+		else if (lp->type == LightType::AreaLight) {
+			auto& al = static_cast<AreaLight&>(*lp);
+			al.setPoints();
+			rl.type = RTX_LIGHT_AREA; put3(rl.pos, al.pos);
+			points.emplace_back(al.points.size() * 3);
+			for (size_t i = 0; i < al.points.size(); ++i) put3(&points.back()[i * 3], al.points[i]);
+			rl.n_points = (uint32_t)al.points.size();
+		}
+		else LOG_ERROR();
+		out.push_back(rl);
+	}
+	// area-light point arrays may have been reallocated while pushing: fix the pointers up now
+	size_t k = 0;
+	for (auto& rl : out) if (rl.type == RTX_LIGHT_AREA) rl.points = points[k++].data();
+}
+
 } // namespace
 
 FlatScene* flattenScene(Scene& sc)
@@ -429,27 +455,7 @@ FlatScene* flattenScene(Scene& sc)
 		}
 		fs->objects.push_back(ro);
 	}
-	for (auto& lp : sc.lights) {
-		rtx_light rl{};
-		put3(rl.color, lp->color); rl.intensity = lp->intensity;
-		if (lp->type == LightType::DistantLight) { rl.type = RTX_LIGHT_DISTANT; put3(rl.dir, static_cast<DistantLight&>(*lp).dir); }
-		else if (lp->type == LightType::PointLight) { rl.type = RTX_LIGHT_POINT; put3(rl.pos, static_cast<PointLight&>(*lp).pos); }
-		else if (lp->type == LightType::AreaLight) {
-			auto& al = static_cast<AreaLight&>(*lp);
-			al.setPoints();
-			rl.type = RTX_LIGHT_AREA; put3(rl.pos, al.pos);
-			fs->lightPoints.emplace_back(al.points.size() * 3);
-			for (size_t i = 0; i < al.points.size(); ++i) put3(&fs->lightPoints.back()[i * 3], al.points[i]);
-			rl.n_points = (uint32_t)al.points.size();
-		}
-		else LOG_ERROR();
-		fs->lights.push_back(rl);
-	}
-	// area-light point arrays may have been reallocated while pushing: fix the pointers up now
-	{
-		size_t k = 0;
-		for (auto& rl : fs->lights) if (rl.type == RTX_LIGHT_AREA) rl.points = fs->lightPoints[k++].data();
-	}
+	flattenLights(sc.lights, fs->lights, fs->lightPoints);
 	fs->desc.n_objects = (uint32_t)fs->objects.size(); fs->desc.objects = fs->objects.data();
 	fs->desc.n_meshes = (uint32_t)fs->meshes.size(); fs->desc.meshes = fs->meshes.data();
 	fs->desc.n_lights = (uint32_t)fs->lights.size(); fs->desc.lights = fs->lights.data();
@@ -644,6 +650,59 @@ void Scene::moveObjectApply(size_t index, const float* pos3, const float* rot3, 
 	m.treeOnDevice = true;
 	float ms[4];
 	if (rtx_scene_edit_times(gpu_, ms) == RTX_OK) { m.ac->buildMs = ms[0]; m.ac->builtOnDevice = true; }
+}
+
+// The lights as the device should hold them now: one rtx_scene_set_lights (nothing to do before the GPU scene exists: it is created
+// from the edited lights).
+void Scene::lightsToDevice()
+{
+	if (!gpu_) return;
+	std::vector<rtx_light> recs;
+	std::vector<std::vector<float>> points;
+	flattenLights(lights, recs, points);
+	gpuCheck(rtx_scene_set_lights(gpu_, (uint32_t)recs.size(), recs.data()), "rtx_scene_set_lights");
+}
+
+namespace {
+void checkLightKeys(const char* who, LightType type, const LightKeys& keys)
+{
+	const char* bad = lightKeyRefused(type, keys);
+	if (!bad) return;
+	const char* name = type == LightType::DistantLight ? "distant" : type == LightType::PointLight ? "point" : "area";
+	noteError(std::string(who) + ": a " + name + " light has no key " + bad);
+	LOG_ERROR();
+}
+}
+
+void Scene::setLight(size_t index, const LightKeys& keys)
+{
+	if (index >= lights.size()) { noteError("setLight: light index out of range"); LOG_ERROR(); }
+	checkLightKeys("setLight", lights[index]->type, keys);
+	std::unique_ptr<Light> keep = cloneLight(*lights[index]);
+	applyLightKeys(*lights[index], keys);
+	try { lightsToDevice(); }
+	catch (...) { lights[index] = std::move(keep); throw; }
+}
+
+size_t Scene::addLight(const std::string& type, const LightKeys& keys)
+{
+	std::unique_ptr<Light> light = makeLight(type);
+	if (!light) { noteError("addLight: unknown light type " + type); LOG_ERROR(); }
+	checkLightKeys("addLight", light->type, keys);
+	applyLightKeys(*light, keys);
+	lights.push_back(std::move(light));
+	try { lightsToDevice(); }
+	catch (...) { lights.pop_back(); throw; }
+	return lights.size() - 1;
+}
+
+void Scene::removeLight(size_t index)
+{
+	if (index >= lights.size()) { noteError("removeLight: light index out of range"); LOG_ERROR(); }
+	std::unique_ptr<Light> keep = std::move(lights[index]);
+	lights.erase(lights.begin() + (std::ptrdiff_t)index);
+	try { lightsToDevice(); }
+	catch (...) { lights.insert(lights.begin() + (std::ptrdiff_t)index, std::move(keep)); throw; }
 }
 
 void Scene::syncTrees()
