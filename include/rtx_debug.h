@@ -114,6 +114,9 @@ int rtx_scene_lights_read(rtx_scene* scene, uint32_t* n_lights, rtx_light* light
                           float* points_out, size_t cap_point_floats);
 int rtx_scene_mesh_prune_copy_read(rtx_scene* scene, uint32_t mesh, uint32_t copy, uint32_t* n_copies, uint32_t* n_wide, void* prune_out,
                                    uint32_t cap_wide);
+/* The object records decoded from device memory (not from the host's copy) into the description's layout: *n_objects / *n_meshes what
+ * the scene holds, objects_out (may be NULL) written up to cap_objects records.  Synchronises the device. */
+int rtx_scene_objects_read(rtx_scene* scene, uint32_t* n_objects, rtx_object* objects_out, uint32_t cap_objects, uint32_t* n_meshes);
 
 /* Device allocations this library holds at the moment, in this process, and their bytes: everything behind scenes, acceleration structures and
  * communicators, scratch of calls in progress included (not the caller's own buffers).  Back where it was once everything created since has been

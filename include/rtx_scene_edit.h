@@ -1,5 +1,5 @@
-/* Editing a live scene: objects of a scene created by rtx_scene_create move between frames and its lights change
- * (DESIGN.md 3.9).  An extension of the C ABI
+/* Editing a live scene: objects of a scene created by rtx_scene_create move between frames, its lights change
+ *  and its objects appear and disappear.  An extension of the C ABI
  * in rtx.h -- the reference has no edit API; moving an object there means editing its [object] block and loading the file again, and a
  * scene edited here renders, bit for bit, what a scene created from the edited description renders.
  *
@@ -37,6 +37,32 @@ int rtx_scene_update_mesh(rtx_scene* scene, uint32_t mesh, const float* tri_pos_
  * rtx_scene_bytes reports a fresh scene's number), the source copies of every mesh's prune records -- laid out again when
  * min(n_lights, 6) changes --, the kernel family (RTX_VARIANT_PLAIN holds while no light is an area light), the cost estimate. */
 int rtx_scene_set_lights(rtx_scene* scene, uint32_t n_lights, const rtx_light* lights);
+
+/* The object list and the mesh list replaced as a whole: one call covers an object appended or inserted at any index, removed, reordered,
+ * of another type or material at its index, and n_objects == 0.  meshes[i] says where mesh i of the new list comes from; the `mesh` field
+ * of the objects indexes the new list.  Refused (RTX_ERR_ARG, the scene untouched): NULL arrays with a count, a bad type, material or
+ * mesh index (the checks of the load), keep out of range, one old mesh kept twice, a new mesh with missing arrays, a normal map without
+ * tangents.  It waits for the device and for `stream` first.  Afterwards the device holds what the load would have uploaded and prepared
+ * for the current view, lights and sky with these objects and meshes: a kept mesh is neither uploaded nor built again, a mesh that is
+ * not kept is freed with everything of its own (rtx_scene_bytes reports a fresh scene's number), the kernel variant is chosen again, and
+ * every source copy of every mesh's prune records is built again. */
+typedef struct rtx_mesh_build {   /* triangles in device memory; the tree is built on the device as by rtx_scene_update_mesh */
+	const float* tri_pos_dev;     /* n_tris x 9 */
+	const float* tri_nrm_dev;     /* n_tris x 9 */
+	const float* tri_tb_dev;      /* n_tris x 6, or NULL (required iff mesh->normal_map) */
+	float root_lo[3], root_hi[3]; /* the root box Mesh::loadModel sets */
+	int32_t ac_penalty;
+} rtx_mesh_build;
+
+typedef struct rtx_mesh_source {
+	int32_t keep;                 /* >= 0: mesh `keep` of the scene as it is now takes this index, untouched; -1: a new mesh */
+	const rtx_mesh* mesh;         /* new mesh: host memory, as in rtx_scene_desc */
+	const rtx_mesh_build* build;  /* NULL: `mesh` carries tree and triangles (the load path);
+	                                 else n_tris (> 0), tri_uv and the maps come from `mesh`, its tree and tri_pos/nrm/tb are ignored */
+} rtx_mesh_source;
+
+int rtx_scene_set_objects(rtx_scene* scene, uint32_t n_objects, const rtx_object* objects, uint32_t n_meshes,
+                          const rtx_mesh_source* meshes, void* stream);
 
 #ifdef __cplusplus
 }

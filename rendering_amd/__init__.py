@@ -40,11 +40,11 @@ RTX_SYMBOLS = [
     "rtx_bvh_build", "rtx_bvh_info", "rtx_bvh_read", "rtx_bvh_destroy",
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
     "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read", "rtx_live_device_memory",
-    "rtx_scene_lights_read", "rtx_scene_mesh_prune_copy_read",
+    "rtx_scene_lights_read", "rtx_scene_mesh_prune_copy_read", "rtx_scene_objects_read",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
-RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh", "rtx_scene_set_lights"]
+RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh", "rtx_scene_set_lights", "rtx_scene_set_objects"]
 
 # the extension of include/rtx_query.h: queries on a loaded scene that render nothing (not part of the drop-in boundary)
 RTX_QUERY_SYMBOLS = ["rtx_occluded_rays"]
@@ -158,6 +158,10 @@ def load():
     host.rah_light_set.argtypes = [vp, i32] + [vp] * 8
     host.rah_light_add.argtypes = [vp, i32] + [vp] * 8
     host.rah_light_remove.argtypes = [vp, i32]
+    rtx.rtx_scene_set_objects.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+    rtx.rtx_scene_objects_read.argtypes = [vp, C.POINTER(C.c_uint32), vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    host.rah_object_add.argtypes = [vp, i32, i32, C.c_char_p] + [vp] * 4 + [C.c_char_p] + [vp] * 2 + [C.c_char_p] * 4
+    host.rah_object_remove.argtypes = [vp, i32]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -318,12 +322,52 @@ LIGHT_KEYS = {"distant": ("direction", "color", "intensity"), "point": ("positio
 _LIGHT_ARGS = ("color", "intensity", "direction", "position", "pos", "i", "j", "samples")
 
 
+class RtxObject(C.Structure):
+    """rtx_object (include/rtx.h)"""
+    _fields_ = [("type", C.c_int32), ("material", C.c_int32), ("pos", C.c_float * 3), ("color", C.c_float * 3), ("ior", C.c_float),
+                ("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float), ("n_specular", C.c_float), ("radius2", C.c_float),
+                ("normal", C.c_float * 3), ("mesh", C.c_int32)]
+
+
+# the keys of an [object] block per type, in the order they are applied, and the values a material= line takes after its name
+OBJECT_TYPES = {"sphere": 1, "plane": 2, "mesh": 3}
+OBJECT_KEYS = {"sphere": ("pos", "color", "material", "radius"), "plane": ("pos", "color", "material", "normal"),
+               "mesh": ("pos", "size", "rot", "color", "material", "name", "diffuse_map", "normal_map", "specular_map")}
+_OBJECT_ARGS = ("pos", "size", "rot", "color", "material", "radius", "normal", "name", "diffuse_map", "normal_map", "specular_map")
+_OBJECT_TEXT = ("material", "name", "diffuse_map", "normal_map", "specular_map")
+MATERIAL_VALUES = {"diffuse": 0, "reflective": 0, "transparent": 1, "phong": 4}
+
+
 class _RtxMesh(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_refs", C.c_uint32), ("n_tris", C.c_uint32), ("node_bounds", C.c_void_p), ("node_skip", C.c_void_p),
                 ("leaf_begin", C.c_void_p), ("leaf_count", C.c_void_p), ("refs", C.c_void_p), ("tri_pos", C.c_void_p), ("tri_nrm", C.c_void_p),
                 ("tri_uv", C.c_void_p), ("tri_tb", C.c_void_p), ("diffuse_w", C.c_uint32), ("diffuse_h", C.c_uint32), ("diffuse_map", C.c_void_p),
                 ("normal_w", C.c_uint32), ("normal_h", C.c_uint32), ("normal_map", C.c_void_p), ("specular_w", C.c_uint32), ("specular_h", C.c_uint32),
                 ("specular_map", C.c_void_p)]
+
+
+class RtxView(C.Structure):
+    """rtx_view (include/rtx.h)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bias", C.c_float), ("max_ray_depth", C.c_int32), ("background", C.c_float * 3),
+                ("flags", C.c_uint32), ("cam_pos", C.c_float * 3), ("cam_matrix", C.c_float * 16), ("scale", C.c_float), ("aspect", C.c_float)]
+
+
+class RtxSceneDesc(C.Structure):
+    """rtx_scene_desc (include/rtx.h): what rah_flat_desc points to"""
+    _fields_ = [("view", RtxView), ("n_objects", C.c_uint32), ("objects", C.POINTER(RtxObject)), ("n_meshes", C.c_uint32),
+                ("meshes", C.POINTER(_RtxMesh)), ("n_lights", C.c_uint32), ("lights", C.POINTER(RtxLight)), ("sky_w", C.c_uint32), ("sky_h", C.c_uint32),
+                ("sky", C.c_void_p * 6)]
+
+
+class RtxMeshBuild(C.Structure):
+    """rtx_mesh_build (include/rtx_scene_edit.h)"""
+    _fields_ = [("tri_pos_dev", C.c_void_p), ("tri_nrm_dev", C.c_void_p), ("tri_tb_dev", C.c_void_p), ("root_lo", C.c_float * 3),
+                ("root_hi", C.c_float * 3), ("ac_penalty", C.c_int32)]
+
+
+class RtxMeshSource(C.Structure):
+    """rtx_mesh_source (include/rtx_scene_edit.h)"""
+    _fields_ = [("keep", C.c_int32), ("mesh", C.POINTER(_RtxMesh)), ("build", C.POINTER(RtxMeshBuild))]
 
 
 def mesh_flatten_probe(bvh):
@@ -398,6 +442,7 @@ class Scene:
         if not self.h:
             raise RtxError("could not load scene %s: %s" % (scene_path, self.host.rah_last_error().decode(errors="replace")))
         self.device = device
+        self._cwd = cwd
         self.host.rah_scene_set_device(self.h, device)
         self._dims()
         self._gpu = None
@@ -555,6 +600,57 @@ class Scene:
             raise ValueError("remove_light: light index %d out of range (%d lights)" % (index, self.n_lights))
         if self.host.rah_light_remove(self.h, index) != 0:
             raise RtxError("remove_light: %s" % self.host.rah_last_error().decode(errors="replace"))
+        self._dims()
+
+    def add_object(self, type, at=None, **keys):
+        """A new object of `type` ("sphere", "plane", "mesh") before object `at` (None: after the last one), as a new [object] block with
+        these keys would load (absent keys: the loader's defaults); returns its index.  Every type takes pos / color / material, a sphere
+        radius, a plane normal, a mesh size / rot / name (its OBJ file) / diffuse_map / normal_map / specular_map; material is the text of
+        a material= line ("reflective", "transparent,1.3", "phong,0.3,0.5,0.6,20"; absent: Diffuse), file names resolve as the scene
+        file's do.  An unknown type, a key the type does not have, a wrong number of values or a bad index raises ValueError, a file that
+        cannot be loaded RtxError, and nothing changes.  With a live GPU scene the device's objects are replaced (rtx_scene_set_objects):
+        every other mesh stays as it is, renders queued before the call see the old objects, later ones the new."""
+        if type not in OBJECT_TYPES:
+            raise ValueError("add_object: unknown object type %r (sphere, plane, mesh)" % (type,))
+        if at is not None and not 0 <= at <= self.n_objects:
+            raise ValueError("add_object: object index %d out of range (%d objects)" % (at, self.n_objects))
+        bad = [k for k in keys if k not in OBJECT_KEYS[type]]
+        if bad:
+            raise ValueError("add_object: a %s has no key %s (it takes %s)" % (type, ", ".join(bad), ", ".join(OBJECT_KEYS[type])))
+        arrs = {}
+        for k, v in keys.items():
+            if k in _OBJECT_TEXT:
+                if not isinstance(v, str) or not v or "\n" in v:
+                    raise ValueError("add_object: %s takes a line of text, got %r" % (k, v))
+                if k == "material":
+                    parts = v.split(",")
+                    if parts[0] not in MATERIAL_VALUES or len(parts) - 1 != MATERIAL_VALUES[parts[0]]:
+                        raise ValueError("add_object: material %r (diffuse, reflective, transparent,<ior>, phong,<ambient>,<diffuse>,<specular>,<n>)" % (v,))
+                    try:
+                        [float(x) for x in parts[1:]]
+                    except ValueError:
+                        raise ValueError("add_object: material %r: its values must be numbers" % (v,))
+                arrs[k] = v.encode()
+                continue
+            want = 1 if k == "radius" else 3
+            a = np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1))
+            if a.size != want:
+                raise ValueError("add_object: %s takes %d value%s, got %d" % (k, want, "" if want == 1 else "s", a.size))
+            arrs[k] = a
+        args = [(arrs[k] if k in _OBJECT_TEXT else _np_ptr(arrs[k])) if k in arrs else None for k in _OBJECT_ARGS]
+        index = self.host.rah_object_add(self.h, OBJECT_TYPES[type], -1 if at is None else at, self._cwd.encode(), *args)
+        if index < 0:
+            raise RtxError("add_object: %s" % self.host.rah_last_error().decode(errors="replace"))
+        self._dims()
+        return index
+
+    def remove_object(self, index):
+        """Removes object `index` (its [object] block deleted); the objects after it move up by one.  With a live GPU scene a removed mesh is
+        freed with everything of its own, and every other mesh stays as it is (rtx_scene_set_objects)."""
+        if not 0 <= index < self.n_objects:
+            raise ValueError("remove_object: object index %d out of range (%d objects)" % (index, self.n_objects))
+        if self.host.rah_object_remove(self.h, index) != 0:
+            raise RtxError("remove_object: %s" % self.host.rah_last_error().decode(errors="replace"))
         self._dims()
 
     # ---- GPU ------------------------------------------------------------------------------------
@@ -805,6 +901,24 @@ class Scene:
         for i in range(n.value):
             recs[i] = (raw[i].type, tuple(raw[i].color), raw[i].intensity, tuple(raw[i].dir), tuple(raw[i].pos), raw[i].n_points)
         return recs, pts.reshape(-1, 3)
+
+    def device_objects(self):
+        """The objects as the device holds them (rtx_scene_objects_read): (records, n_meshes) -- a structured array with the fields of
+        rtx_object (type, material, pos, color, ior, ambient, diffuse, specular, n_specular, radius2, normal, mesh), decoded from the
+        device's records, and the number of meshes."""
+        g = self.gpu()
+        n, nm = C.c_uint32(0), C.c_uint32(0)
+        _check(self.rtx.rtx_scene_objects_read(g, C.byref(n), None, 0, C.byref(nm)), "rtx_scene_objects_read")
+        raw = (RtxObject * max(n.value, 1))()
+        _check(self.rtx.rtx_scene_objects_read(g, C.byref(n), raw, n.value, C.byref(nm)), "rtx_scene_objects_read")
+        recs = np.zeros(n.value, [("type", np.int32), ("material", np.int32), ("pos", np.float32, 3), ("color", np.float32, 3), ("ior", np.float32),
+                                  ("ambient", np.float32), ("diffuse", np.float32), ("specular", np.float32), ("n_specular", np.float32),
+                                  ("radius2", np.float32), ("normal", np.float32, 3), ("mesh", np.int32)])
+        for i in range(n.value):
+            r = raw[i]
+            recs[i] = (r.type, r.material, tuple(r.pos), tuple(r.color), r.ior, r.ambient, r.diffuse, r.specular, r.n_specular, r.radius2,
+                       tuple(r.normal), r.mesh)
+        return recs, nm.value
 
     def device_prune_copies(self, mesh):
         """Every copy of mesh `mesh`'s prune blocks as the device holds them (rtx_scene_mesh_prune_copy_read): float32 (copies, n_wide, 2 S, 8)

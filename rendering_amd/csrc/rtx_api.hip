@@ -142,6 +142,10 @@ struct rtx_scene {
 	// allocations of its geometry, normals and tangents (replaced as a whole by rtx_scene_update_mesh); per object its record and its description
 	std::vector<Mesh> meshRecs;
 	std::vector<DevBag> meshOwned;
+	// per mesh what rtx_scene_update_mesh keeps: its uv and maps (freed with the mesh by rtx_scene_set_objects); and the Mesh[] and Object[]
+	// arrays behind params.meshes / params.objects with the spheres' entry of meshLeaves, replaced as a whole by rtx_scene_set_objects
+	std::vector<DevBag> meshFixed;
+	DevBag recordsOwned;
 	std::vector<Object> objectRecs;
 	std::vector<rtx_object> objectDescs;
 	DevArray<float> sphereLeafDev;     // the spheres' entry of meshLeaves once an edit has rebuilt it
@@ -887,10 +891,9 @@ int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nL
 	return RTX_OK;
 }
 
-// The fields of a mesh object's record that derive from its mesh (rootBox from meshBounds).
-void meshObjectRecord(const rtx_scene* s, Object& d, const Mesh& dm, const rtx_scene::SrcMesh& sm)
+// The fields of a mesh object's record that derive from its mesh (bx: the mesh's root box, its six floats of meshBounds).
+void meshObjectRecord(const float* bx, Object& d, const Mesh& dm, const rtx_scene::SrcMesh& sm)
 {
-	const float* bx = &s->meshBounds[(size_t)d.mesh * 6];
 	for (int c = 0; c < 3; c++) { d.rootBox[2 * c] = bx[c]; d.rootBox[2 * c + 1] = bx[3 + c]; }
 	d.fatRadius = dm.fatRadius; memcpy(d.centre, dm.centre, 12); d.radius = dm.radius;
 	d.meshFlags = (dm.nNodes ? 1u : 0u) | (dm.boxesRegular ? 2u : 0u) | (dm.nWide ? 4u : 0u);
@@ -900,6 +903,87 @@ void meshObjectRecord(const rtx_scene* s, Object& d, const Mesh& dm, const rtx_s
 	// The box test inflates a slot's true box by 216 dmax |orig - v0|_inf P (pruneAlive): with the origin about a mesh size away
 	// that is 216 P mesh sizes, so only meshes of small triangles gain from it; the plane test does not depend on P.
 	d.pruneBoxes = (dm.prune && std::isfinite(dm.rootRec.P) && dm.rootRec.P < 1.0f / 216.0f) ? 1u : 0u;
+}
+
+// A mesh of a description, checked before anything of it is uploaded (rtx_scene_create, rtx_scene_set_objects).
+int checkMesh(const rtx_mesh& m)
+{
+	if (!m.node_bounds || !m.node_skip || !m.leaf_begin || !m.leaf_count || (m.n_refs && !m.refs) || (m.n_tris && (!m.tri_pos || !m.tri_nrm || !m.tri_uv)))
+		return fail(RTX_ERR_ARG, "mesh arrays missing");
+	if (m.normal_map && !m.tri_tb) return fail(RTX_ERR_ARG, "normal map without tangents");
+	return RTX_OK;
+}
+
+// What of a mesh stays when its triangles move (rtx_scene_update_mesh): uv and maps, into a bag of their own.
+int uploadMeshFixed(const rtx_mesh& m, DevBag& fixed, Mesh& dm)
+{
+	HIPCHK(fixed.upload(m.tri_uv, (size_t)m.n_tris * 6, &dm.uv));
+	HIPCHK(fixed.upload(m.diffuse_map, (size_t)m.diffuse_w * m.diffuse_h * 3, &dm.diffuse));
+	HIPCHK(fixed.upload(m.normal_map, (size_t)m.normal_w * m.normal_h * 3, &dm.normal));
+	HIPCHK(fixed.upload(m.specular_map, (size_t)m.specular_w * m.specular_h, &dm.specular));
+	dm.dW = m.diffuse_w; dm.dH = m.diffuse_h; dm.nW = m.normal_w; dm.nH = m.normal_h; dm.sW = m.specular_w; dm.sH = m.specular_h;
+	return RTX_OK;
+}
+
+// Mesh `mi` of a description as the load uploads it, for nLights lights: the geometry, normals and tangents into `owned` (what
+// rtx_scene_update_mesh replaces), uv and maps into `fixed`.
+int uploadMesh(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, DevBag& owned, DevBag& fixed, Mesh& dm, rtx_scene::SrcMesh& sm,
+               rtx_scene::MeshLeaves& leaves, float bounds[6])
+{
+	memset(&dm, 0, sizeof(dm));
+	int rc;
+	if ((rc = uploadMeshGeometry(s, m, mi, nLights, owned, dm, sm, leaves, bounds))) return rc;
+	HIPCHK(owned.upload(m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm));
+	HIPCHK(owned.upload(m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb));
+	return uploadMeshFixed(m, fixed, dm);
+}
+
+// The objects of a description, checked before anything is uploaded or replaced (rtx_scene_create, rtx_scene_set_objects).
+int checkObjects(uint32_t n, const rtx_object* objects, uint32_t nMeshes)
+{
+	if (n && !objects) return fail(RTX_ERR_ARG, "objects is NULL");
+	for (uint32_t i = 0; i < n; i++) {
+		const rtx_object& o = objects[i];
+		if (o.type < RTX_OBJ_SPHERE || o.type > RTX_OBJ_MESH) return fail(RTX_ERR_ARG, "bad object type");
+		if (o.material < 0 || o.material > 3) return fail(RTX_ERR_ARG, "bad material");
+		if (o.type == RTX_OBJ_MESH && (o.mesh < 0 || (uint32_t)o.mesh >= nMeshes)) return fail(RTX_ERR_ARG, "bad mesh index");
+	}
+	return RTX_OK;
+}
+
+// The object records of a description (checked: checkObjects) over the mesh records, source records and root boxes of its meshes.
+std::vector<Object> objectRecords(uint32_t n, const rtx_object* objects, const std::vector<Mesh>& meshes, const std::vector<rtx_scene::SrcMesh>& sms,
+                                  const std::vector<float>& meshBounds)
+{
+	std::vector<Object> objs(n);
+	for (uint32_t i = 0; i < n; i++) {
+		const rtx_object& o = objects[i];
+		Object& d = objs[i];
+		memset(&d, 0, sizeof(d));
+		d.type = o.type; d.material = o.material;
+		memcpy(d.pos, o.pos, 12); memcpy(d.color, o.color, 12); memcpy(d.normal, o.normal, 12);
+		d.ior = o.ior; d.ambient = o.ambient; d.diffuse = o.diffuse; d.specular = o.specular; d.nSpecular = o.n_specular;
+		d.r2 = o.radius2; d.mesh = o.mesh;
+		if (o.type == RTX_OBJ_MESH) meshObjectRecord(&meshBounds[(size_t)o.mesh * 6], d, meshes[o.mesh], sms[o.mesh]);
+	}
+	return objs;
+}
+
+// The Mesh[] and Object[] arrays and the spheres' entry of the cost estimate (sb: analyticEstimate) into `bag`.
+int uploadRecords(const std::vector<Mesh>& meshes, const std::vector<Object>& objs, const std::vector<float>& sb, DevBag& bag, const Mesh** devMeshes,
+                  const Object** devObjs, const float** devSpheres)
+{
+	HIPCHK(bag.upload(sb.data(), sb.size(), devSpheres));
+	HIPCHK(bag.upload(meshes.data(), meshes.size(), devMeshes));
+	HIPCHK(bag.upload(objs.data(), objs.size(), devObjs));
+	return RTX_OK;
+}
+
+// No object is a triangle mesh: the kernels without the walk are launched (over the current records).
+void chooseAnalytic(rtx_scene* s)
+{
+	s->analytic = true;
+	for (const Object& d : s->objectRecs) if (d.type == RTX_OBJ_MESH) s->analytic = false;
 }
 
 // The lights of a description, checked before anything is uploaded or replaced (rtx_scene_create, rtx_scene_set_lights).
@@ -1018,58 +1102,33 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 	memset(&s->params, 0, sizeof(Params));
 
 	// meshes: nodes -> 32-byte records, leaf references -> (v0, e1, e2, tri) in three parallel arrays
+	int rc;
 	std::vector<Mesh> meshes(desc->n_meshes);
 	s->meshOwned.resize(desc->n_meshes);
+	s->meshFixed.resize(desc->n_meshes);
 	for (uint32_t mi = 0; mi < desc->n_meshes; mi++) {
 		const rtx_mesh& m = desc->meshes[mi];
-		if (!m.node_bounds || !m.node_skip || !m.leaf_begin || !m.leaf_count || (m.n_refs && !m.refs) || (m.n_tris && (!m.tri_pos || !m.tri_nrm || !m.tri_uv)))
-			return fail(RTX_ERR_ARG, "mesh arrays missing");
-		if (m.normal_map && !m.tri_tb) return fail(RTX_ERR_ARG, "normal map without tangents");
-		Mesh& dm = meshes[mi];
-		memset(&dm, 0, sizeof(dm));
+		if ((rc = checkMesh(m))) return rc;
 		rtx_scene::SrcMesh sm;
 		rtx_scene::MeshLeaves leaves{ nullptr, 0 };
 		float bounds[6];
-		// (the mesh's own allocations are what rtx_scene_update_mesh replaces; uv and maps stay for the scene's life)
-		int rc;
-		if ((rc = uploadMeshGeometry(s, m, mi, desc->n_lights, s->meshOwned[mi], dm, sm, leaves, bounds))) return rc;
+		// (the mesh's own allocations are what rtx_scene_update_mesh replaces; uv and maps stay for the mesh's life)
+		if ((rc = uploadMesh(s, m, mi, desc->n_lights, s->meshOwned[mi], s->meshFixed[mi], meshes[mi], sm, leaves, bounds))) return rc;
 		s->meshBounds.insert(s->meshBounds.end(), bounds, bounds + 6);
 		s->meshLeaves.push_back(leaves);
 		s->srcMeshes.push_back(sm);
-		HIPCHK(s->meshOwned[mi].upload(m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm));
-		HIPCHK(s->owned.upload(m.tri_uv, (size_t)m.n_tris * 6, &dm.uv));
-		HIPCHK(s->meshOwned[mi].upload(m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb));
-		HIPCHK(s->owned.upload(m.diffuse_map, (size_t)m.diffuse_w * m.diffuse_h * 3, &dm.diffuse));
-		HIPCHK(s->owned.upload(m.normal_map, (size_t)m.normal_w * m.normal_h * 3, &dm.normal));
-		HIPCHK(s->owned.upload(m.specular_map, (size_t)m.specular_w * m.specular_h, &dm.specular));
-		dm.dW = m.diffuse_w; dm.dH = m.diffuse_h; dm.nW = m.normal_w; dm.nH = m.normal_h; dm.sW = m.specular_w; dm.sH = m.specular_h;
 	}
-	std::vector<Object> objs(desc->n_objects);
-	for (uint32_t i = 0; i < desc->n_objects; i++) {
-		const rtx_object& o = desc->objects[i];
-		Object& d = objs[i];
-		memset(&d, 0, sizeof(d));
-		if (o.type < RTX_OBJ_SPHERE || o.type > RTX_OBJ_MESH) return fail(RTX_ERR_ARG, "bad object type");
-		if (o.material < 0 || o.material > 3) return fail(RTX_ERR_ARG, "bad material");
-		if (o.type == RTX_OBJ_MESH && (o.mesh < 0 || (uint32_t)o.mesh >= desc->n_meshes)) return fail(RTX_ERR_ARG, "bad mesh index");
-		if (o.type == RTX_OBJ_MESH) s->analytic = false;
-		d.type = o.type; d.material = o.material;
-		memcpy(d.pos, o.pos, 12); memcpy(d.color, o.color, 12); memcpy(d.normal, o.normal, 12);
-		d.ior = o.ior; d.ambient = o.ambient; d.diffuse = o.diffuse; d.specular = o.specular; d.nSpecular = o.n_specular;
-		d.r2 = o.radius2; d.mesh = o.mesh;
-		if (o.type == RTX_OBJ_MESH) meshObjectRecord(s, d, meshes[o.mesh], s->srcMeshes[o.mesh]);
-	}
+	if ((rc = checkObjects(desc->n_objects, desc->objects, desc->n_meshes))) return rc;
+	std::vector<Object> objs = objectRecords(desc->n_objects, desc->objects, meshes, s->srcMeshes, s->meshBounds);
+	if ((rc = checkLights(desc->n_lights, desc->lights))) return rc;
 	{
 		const std::vector<float> sb = analyticEstimate(s, desc->objects, desc->n_objects);
 		const float* dev = nullptr;
-		HIPCHK(s->owned.upload(sb.data(), sb.size(), &dev));
+		if ((rc = uploadRecords(meshes, objs, sb, s->recordsOwned, &s->params.meshes, &s->params.objects, &dev))) return rc;
 		if (!sb.empty()) s->meshLeaves.push_back({ dev, (uint32_t)(sb.size() / 8) });
 	}
-	int rc;
-	if ((rc = checkLights(desc->n_lights, desc->lights))) return rc;
-	HIPCHK(s->owned.upload(meshes.data(), meshes.size(), &s->params.meshes));
-	HIPCHK(s->owned.upload(objs.data(), objs.size(), &s->params.objects));
 	s->meshRecs = meshes; s->objectRecs = objs;
+	chooseAnalytic(s);
 	chooseBoxPrune(s);
 	s->objectDescs.assign(desc->objects, desc->objects + desc->n_objects);
 	if ((rc = uploadLights(desc->n_lights, desc->lights, s->lightsOwned, s->lightRecs, &s->params.lights))) return rc;
@@ -2072,8 +2131,9 @@ int rtx_kernel_time_stats(rtx_scene* s, int which, uint32_t* launches, double* t
 int rtx_scene_bytes(rtx_scene* s, size_t* bytes)
 {
 	if (!s || !bytes) return fail(RTX_ERR_ARG, "scene/bytes is NULL");
-	*bytes = s->owned.bytes() + s->lightsOwned.bytes();
+	*bytes = s->owned.bytes() + s->lightsOwned.bytes() + s->recordsOwned.bytes();
 	for (const DevBag& m : s->meshOwned) *bytes += m.bytes();
+	for (const DevBag& m : s->meshFixed) *bytes += m.bytes();
 	return RTX_OK;
 }
 

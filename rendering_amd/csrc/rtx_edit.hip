@@ -1,5 +1,5 @@
-// Editing a live scene (include/rtx_scene_edit.h, DESIGN.md 3.7, 3.9): an object's record (rtx_scene_set_object), a mesh's triangles
-// (rtx_scene_update_mesh) and the lights (rtx_scene_set_lights).  A scene edited here holds what rtx_scene_create would have uploaded for the edited description: the mesh's
+// Editing a live scene (include/rtx_scene_edit.h, DESIGN.md 3.7, 3.9, 3.10): an object's record (rtx_scene_set_object), a mesh's triangles
+// (rtx_scene_update_mesh), the lights (rtx_scene_set_lights) and the object and mesh lists (rtx_scene_set_objects).  A scene edited here holds what rtx_scene_create would have uploaded for the edited description: the mesh's
 // structure is built again on the device with the reference's builder (rtx_bvh.hip) and flattened with the very code the load runs
 // (flattenMesh / uploadMeshGeometry in rtx_api.hip); everything derived from the geometry that preparing a view reads is rebuilt.
 // Part of rtx_api.hip's translation unit (no kernel of its own).
@@ -60,6 +60,23 @@ int refreshView(rtx_scene* s)
 	return prepEnd(s);
 }
 
+// The geometry of mesh `mi` from nt triangles in device memory (rtx_scene_update_mesh, a new mesh of rtx_scene_set_objects): the reference's
+// builder on the device, then the flatten on the device (rtx_flatten.hip: node records, wide nodes, prune blocks and their copies for the
+// lights of the moment, leaf references, leaf boxes), normals and tangents.  dm keeps its uv and maps; *built: the wall clock after the build.
+int deviceMesh(rtx_scene* s, uint32_t nt, const float* tri_pos_dev, const float* tri_nrm_dev, const float* tri_tb_dev, const float* root_lo, const float* root_hi,
+               int32_t ac_penalty, uint32_t mi, DevBag& owned, Mesh& dm, rtx_scene::SrcMesh& sm, rtx_scene::MeshLeaves& leaves, float box[6], double* built)
+{
+	int rc;
+	rtx_bvh* b = nullptr;
+	if ((rc = rtxBvhBuildDevice(tri_pos_dev, nt, root_lo, root_hi, ac_penalty, s->device, &b))) return rc;
+	const std::unique_ptr<rtx_bvh, void (*)(rtx_bvh*)> hold(b, rtx_bvh_destroy);
+	if (built) *built = wallMs();
+	if ((rc = deviceMeshGeometry(s, b, tri_pos_dev, nt, mi, (uint32_t)s->srcLightPos.size(), owned, dm, sm, leaves, box))) return rc;
+	HIPCHK(owned.copyFrom(tri_nrm_dev, (size_t)nt * 9, &dm.nrm));
+	HIPCHK(owned.copyFrom(tri_tb_dev, (size_t)nt * 6, &dm.tb));
+	return RTX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -102,13 +119,7 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	int rc;
 	if ((rc = editBegin(s, stream))) return rc;
 
-	// 1. the reference's builder on the device, from the caller's triangles
-	rtx_bvh* b = nullptr;
-	if ((rc = rtxBvhBuildDevice(tri_pos_dev, nt, root_lo, root_hi, ac_penalty, s->device, &b))) return rc;
-	const std::unique_ptr<rtx_bvh, void (*)(rtx_bvh*)> hold(b, rtx_bvh_destroy);
-	const double t1 = wallMs();
-
-	// 2. the flatten on the device (rtx_flatten.hip): node records, wide nodes, prune blocks and their copies, leaf references, leaf boxes
+	// 1. the reference's builder on the device, from the caller's triangles; 2. the flatten on the device (deviceMesh)
 	Mesh dm;
 	memset(&dm, 0, sizeof(dm));
 	dm.uv = old.uv; dm.diffuse = old.diffuse; dm.normal = old.normal; dm.specular = old.specular;      // (uv and maps stay)
@@ -117,15 +128,14 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	rtx_scene::MeshLeaves leaves{ nullptr, 0 };
 	float box[6];
 	DevBag owned;      // (dropped with everything in it unless the edit goes through)
-	if ((rc = deviceMeshGeometry(s, b, tri_pos_dev, nt, mesh, (uint32_t)s->srcLightPos.size(), owned, dm, sm, leaves, box))) return rc;
-	HIPCHK(owned.copyFrom(tri_nrm_dev, (size_t)nt * 9, &dm.nrm));
-	HIPCHK(owned.copyFrom(old.tb ? tri_tb_dev : nullptr, (size_t)nt * 6, &dm.tb));
+	double t1 = t0;
+	if ((rc = deviceMesh(s, nt, tri_pos_dev, tri_nrm_dev, old.tb ? tri_tb_dev : nullptr, root_lo, root_hi, ac_penalty, mesh, owned, dm, sm, leaves, box, &t1))) return rc;
 	// the objects of this mesh with their derived fields; then everything is in place on the host and goes up in two copies
 	std::vector<Object> objs = s->objectRecs;
 	const std::vector<float> oldBounds(s->meshBounds.begin() + (size_t)mesh * 6, s->meshBounds.begin() + (size_t)mesh * 6 + 6);
 	std::copy(box, box + 6, s->meshBounds.begin() + (size_t)mesh * 6);
 	for (Object& d : objs)
-		if (d.type == RTX_OBJ_MESH && d.mesh == (int32_t)mesh) meshObjectRecord(s, d, dm, sm);
+		if (d.type == RTX_OBJ_MESH && d.mesh == (int32_t)mesh) meshObjectRecord(&s->meshBounds[(size_t)mesh * 6], d, dm, sm);
 	if (hipMemcpy((Mesh*)s->params.meshes + mesh, &dm, sizeof(Mesh), hipMemcpyHostToDevice) != hipSuccess ||
 	    hipMemcpy((Object*)s->params.objects, objs.data(), objs.size() * sizeof(Object), hipMemcpyHostToDevice) != hipSuccess) {
 		// (put the old records back: the scene stays as it was)
@@ -146,6 +156,105 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	const double t3 = wallMs();
 	s->editMs[0] = (float)(t1 - t0); s->editMs[1] = (float)(t2 - t1); s->editMs[2] = (float)(t3 - t2); s->editMs[3] = (float)(t3 - t0);
 	return RTX_OK;
+}
+
+// The object list and the mesh list of a live scene replaced as a whole (include/rtx_scene_edit.h).  Kept meshes move to their new
+// index with everything of theirs; new ones are uploaded as the load uploads them (host form) or built on the device as rtx_scene_update_mesh
+// builds them (device form); removed ones are freed.  Everything rtx_scene_create derives from the objects is derived again, and no source
+// copy of any mesh's prune records survives the call: they are certified for the srcNmax of the moment, which a new plane may change.
+int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* objects, uint32_t nMeshes, const rtx_mesh_source* sources, void* stream)
+{
+	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
+	int rc;
+	if (nMeshes && !sources) return fail(RTX_ERR_ARG, "meshes is NULL");
+	const size_t nOld = s->meshRecs.size();
+	std::vector<uint8_t> kept(nOld, 0);
+	for (uint32_t mi = 0; mi < nMeshes; mi++) {
+		const rtx_mesh_source& src = sources[mi];
+		if (src.keep >= 0) {
+			if ((size_t)src.keep >= nOld) return fail(RTX_ERR_ARG, "rtx_scene_set_objects: keep out of range");
+			if (kept[src.keep]) return fail(RTX_ERR_ARG, "rtx_scene_set_objects: a mesh is kept twice");
+			kept[src.keep] = 1;
+			continue;
+		}
+		if (src.keep != -1) return fail(RTX_ERR_ARG, "rtx_scene_set_objects: keep out of range");
+		if (!src.mesh) return fail(RTX_ERR_ARG, "rtx_scene_set_objects: a new mesh without its description");
+		const rtx_mesh& m = *src.mesh;
+		if (!src.build) { if ((rc = checkMesh(m))) return rc; continue; }
+		// (there is nothing to build a tree from without triangles: an empty mesh goes the host form's way, as Scene::addObject sends it)
+		if (!m.n_tris) return fail(RTX_ERR_ARG, "rtx_scene_set_objects: a mesh without triangles has no device form");
+		if (!src.build->tri_pos_dev || !src.build->tri_nrm_dev || !m.tri_uv) return fail(RTX_ERR_ARG, "mesh arrays missing");
+		if (m.normal_map && !src.build->tri_tb_dev) return fail(RTX_ERR_ARG, "normal map without tangents");
+	}
+	if ((rc = checkObjects(nObjects, objects, nMeshes))) return rc;
+	if ((rc = editBegin(s, stream))) return rc;
+
+	// 1. the new meshes, beside the scene's until everything that can fail has been done
+	const uint32_t nLights = (uint32_t)s->srcLightPos.size();
+	std::vector<Mesh> meshes(nMeshes);
+	std::vector<DevBag> owned(nMeshes), fixed(nMeshes);
+	std::vector<rtx_scene::SrcMesh> sms(nMeshes);
+	std::vector<rtx_scene::MeshLeaves> leaves(nMeshes, rtx_scene::MeshLeaves{ nullptr, 0 });
+	std::vector<float> bounds((size_t)nMeshes * 6);
+	for (uint32_t mi = 0; mi < nMeshes; mi++) {
+		const rtx_mesh_source& src = sources[mi];
+		if (src.keep >= 0) {
+			meshes[mi] = s->meshRecs[src.keep]; sms[mi] = s->srcMeshes[src.keep]; leaves[mi] = s->meshLeaves[src.keep];
+			sms[mi].meshIndex = mi;
+			std::copy(s->meshBounds.begin() + (size_t)src.keep * 6, s->meshBounds.begin() + (size_t)src.keep * 6 + 6, bounds.begin() + (size_t)mi * 6);
+			continue;
+		}
+		const rtx_mesh& m = *src.mesh;
+		if (!src.build) {
+			if ((rc = uploadMesh(s, m, mi, nLights, owned[mi], fixed[mi], meshes[mi], sms[mi], leaves[mi], &bounds[(size_t)mi * 6]))) return rc;
+			continue;
+		}
+		const rtx_mesh_build& b = *src.build;
+		memset(&meshes[mi], 0, sizeof(Mesh));
+		if ((rc = uploadMeshFixed(m, fixed[mi], meshes[mi]))) return rc;
+		if ((rc = deviceMesh(s, m.n_tris, b.tri_pos_dev, b.tri_nrm_dev, b.tri_tb_dev, b.root_lo, b.root_hi, b.ac_penalty, mi, owned[mi], meshes[mi], sms[mi], leaves[mi],
+		                     &bounds[(size_t)mi * 6], nullptr))) return rc;
+	}
+
+	// 2. the records over them, and the spheres' and planes' share of the derived state (put back if the upload fails)
+	std::vector<Object> objs = objectRecords(nObjects, objects, meshes, sms, bounds);
+	const std::vector<std::array<float, 6>> oldPlanes = s->estPlanes;
+	const float oldNmax = s->srcNmax, oldNmax2 = s->params.srcNmax2;
+	const std::vector<float> sb = analyticEstimate(s, objects, nObjects);
+	DevBag records;
+	const Mesh* devMeshes = nullptr; const Object* devObjs = nullptr; const float* devSpheres = nullptr;
+	if ((rc = uploadRecords(meshes, objs, sb, records, &devMeshes, &devObjs, &devSpheres))) {
+		s->estPlanes = oldPlanes; s->srcNmax = oldNmax; s->params.srcNmax2 = oldNmax2;
+		return rc;
+	}
+
+	// 3. everything takes the old scene's place: kept meshes carry their allocations over, what is left behind is freed (nothing queued
+	// reads it: editBegin)
+	for (uint32_t mi = 0; mi < nMeshes; mi++)
+		if (sources[mi].keep >= 0) { owned[mi].swap(s->meshOwned[sources[mi].keep]); fixed[mi].swap(s->meshFixed[sources[mi].keep]); }
+	s->meshOwned.swap(owned); s->meshFixed.swap(fixed);
+	owned.clear(); fixed.clear();
+	s->recordsOwned.swap(records);
+	records.clear();
+	s->sphereLeafDev.reset();
+	s->meshRecs.swap(meshes); s->srcMeshes.swap(sms); s->meshBounds.swap(bounds); s->objectRecs.swap(objs);
+	s->objectDescs.assign(objects, objects + nObjects);
+	s->meshLeaves.swap(leaves);
+	if (!sb.empty()) s->meshLeaves.push_back({ devSpheres, (uint32_t)(sb.size() / 8) });
+	s->params.meshes = devMeshes; s->params.objects = devObjs; s->params.nObjects = nObjects;
+
+	// 4. the kernel variant again; with another family pass 1's grid, and the ray kernels' occupancy is asked again
+	const bool wasAnalytic = s->analytic, wasPlain = s->plain;
+	chooseAnalytic(s);
+	chooseBoxPrune(s);
+	choosePlain(s);
+	if (s->analytic != wasAnalytic || s->plain != wasPlain)
+		if ((rc = askResidentBlocks(s))) return rc;
+	s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;
+	memset(s->rayOccludedBlocks, 0, sizeof(s->rayOccludedBlocks));
+
+	// 5. the view's preparation again: every source copy is built again, every tile list and frame-mode measurement forgotten
+	return refreshView(s);
 }
 
 // The lights of a live scene replaced as a whole (include/rtx_scene_edit.h).  Everything rtx_scene_create derives from the
@@ -192,7 +301,7 @@ int rtx_scene_set_lights(rtx_scene* s, uint32_t n, const rtx_light* lights)
 			sms[mi].pruneAlloc = fresh[mi];
 		}
 		for (Object& d : objs)
-			if (d.type == RTX_OBJ_MESH) meshObjectRecord(s, d, meshes[d.mesh], sms[d.mesh]);
+			if (d.type == RTX_OBJ_MESH) meshObjectRecord(&s->meshBounds[(size_t)d.mesh * 6], d, meshes[d.mesh], sms[d.mesh]);
 		if ((!meshes.empty() && hipMemcpy((Mesh*)s->params.meshes, meshes.data(), meshes.size() * sizeof(Mesh), hipMemcpyHostToDevice) != hipSuccess) ||
 		    (!objs.empty() && hipMemcpy((Object*)s->params.objects, objs.data(), objs.size() * sizeof(Object), hipMemcpyHostToDevice) != hipSuccess)) {
 			// (put the old records back: the scene stays as it was)
@@ -323,6 +432,31 @@ int rtx_scene_lights_read(rtx_scene* s, uint32_t* n_lights, rtx_light* lights_ou
 		at += nf;
 	}
 	if (n_point_floats) *n_point_floats = at;
+	return RTX_OK;
+}
+
+// rtx_debug.h: the object records decoded from device memory into the description's layout
+int rtx_scene_objects_read(rtx_scene* s, uint32_t* n_objects, rtx_object* objects_out, uint32_t cap_objects, uint32_t* n_meshes)
+{
+	if (!s || !n_objects) return fail(RTX_ERR_ARG, "scene/n_objects is NULL");
+	const uint32_t n = s->params.nObjects;
+	*n_objects = n;
+	if (n_meshes) *n_meshes = (uint32_t)s->meshRecs.size();
+	const uint32_t m = std::min(n, cap_objects);
+	if (!m || !objects_out) return RTX_OK;
+	HIPCHK(hipSetDevice(s->device));
+	HIPCHK(hipDeviceSynchronize());
+	std::vector<Object> recs(m);
+	HIPCHK(hipMemcpy(recs.data(), s->params.objects, (size_t)m * sizeof(Object), hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < m; i++) {
+		const Object& d = recs[i];
+		rtx_object& o = objects_out[i];
+		memset(&o, 0, sizeof(o));
+		o.type = d.type; o.material = d.material;
+		memcpy(o.pos, d.pos, 12); memcpy(o.color, d.color, 12); memcpy(o.normal, d.normal, 12);
+		o.ior = d.ior; o.ambient = d.ambient; o.diffuse = d.diffuse; o.specular = d.specular; o.n_specular = d.nSpecular;
+		o.radius2 = d.r2; o.mesh = d.mesh;
+	}
 	return RTX_OK;
 }
 

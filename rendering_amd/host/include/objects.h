@@ -72,7 +72,8 @@ public:
 class Mesh : public Object {
 public:
 	Mesh() { objectType = ObjectType::Mesh; }
-	bool loadOBJ(const std::string& filename, const Options& options);
+	// buildTree = false: `ac` gets its root box only -- the GPU scene builds the structure (Scene::addObject, then treeOnDevice)
+	bool loadOBJ(const std::string& filename, const Options& options, bool buildTree = true);
 	bool loadDiffuseMap(const std::string& filename);
 	bool loadNormalMap(const std::string& filename);
 	bool loadSpecularMap(const std::string& filename);
@@ -99,3 +100,18 @@ public:
 	bool normalMapLoaded = false; int normalMapWidth = 0, normalMapHeight = 0; std::vector<Vec3f> normalMap;
 	bool specularMapLoaded = false; int specularMapWidth = 0, specularMapHeight = 0; std::vector<float> specularMap;
 };
+
+// The values of an [object] block's keys (NULL: the key is absent).  The .scene parser applies every key=value line of a block through
+// applyObjectKeys, and so does Scene::addObject: an added object is the object its block loads.  material, name and the maps are the text
+// of their lines' values ("transparent,1.3"; a file name).
+struct ObjectKeys {
+	const float *pos = nullptr, *size = nullptr, *rot = nullptr, *color = nullptr;      // pos, color: every type; size, rot: mesh
+	const char* material = nullptr;                                                     // every type
+	const float *radius = nullptr, *normal = nullptr;                                   // sphere; plane
+	const char *name = nullptr, *diffuse_map = nullptr, *normal_map = nullptr, *specular_map = nullptr;      // mesh
+};
+std::unique_ptr<Object> makeObject(const std::string& type);       // "plane" / "sphere" / "mesh" (the block's type= line); null otherwise
+const char* objectKeyRefused(ObjectType type, const ObjectKeys& keys);      // the first key given that the type does not have; NULL when all fit
+// Sets the given keys (all of which the type has) in the order pos, size, rot, color, material, radius | normal, name, diffuse_map,
+// normal_map, specular_map: a mesh's OBJ is read and placed with the pos, size and rot set before it, as in a block that names them first.
+void applyObjectKeys(Object& object, const ObjectKeys& keys, const Options& options, bool buildTree = true);

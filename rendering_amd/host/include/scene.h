@@ -87,6 +87,12 @@ public:
 	void setLight(size_t index, const LightKeys& keys);
 	size_t addLight(const std::string& type, const LightKeys& keys);
 	void removeLight(size_t index);
+	// The object list edited as the scene file's [object] blocks would be (objects.h: the keys go through the code the parser applies them
+	// with).  addObject puts a new block's object before object `at` (default: after the last one) and returns its index; an OBJ or a map
+	// that fails to load, a key the type does not have or a bad index is an error and nothing changes.  With a live GPU scene each ends in
+	// one rtx_scene_set_objects (include/rtx_scene_edit.h) that keeps every other mesh as it is; if that fails the objects are put back.
+	size_t addObject(const std::string& type, const ObjectKeys& keys, size_t at = (size_t)-1);
+	void removeObject(size_t index);
 	void syncTrees();                          // meshes moved on the GPU: their `ac` read back from the device (done by every reader of `ac`)
 	// host wall ms of the last moveObject: {placement (Mesh::place), upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
 	double lastMoveMs[4] = { 0, 0, 0, 0 };
@@ -117,6 +123,7 @@ private:
 	void readTimes();
 	void renderAC();
 	void lightsToDevice();
+	void objectsToDevice(const std::vector<const Object*>& before);
 	rtx_scene* gpu_ = nullptr;
 	bool viewDirty_ = true;
 	std::unique_ptr<DeviceFrame> frame_;

@@ -300,6 +300,42 @@ int rah_light_remove(void* h, int index)
 	});
 }
 
+// A new object of RTX_OBJ_* `type` before object `at` (at < 0: after the last one), as a new [object] block with these keys would load
+// (Scene::addObject; NULL = absent, the loader's default): every type pos3 / color3 / material (the text of a material= line), a mesh size3 /
+// rot3 / name / diffuse_map / normal_map / specular_map, a sphere radius1, a plane normal3.  File names resolve against cwd when given, as in
+// rah_scene_load.  Its index, or -1 with rah_last_error (a key the type does not have, an OBJ or a map that cannot be loaded, a bad index,
+// a device error): the scene is then as it was.
+int rah_object_add(void* h, int type, int at, const char* cwd, const float* pos3, const float* size3, const float* rot3, const float* color3,
+                   const char* material, const float* radius1, const float* normal3, const char* name, const char* diffuse_map, const char* normal_map,
+                   const char* specular_map)
+{
+	return guarded<int>(-1, [&]() -> int {
+		const char* kind = type == RTX_OBJ_SPHERE ? "sphere" : type == RTX_OBJ_PLANE ? "plane" : type == RTX_OBJ_MESH ? "mesh" : "?";
+		Scene* s = (Scene*)h;
+		ObjectKeys k;
+		k.pos = pos3; k.size = size3; k.rot = rot3; k.color = color3; k.material = material; k.radius = radius1; k.normal = normal3;
+		k.name = name; k.diffuse_map = diffuse_map; k.normal_map = normal_map; k.specular_map = specular_map;
+		char back[4096];
+		const bool moved = cwd && cwd[0];
+		if (moved && (!getcwd(back, sizeof(back)) || chdir(cwd) != 0)) { noteError("cannot change to the scene's base directory"); LOG_ERROR(); }
+		struct Restore { const char* dir; ~Restore() { if (dir && chdir(dir) != 0) {} } } restore{ moved ? back : nullptr };
+		const bool quiet = options::enableOutput;
+		struct Quiet { bool keep; ~Quiet() { options::enableOutput = keep; } } q{ quiet };
+		options::enableOutput = false;
+		return (int)s->addObject(kind, k, at < 0 ? (size_t)-1 : (size_t)at);
+	});
+}
+
+// Removes object `index` (Scene::removeObject): 0, or -1 with rah_last_error.
+int rah_object_remove(void* h, int index)
+{
+	return guarded<int>(-1, [&] {
+		if (index < 0) { noteError("removeObject: object index out of range"); LOG_ERROR(); }
+		((Scene*)h)->removeObject((size_t)index);
+		return 0;
+	});
+}
+
 // host wall ms of the last rah_object_move: {placement, upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
 void rah_object_move_times(void* h, float* ms4)
 {

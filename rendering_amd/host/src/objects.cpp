@@ -276,7 +276,7 @@ void Mesh::place(const Options& options)
 	}
 }
 
-bool Mesh::loadOBJ(const std::string& filename, const Options& options)
+bool Mesh::loadOBJ(const std::string& filename, const Options& options, bool buildTree)
 {
 	Timer timer("OBJ loading");
 	std::ifstream in(filename);
@@ -386,7 +386,7 @@ bool Mesh::loadOBJ(const std::string& filename, const Options& options)
 		}
 	}
 	place(options);
-	if (!ac->setup(allTris, options)) return false;
+	if (buildTree && !ac->setup(allTris, options)) return false;
 	stats::meshCount += allTris.size();
 	return true;
 }
@@ -443,4 +443,64 @@ bool Mesh::loadSpecularMap(const std::string& filename)
 		specularMap[i] = (c.x + c.y + c.z) / 3.0f;
 	}
 	return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the keys of an [object] block (scene.cpp:270-312)
+// ------------------------------------------------------------------------------------------------
+std::unique_ptr<Object> makeObject(const std::string& type)
+{
+	if (type == "plane") return std::make_unique<Plane>();
+	if (type == "sphere") return std::make_unique<Sphere>();
+	if (type == "mesh") return std::make_unique<Mesh>();
+	return nullptr;
+}
+
+const char* objectKeyRefused(ObjectType type, const ObjectKeys& k)
+{
+	const bool mesh = type == ObjectType::Mesh;
+	if (k.size && !mesh) return "size";
+	if (k.rot && !mesh) return "rot";
+	if (k.radius && type != ObjectType::Sphere) return "radius";
+	if (k.normal && type != ObjectType::Plane) return "normal";
+	if (k.name && !mesh) return "name";
+	if (k.diffuse_map && !mesh) return "diffuse_map";
+	if (k.normal_map && !mesh) return "normal_map";
+	if (k.specular_map && !mesh) return "specular_map";
+	return nullptr;
+}
+
+void applyObjectKeys(Object& o, const ObjectKeys& k, const Options& options, bool buildTree)
+{
+	auto v3 = [](const float* p) { return Vec3f(p[0], p[1], p[2]); };
+	if (k.pos) o.pos = v3(k.pos);
+	if (k.size) static_cast<Mesh&>(o).size = v3(k.size);
+	if (k.rot) static_cast<Mesh&>(o).rot = v3(k.rot);
+	if (k.color) o.color = v3(k.color);
+	if (k.material) {
+		const auto parts = splitString(k.material, ',');
+		if (parts.empty()) LOG_ERROR();
+		if (parts[0] == "transparent") {
+			o.materialType = MaterialType::Transparent;
+			o.indexOfRefraction = strToFloat(parts.at(1));
+		}
+		else if (parts[0] == "reflective") o.materialType = MaterialType::Reflective;
+		else if (parts[0] == "phong") {
+			o.materialType = MaterialType::Phong;
+			o.ambient = strToFloat(parts.at(1)); o.diffuse = strToFloat(parts.at(2));
+			o.specular = strToFloat(parts.at(3)); o.nSpecular = strToFloat(parts.at(4));
+		}
+	}
+	if (k.radius) {
+		auto& s = static_cast<Sphere&>(o);
+		s.r = k.radius[0];
+		s.r2 = s.r * s.r;          // powf(r, 2) is folded to r*r by the reference build (scene.cpp:294)
+	}
+	if (k.normal) static_cast<Plane&>(o).normal = v3(k.normal);
+	if (o.objectType != ObjectType::Mesh) return;
+	auto& m = static_cast<Mesh&>(o);
+	if (k.name) m.loadOBJ(k.name, options, buildTree);
+	if (k.diffuse_map) m.diffuseMapLoaded = m.loadDiffuseMap(k.diffuse_map);
+	if (k.normal_map) m.normalMapLoaded = m.loadNormalMap(k.normal_map);
+	if (k.specular_map) m.specularMapLoaded = m.loadSpecularMap(k.specular_map);
 }

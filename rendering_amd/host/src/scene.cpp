@@ -106,51 +106,38 @@ void parseLight(std::unique_ptr<Light>& light, const KeyValue& kv)
 	applyLightKeys(*light, keys);
 }
 
+// One key=value line of an [object] block: its value goes through applyObjectKeys (objects.h), as an added object's do (Scene::addObject).
+// A key the object's type does not have is skipped, as an unknown one is.
 void parseObject(Scene& sc, std::unique_ptr<Object>& object, const KeyValue& kv)
 {
 	const std::string& k = kv.key; const std::string& v = kv.value;
 	if (k == "type") {
-		if (v == "plane") object = std::make_unique<Plane>();
-		else if (v == "sphere") object = std::make_unique<Sphere>();
-		else if (v == "mesh") object = std::make_unique<Mesh>();
+		if (auto made = makeObject(v)) object = std::move(made);
 		return;
 	}
 	if (!object) { std::cout << "Error, object type missing\n"; return; }
-	if (k == "color") object->color = str3ToFloat(splitString(v, ','));
-	else if (k == "pos") object->pos = str3ToFloat(splitString(v, ','));
-	else if (k == "material") {
-		const auto parts = splitString(v, ',');
-		if (parts.empty()) LOG_ERROR();
-		if (parts[0] == "transparent") {
-			object->materialType = MaterialType::Transparent;
-			object->indexOfRefraction = strToFloat(parts.at(1));
-		}
-		else if (parts[0] == "reflective") object->materialType = MaterialType::Reflective;
-		else if (parts[0] == "phong") {
-			object->materialType = MaterialType::Phong;
-			object->ambient = strToFloat(parts.at(1)); object->diffuse = strToFloat(parts.at(2));
-			object->specular = strToFloat(parts.at(3)); object->nSpecular = strToFloat(parts.at(4));
-		}
+	ObjectKeys keys;
+	Vec3f v3;
+	float f = 0;
+	const float** vec = k == "color" ? &keys.color : k == "pos" ? &keys.pos : k == "normal" ? &keys.normal : k == "size" ? &keys.size : k == "rot" ? &keys.rot : nullptr;
+	const char** text = k == "material" ? &keys.material : k == "name" ? &keys.name : k == "diffuse_map" ? &keys.diffuse_map
+	                    : k == "normal_map" ? &keys.normal_map : k == "specular_map" ? &keys.specular_map : nullptr;
+	if (vec) {
+		*vec = &v3.x;
+		if (objectKeyRefused(object->objectType, keys)) return;
+		v3 = str3ToFloat(splitString(v, ','));
 	}
-	else if (object->objectType == ObjectType::Sphere) {
-		if (k == "radius") {
-			auto& s = static_cast<Sphere&>(*object);
-			s.r = strToFloat(v);
-			s.r2 = s.r * s.r;          // powf(r, 2) is folded to r*r by the reference build (scene.cpp:294)
-		}
+	else if (text) {
+		*text = v.c_str();
+		if (objectKeyRefused(object->objectType, keys)) return;
 	}
-	else if (object->objectType == ObjectType::Plane) {
-		if (k == "normal") static_cast<Plane&>(*object).normal = str3ToFloat(splitString(v, ','));
+	else if (k == "radius") {
+		keys.radius = &f;
+		if (objectKeyRefused(object->objectType, keys)) return;
+		f = strToFloat(v);
 	}
-	else if (object->objectType == ObjectType::Mesh) {
-		auto& m = static_cast<Mesh&>(*object);
-		if (k == "size") m.size = str3ToFloat(splitString(v, ','));
-		else if (k == "rot") m.rot = str3ToFloat(splitString(v, ','));
-		else if (k == "name") m.loadOBJ(v, sc.options);
-		else if (k == "diffuse_map") m.diffuseMapLoaded = m.loadDiffuseMap(v);
-		else if (k == "normal_map") m.normalMapLoaded = m.loadNormalMap(v);
-		else if (k == "specular_map") m.specularMapLoaded = m.loadSpecularMap(v);
-	}
+	else return;
+	applyObjectKeys(*object, keys, sc.options);
 }
 
 // ---- legacy dialect (hardening) ------------------------------------------------
@@ -410,6 +397,46 @@ void flattenLights(LightsVector& lights, std::vector<rtx_light>& out, std::vecto
 
 } // namespace
 
+namespace {
+// A mesh's record in the description, its arrays kept alive in A.  withTree = false: the acceleration structure stays out (the device
+// form of rtx_scene_set_objects builds it from the triangles).
+rtx_mesh flattenMesh(const Mesh& m, FlatScene::MeshArrays& A, bool withTree)
+{
+	rtx_mesh rm{};
+	if (withTree) {
+		const auto& nodes = m.ac->nodes;
+		A.bounds.resize(nodes.size() * 6); A.skip.resize(nodes.size()); A.leafBegin.resize(nodes.size()); A.leafCount.resize(nodes.size());
+		for (size_t i = 0; i < nodes.size(); ++i) {
+			put3(&A.bounds[i * 6], nodes[i].bounds[0]); put3(&A.bounds[i * 6 + 3], nodes[i].bounds[1]);
+			A.skip[i] = nodes[i].skip; A.leafBegin[i] = nodes[i].leafBegin; A.leafCount[i] = nodes[i].leafCount;
+		}
+		rm.n_nodes = (uint32_t)nodes.size(); rm.n_refs = (uint32_t)m.ac->refs.size();
+		rm.node_bounds = A.bounds.data(); rm.node_skip = A.skip.data(); rm.leaf_begin = A.leafBegin.data(); rm.leaf_count = A.leafCount.data();
+		rm.refs = m.ac->refs.data();
+	}
+	const size_t nt = m.allTris.size();
+	A.pos.resize(nt * 9); A.nrm.resize(nt * 9); A.uv.resize(nt * 6); A.tb.resize(nt * 6);
+	for (size_t i = 0; i < nt; ++i) {
+		const Triangle& t = m.allTris[i];
+		put3(&A.pos[i * 9], t.a); put3(&A.pos[i * 9 + 3], t.b); put3(&A.pos[i * 9 + 6], t.c);
+		put3(&A.nrm[i * 9], t.n_a); put3(&A.nrm[i * 9 + 3], t.n_b); put3(&A.nrm[i * 9 + 6], t.n_c);
+		A.uv[i * 6] = t.t_a.x; A.uv[i * 6 + 1] = t.t_a.y; A.uv[i * 6 + 2] = t.t_b.x; A.uv[i * 6 + 3] = t.t_b.y;
+		A.uv[i * 6 + 4] = t.t_c.x; A.uv[i * 6 + 5] = t.t_c.y;
+		put3(&A.tb[i * 6], t.tangent); put3(&A.tb[i * 6 + 3], t.bitangent);
+	}
+	rm.n_tris = (uint32_t)nt;
+	rm.tri_pos = A.pos.data(); rm.tri_nrm = A.nrm.data(); rm.tri_uv = A.uv.data(); rm.tri_tb = A.tb.data();
+	auto flat3 = [](const std::vector<Vec3f>& src, std::vector<float>& dst) {
+		dst.resize(src.size() * 3);
+		for (size_t i = 0; i < src.size(); ++i) put3(&dst[i * 3], src[i]);
+	};
+	if (m.diffuseMapLoaded) { flat3(m.diffuseMap, A.diffuse); rm.diffuse_w = m.diffuseMapWidth; rm.diffuse_h = m.diffuseMapHeight; rm.diffuse_map = A.diffuse.data(); }
+	if (m.normalMapLoaded) { flat3(m.normalMap, A.normal); rm.normal_w = m.normalMapWidth; rm.normal_h = m.normalMapHeight; rm.normal_map = A.normal.data(); }
+	if (m.specularMapLoaded) { rm.specular_w = m.specularMapWidth; rm.specular_h = m.specularMapHeight; rm.specular_map = m.specularMap.data(); }
+	return rm;
+}
+} // namespace
+
 FlatScene* flattenScene(Scene& sc)
 {
 	sc.syncTrees();
@@ -422,36 +449,7 @@ FlatScene* flattenScene(Scene& sc)
 			const Mesh& m = static_cast<const Mesh&>(o);
 			if (!m.ac) { std::cout << "Mesh without acceleration structure (OBJ failed to load)\n"; LOG_ERROR(); }
 			fs->meshArrays.push_back(std::make_unique<FlatScene::MeshArrays>());
-			auto& A = *fs->meshArrays.back();
-			const auto& nodes = m.ac->nodes;
-			A.bounds.resize(nodes.size() * 6); A.skip.resize(nodes.size()); A.leafBegin.resize(nodes.size()); A.leafCount.resize(nodes.size());
-			for (size_t i = 0; i < nodes.size(); ++i) {
-				put3(&A.bounds[i * 6], nodes[i].bounds[0]); put3(&A.bounds[i * 6 + 3], nodes[i].bounds[1]);
-				A.skip[i] = nodes[i].skip; A.leafBegin[i] = nodes[i].leafBegin; A.leafCount[i] = nodes[i].leafCount;
-			}
-			const size_t nt = m.allTris.size();
-			A.pos.resize(nt * 9); A.nrm.resize(nt * 9); A.uv.resize(nt * 6); A.tb.resize(nt * 6);
-			for (size_t i = 0; i < nt; ++i) {
-				const Triangle& t = m.allTris[i];
-				put3(&A.pos[i * 9], t.a); put3(&A.pos[i * 9 + 3], t.b); put3(&A.pos[i * 9 + 6], t.c);
-				put3(&A.nrm[i * 9], t.n_a); put3(&A.nrm[i * 9 + 3], t.n_b); put3(&A.nrm[i * 9 + 6], t.n_c);
-				A.uv[i * 6] = t.t_a.x; A.uv[i * 6 + 1] = t.t_a.y; A.uv[i * 6 + 2] = t.t_b.x; A.uv[i * 6 + 3] = t.t_b.y;
-				A.uv[i * 6 + 4] = t.t_c.x; A.uv[i * 6 + 5] = t.t_c.y;
-				put3(&A.tb[i * 6], t.tangent); put3(&A.tb[i * 6 + 3], t.bitangent);
-			}
-			rtx_mesh rm{};
-			rm.n_nodes = (uint32_t)nodes.size(); rm.n_refs = (uint32_t)m.ac->refs.size(); rm.n_tris = (uint32_t)nt;
-			rm.node_bounds = A.bounds.data(); rm.node_skip = A.skip.data(); rm.leaf_begin = A.leafBegin.data(); rm.leaf_count = A.leafCount.data();
-			rm.refs = m.ac->refs.data();
-			rm.tri_pos = A.pos.data(); rm.tri_nrm = A.nrm.data(); rm.tri_uv = A.uv.data(); rm.tri_tb = A.tb.data();
-			auto flat3 = [](const std::vector<Vec3f>& src, std::vector<float>& dst) {
-				dst.resize(src.size() * 3);
-				for (size_t i = 0; i < src.size(); ++i) put3(&dst[i * 3], src[i]);
-			};
-			if (m.diffuseMapLoaded) { flat3(m.diffuseMap, A.diffuse); rm.diffuse_w = m.diffuseMapWidth; rm.diffuse_h = m.diffuseMapHeight; rm.diffuse_map = A.diffuse.data(); }
-			if (m.normalMapLoaded) { flat3(m.normalMap, A.normal); rm.normal_w = m.normalMapWidth; rm.normal_h = m.normalMapHeight; rm.normal_map = A.normal.data(); }
-			if (m.specularMapLoaded) { rm.specular_w = m.specularMapWidth; rm.specular_h = m.specularMapHeight; rm.specular_map = m.specularMap.data(); }
-			fs->meshes.push_back(rm);
+			fs->meshes.push_back(flattenMesh(m, *fs->meshArrays.back(), true));
 		}
 		fs->objects.push_back(ro);
 	}
@@ -703,6 +701,93 @@ void Scene::removeLight(size_t index)
 	lights.erase(lights.begin() + (std::ptrdiff_t)index);
 	try { lightsToDevice(); }
 	catch (...) { lights.insert(lights.begin() + (std::ptrdiff_t)index, std::move(keep)); throw; }
+}
+
+// The objects as the device should hold them now: one rtx_scene_set_objects (nothing to do before the GPU scene exists: it is created from
+// the edited objects).  `before`: the objects in the device's order -- every mesh among them is kept, under its index there; a mesh that is
+// not among them is new, and its placed triangles go up in the layout moveObjectApply uploads for the device to build the structure from.
+void Scene::objectsToDevice(const std::vector<const Object*>& before)
+{
+	if (!gpu_) return;
+	std::vector<std::pair<const Object*, int32_t>> oldMesh;
+	for (const Object* o : before)
+		if (o->objectType == ObjectType::Mesh) oldMesh.emplace_back(o, (int32_t)oldMesh.size());
+	std::vector<rtx_object> recs;
+	std::vector<rtx_mesh_source> srcs;
+	// (at most one mesh is new: its description, its triangles on the device)
+	FlatScene::MeshArrays A;
+	rtx_mesh rm{};
+	rtx_mesh_build build{};
+	Mesh* fresh = nullptr;
+	for (auto& op : objects) {
+		recs.push_back(objectRecord(*op, (int32_t)srcs.size()));
+		if (op->objectType != ObjectType::Mesh) continue;
+		rtx_mesh_source src{};
+		src.keep = -1;
+		for (const auto& om : oldMesh) if (om.first == op.get()) src.keep = om.second;
+		if (src.keep < 0) {
+			if (fresh) { noteError("objectsToDevice: more than one new mesh"); LOG_ERROR(); }
+			fresh = static_cast<Mesh*>(op.get());
+			src.mesh = &rm;
+		}
+		srcs.push_back(src);
+	}
+	float* dev = nullptr;
+	bool onDevice = false;
+	if (fresh) {
+		onDevice = !fresh->allTris.empty() && fresh->ac->nodes.empty();
+		rm = flattenMesh(*fresh, A, !onDevice);
+		if (onDevice) {
+			const size_t nt = fresh->allTris.size();
+			hipCheck(hipSetDevice(device), "hipSetDevice");
+			hipCheck(hipMalloc((void**)&dev, nt * 24 * sizeof(float)), "hipMalloc");
+			hipError_t e = hipMemcpy(dev, A.pos.data(), nt * 9 * sizeof(float), hipMemcpyHostToDevice);
+			if (e == hipSuccess) e = hipMemcpy(dev + nt * 9, A.nrm.data(), nt * 9 * sizeof(float), hipMemcpyHostToDevice);
+			if (e == hipSuccess) e = hipMemcpy(dev + nt * 18, A.tb.data(), nt * 6 * sizeof(float), hipMemcpyHostToDevice);
+			if (e != hipSuccess) { (void)hipFree(dev); hipCheck(e, "hipMemcpy"); }
+			build.tri_pos_dev = dev; build.tri_nrm_dev = dev + nt * 9; build.tri_tb_dev = dev + nt * 18;
+			put3(build.root_lo, fresh->ac->rootBounds[0]); put3(build.root_hi, fresh->ac->rootBounds[1]);
+			build.ac_penalty = options.acPenalty;
+			for (auto& src : srcs) if (src.mesh == &rm) src.build = &build;
+		}
+	}
+	const int rc = rtx_scene_set_objects(gpu_, (uint32_t)recs.size(), recs.data(), (uint32_t)srcs.size(), srcs.data(), nullptr);
+	if (dev) (void)hipFree(dev);
+	gpuCheck(rc, "rtx_scene_set_objects");
+	if (onDevice) { fresh->treeOnDevice = true; fresh->ac->builtOnDevice = true; }
+}
+
+size_t Scene::addObject(const std::string& type, const ObjectKeys& keys, size_t at)
+{
+	std::unique_ptr<Object> object = makeObject(type);
+	if (!object) { noteError("addObject: unknown object type " + type); LOG_ERROR(); }
+	if (at == (size_t)-1) at = objects.size();
+	if (at > objects.size()) { noteError("addObject: object index out of range"); LOG_ERROR(); }
+	if (const char* bad = objectKeyRefused(object->objectType, keys)) { noteError("addObject: a " + type + " has no key " + bad); LOG_ERROR(); }
+	// (with a live GPU scene the device builds a new mesh's structure from its placed triangles)
+	applyObjectKeys(*object, keys, options, !gpu_);
+	if (object->objectType == ObjectType::Mesh) {
+		auto& m = static_cast<Mesh&>(*object);
+		if (!m.ac) { noteError(std::string("addObject: the mesh's OBJ could not be loaded: ") + (keys.name ? keys.name : "(no name)")); LOG_ERROR(); }
+		if (gpu_ && m.allTris.empty() && !m.ac->setup(m.allTris, options)) { noteError("addObject: the acceleration structure could not be built"); LOG_ERROR(); }
+	}
+	std::vector<const Object*> before;
+	for (auto& op : objects) before.push_back(op.get());
+	objects.insert(objects.begin() + (std::ptrdiff_t)at, std::move(object));
+	try { objectsToDevice(before); }
+	catch (...) { objects.erase(objects.begin() + (std::ptrdiff_t)at); throw; }
+	return at;
+}
+
+void Scene::removeObject(size_t index)
+{
+	if (index >= objects.size()) { noteError("removeObject: object index out of range"); LOG_ERROR(); }
+	std::vector<const Object*> before;
+	for (auto& op : objects) before.push_back(op.get());
+	std::unique_ptr<Object> keep = std::move(objects[index]);
+	objects.erase(objects.begin() + (std::ptrdiff_t)index);
+	try { objectsToDevice(before); }
+	catch (...) { objects.insert(objects.begin() + (std::ptrdiff_t)index, std::move(keep)); throw; }
 }
 
 void Scene::syncTrees()
