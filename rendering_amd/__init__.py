@@ -49,6 +49,14 @@ RTX_EDIT_SYMBOLS = ["rtx_scene_set_object", "rtx_scene_update_mesh", "rtx_scene_
 # the extension of include/rtx_query.h: queries on a loaded scene that render nothing (not part of the drop-in boundary)
 RTX_QUERY_SYMBOLS = ["rtx_occluded_rays"]
 
+# the extension of include/rtx_aov.h: first-hit buffers of a frame (not part of the drop-in boundary)
+RTX_AOV_SYMBOLS = ["rtx_render_aov"]
+
+
+class AovBuffers(C.Structure):
+    """rtx_aov_buffers (include/rtx_aov.h): six device pointers, any of them NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("depth_dev", "object_dev", "triangle_dev", "uv_dev", "normal_dev", "albedo_dev")]
+
 
 def load():
     """Loads the native libraries (raises RtxError when they have not been built: run ./build.sh)."""
@@ -91,6 +99,7 @@ def load():
     rtx.rtx_cast_rays.argtypes = [vp, u32, vp, vp, vp]
     rtx.rtx_trace_rays.argtypes = [vp, u32, vp, vp, vp, vp]
     rtx.rtx_occluded_rays.argtypes = [vp, u32, vp, vp, vp, vp]
+    rtx.rtx_render_aov.argtypes = [vp, u32, u32, C.POINTER(AovBuffers), vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -169,7 +178,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -860,6 +869,42 @@ class Scene:
                                           C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
                "rtx_occluded_rays")
         return out
+
+    def render_aov(self, depth=None, object_id=None, triangle_id=None, uv=None, normal=None, albedo=None, rows=None, stream=None):
+        """rtx_render_aov: what the primary ray of every pixel of pass 1 met, written into the device tensors that are given (any subset,
+        at least one): depth float32 (H, W), object_id and triangle_id int32 (H, W), uv float32 (H, W, 2), normal and albedo float32
+        (H, W, 3) -- contiguous, on this scene's device.  Written: the pixels x < W-1, y < H-1 of rows [r0, r1) that this part owns;
+        nothing else of a tensor is touched.  A miss: depth FLT_MAX, ids -1, uv (-1, -1), normal 0, albedo the sky / background colour.
+        Asynchronous on `stream` (None: torch's current stream of the scene's device); with a torch.cuda.Stream the tensors are
+        recorded on it."""
+        import torch
+        given = (("depth", depth, torch.float32, ()), ("object_id", object_id, torch.int32, ()), ("triangle_id", triangle_id, torch.int32, ()),
+                 ("uv", uv, torch.float32, (2,)), ("normal", normal, torch.float32, (3,)), ("albedo", albedo, torch.float32, (3,)))
+        if all(t is None for _, t, _, _ in given):
+            raise ValueError("render_aov: nothing to compute (at least one buffer is needed)")
+        for name, t, dtype, tail in given:
+            if t is None:
+                continue
+            shape = (self.height, self.width) + tail
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("render_aov: %s must be a torch tensor, got %s" % (name, type(t).__name__))
+            if t.dtype != dtype:
+                raise ValueError("render_aov: %s must be %s, got %s" % (name, str(dtype).replace("torch.", ""), t.dtype))
+            if tuple(t.shape) != shape:
+                raise ValueError("render_aov: %s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if not t.is_contiguous():
+                raise ValueError("render_aov: %s must be contiguous" % name)
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError("render_aov: %s must be on cuda:%d, the scene's device, got %s" % (name, self.device, t.device))
+        r0, r1 = rows if rows is not None else (0, self.height)
+        if isinstance(stream, torch.cuda.Stream):
+            for _, t, _, _ in given:
+                if t is not None:
+                    t.record_stream(stream)
+        bufs = AovBuffers(*[t.data_ptr() if t is not None else None for _, t, _, _ in given])
+        _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(bufs),
+                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
+               "rtx_render_aov")
 
     def device_mesh(self, mesh):
         """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,

@@ -1,0 +1,63 @@
+// First-hit buffers of a frame (rtx_render_aov, include/rtx_aov.h): for every pixel of pass 1 the channels of
+// Render::trace of its primary ray and of getSurfaceData at the hit -- depth, object id, triangle id, uv, normal, albedo.
+//
+// A kernel of its own after the pattern of rtxNormalsKernel's mode 0: one 8x8 tile per wave over a plain grid, the pixel's ray from
+// primaryRay (never stored), traceWave in its trace-only form with source class 1 (the camera's copies of the prune records, which only
+// rays that start at view.camPos may use).  No state machine, no park area, no recursion frames, no queue.
+// SURFACE = false: only the hit record is written; shadePrimary and its fetches (uv, normals, tangents, maps) are not compiled in, which
+// keeps the kernel in the register class of rtxRayHitKernel.  SURFACE = true: shadePrimary's N and objColor are written as well.
+#pragma clang fp contract(off)
+
+template <bool MESH, bool BOXES, int CULLK, bool SURFACE>
+__global__ void __launch_bounds__(256) rtxAovKernel(const Params P, const rtx_aov_buffers out)
+{
+	const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
+	if (wave >= P.nTiles) return;
+	const uint32_t W = P.view.width, H = P.view.height;
+	const uint32_t tx = wave % P.tilesX, ty = P.tileRow0 + wave / P.tilesX;
+	const uint32_t x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+	// pass 1's pixels of the rows this part owns (no halo rows: nothing here looks at a neighbour)
+	const bool valid = x < W - 1 && y < H - 1 && y >= P.rowBegin && y < P.rowEnd && rowOwned(P.bandH, P.nParts, P.part, y);
+	if (ballot(valid) == 0) return;
+	V3 o, d;
+	primaryRay(P, (float)x + 0.5f, (float)y + 0.5f, o, d);
+	Hit h;
+	Counts cnt = {};
+	traceWave<false, MESH, false, BOXES, CULLK>(P, valid, false, o, d, kFltMax, h, cnt, 1u);
+	if (!valid) return;
+	// The stores of one channel stay together: a tile row's eight lanes write 32 (depth, ids), 64 (uv) or 96 (normal, albedo) consecutive
+	// bytes, eight such runs per instruction.
+	const size_t i = (size_t)y * W + x;
+	const bool hit = h.obj >= 0;
+	if (out.depth_dev) out.depth_dev[i] = h.t;      // (a miss keeps the range it started with: FLT_MAX)
+	if (out.object_dev) out.object_dev[i] = hit ? h.obj : -1;
+	if (out.triangle_dev) {
+		// rtx_cast_rays' record: the triangle of a mesh only (a sphere's or a plane's h.tri is whatever an earlier mesh left)
+		const bool mesh = hit && P.objects[hit ? h.obj : 0].type == 3;
+		out.triangle_dev[i] = mesh ? (int32_t)h.tri : -1;
+	}
+	if (out.uv_dev) { float* p = out.uv_dev + i * 2; p[0] = hit ? h.u : -1.f; p[1] = hit ? h.v : -1.f; }
+	if (SURFACE) {
+		V3 n = mk(0, 0, 0), a;
+		if (hit) {
+			Lane s;
+			s.ro = o; s.rd = d;
+			shadePrimary(P, s, h);      // (only the lanes that hit are here: its loop is over their objects)
+			n = s.N; a = s.objColor;
+		}
+		else a = skyColor(P, d);
+		if (out.normal_dev) { float* p = out.normal_dev + i * 3; p[0] = n.x; p[1] = n.y; p[2] = n.z; }
+		if (out.albedo_dev) { float* p = out.albedo_dev + i * 3; p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+	}
+}
+
+// per (box test of the prune records, culling) like the other trace-only kernels, each with and without the surface fetch; scenes without
+// meshes have the walk-free form
+#define RTX_AOV_INSTANCES(S)                                                                     \
+template __global__ void rtxAovKernel<true, true, 1, S>(const Params, const rtx_aov_buffers);   \
+template __global__ void rtxAovKernel<true, false, 1, S>(const Params, const rtx_aov_buffers);  \
+template __global__ void rtxAovKernel<true, true, 0, S>(const Params, const rtx_aov_buffers);   \
+template __global__ void rtxAovKernel<true, false, 0, S>(const Params, const rtx_aov_buffers);  \
+template __global__ void rtxAovKernel<false, true, -1, S>(const Params, const rtx_aov_buffers);
+RTX_AOV_INSTANCES(false) RTX_AOV_INSTANCES(true)
+#undef RTX_AOV_INSTANCES

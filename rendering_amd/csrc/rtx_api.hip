@@ -19,6 +19,7 @@
 #include "../../include/rtx_debug.h"
 #include "../../include/rtx_scene_edit.h"
 #include "../../include/rtx_query.h"
+#include "../../include/rtx_aov.h"
 #include "rtx_device.h"
 #include "rtx_own.h"
 
@@ -29,6 +30,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_kernels.hip"
 #include "rtx_source.hip"
 #include "rtx_rays.hip"
+#include "rtx_aov.hip"
 
 // rtx_sort.hip
 hipError_t rtxSortRayKeys(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, uint32_t* order, uint32_t n, int endBit,
@@ -363,6 +365,13 @@ RayKernel rayColourKernel(const Variant& v)
 {
 	if (v.analytic) return rtxRayColourKernel<false, true, -1, false>;
 	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> RayKernel { return rtxRayColourKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+// (surface: the normal or the albedo is asked for -- only then is shadePrimary part of the kernel)
+typedef void (*AovKernel)(const Params, const rtx_aov_buffers);
+AovKernel aovKernel(const Variant& v, bool surface)
+{
+	if (v.analytic) return surface ? rtxAovKernel<false, true, -1, true> : rtxAovKernel<false, true, -1, false>;
+	return dispatchVariant(v.boxes, v.cull, surface, [](auto b, auto c, auto sf) -> AovKernel { return rtxAovKernel<true, decltype(b)::value, decltype(c)::value, decltype(sf)::value>; });
 }
 // (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
 typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
@@ -2408,6 +2417,36 @@ int rtx_occluded_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const flo
 	const uint32_t waves = (n + 63) / 64;
 	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
 	hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, tmax_dev, occluded_dev);
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_render_aov(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_aov_buffers* out, void* stream)
+{
+	RoctxRange range("First-hit buffers (rtx_render_aov)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	if (!out->depth_dev && !out->object_dev && !out->triangle_dev && !out->uv_dev && !out->normal_dev && !out->albedo_dev)
+		return fail(RTX_ERR_ARG, "rtx_render_aov: no output (all six buffers are NULL)");
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_aov collects no statistics (rtx_counters_enable)");
+	const uint32_t W = s->params.view.width, H = s->params.view.height;
+	if (rowEnd > H) rowEnd = H;
+	if (rowBegin >= rowEnd) return RTX_OK;
+	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
+	if (lastRow <= rowBegin) return RTX_OK;
+	HIPCHK(hipSetDevice(s->device));
+	hipStream_t st = (hipStream_t)stream;
+	if (int ro = renderOn(s, st)) return ro;
+	// A plain grid over the tiles, as the normals view: neither the tile lists nor the tile costs are read or written, and no event is
+	// recorded (rtx_last_kernel_ms and the frame-mode measurements keep what the ordinary frames left).
+	Params p = s->params;
+	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
+	p.tilesX = (W - 1 + 7) / 8;
+	p.tileRow0 = rowBegin / 8;
+	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
+	if (tiles >= (1u << 30)) return fail(RTX_ERR_ARG, "frame too large");
+	p.nTiles = (uint32_t)tiles;
+	const bool surface = out->normal_dev || out->albedo_dev;
+	hipLaunchKernelGGL(aovKernel(variantOf(s), surface), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, *out);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

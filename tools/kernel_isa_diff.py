@@ -1,6 +1,7 @@
 """Which kernels' machine code differs between two builds: the device assembly build.sh keeps (build/*-hip-amdgcn-amd-amdhsa-gfx950.s),
 normalised as tools/device_code_hash.sh does (comments and blank lines dropped, the compilation unit's id replaced by a constant), cut at the
-labels of the functions and hashed per function.  A change meant for some kernels must leave every other one as it was.
+labels of the functions and hashed per function.  A function's number within its unit, which its local labels carry (.LBB<number>_<block>) and
+which moves when kernels are added in front of it, is replaced by a constant too.  A change meant for some kernels must leave every other one as it was.
   python tools/kernel_isa_diff.py <build directory of the parent> [build directory, default: build]"""
 import hashlib
 import os
@@ -16,6 +17,7 @@ def functions(path):
     for ln in open(path):
         ln = re.sub(r"[ \t]*;.*$", "", ln.rstrip("\n"))
         ln = re.sub(r"__hip_cuid_[0-9a-f]*", "__hip_cuid_X", ln)
+        ln = re.sub(r"\.LBB\d+_", ".LBBn_", ln)
         if not ln.strip():
             continue
         m = re.match(r"^(_Z\w+):$", ln)
