@@ -17,7 +17,7 @@ ROOT = os.path.dirname(HERE)
 LIB_RTX = os.path.join(HERE, "librtx_hip.so")
 LIB_HOST = os.path.join(HERE, "librendering_host.so")
 
-__all__ = ["load", "Scene", "Comm", "RtxError", "device_count", "math_probe", "gather_plan", "exported_symbols"]
+__all__ = ["load", "Scene", "Comm", "RtxError", "device_count", "math_probe", "gather_plan", "exported_symbols", "sphere_directions"]
 
 
 class RtxError(RuntimeError):
@@ -53,9 +53,34 @@ RTX_QUERY_SYMBOLS = ["rtx_occluded_rays"]
 RTX_AOV_SYMBOLS = ["rtx_render_aov"]
 
 
+# the extension of include/rtx_ao.h: ambient occlusion of a frame (not part of the drop-in boundary)
+RTX_AO_SYMBOLS = ["rtx_render_ao"]
+
+
 class AovBuffers(C.Structure):
     """rtx_aov_buffers (include/rtx_aov.h): six device pointers, any of them NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth_dev", "object_dev", "triangle_dev", "uv_dev", "normal_dev", "albedo_dev")]
+
+
+class AoParams(C.Structure):
+    """rtx_ao_params (include/rtx_ao.h)"""
+    _fields_ = [("n_dirs", C.c_uint32), ("dirs_dev", C.c_void_p), ("radius", C.c_float)]
+
+
+def sphere_directions(n):
+    """n directions (n even) as float32 (n, 3): the first n / 2 are the upper half of a Fibonacci spiral over the sphere --
+    z = 1 - 2 (i + 0.5) / n, phi = (i + 0.5) pi (3 - sqrt 5), (r cos phi, r sin phi, z) with r = sqrt(1 - z^2), in float64 rounded to
+    float32 --, the others their negatives: an antipodal set, of which every surface point has about n / 2 on the side of its normal
+    (Scene.render_ao)."""
+    n = int(n)
+    if n < 2 or n % 2:
+        raise ValueError("sphere_directions: n must be even and at least 2, got %d" % n)
+    i = np.arange(n // 2, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * i / n
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(1.0 - z * z)
+    half = np.stack([r * np.cos(phi), r * np.sin(phi), z], 1).astype(np.float32)
+    return np.concatenate([half, -half], 0)
 
 
 def load():
@@ -100,6 +125,7 @@ def load():
     rtx.rtx_trace_rays.argtypes = [vp, u32, vp, vp, vp, vp]
     rtx.rtx_occluded_rays.argtypes = [vp, u32, vp, vp, vp, vp]
     rtx.rtx_render_aov.argtypes = [vp, u32, u32, C.POINTER(AovBuffers), vp]
+    rtx.rtx_render_ao.argtypes = [vp, u32, u32, C.POINTER(AoParams), vp, vp, vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -178,7 +204,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -905,6 +931,45 @@ class Scene:
         _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(bufs),
                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
                "rtx_render_aov")
+
+    def render_ao(self, dirs, radius=float("inf"), ao=None, counts=None, rows=None, stream=None):
+        """rtx_render_ao: ambient occlusion of the frame in one launch.  For every pixel of pass 1 whose primary ray hits, each direction
+        of `dirs` (float32 (K, 3), K in 1 .. 256, world space, used as stored) with N . d > 0 is traced from P + N * bias with the rule of
+        occluded() and the range `radius` (> 0; inf: the whole ray; the library refuses anything else, and K outside 1 .. 256).
+        ao, float32 (H, W): open / traced, 1.0 where nothing was traced or hit; counts, int32 (H, W): open | traced << 16.  At least
+        one of the two is given; all tensors are contiguous and on this scene's device.  Written: the pixels x < W-1, y < H-1 of rows [r0, r1) that this part owns; nothing else of a tensor is touched.
+        Asynchronous on `stream` (None: torch's current stream of the scene's device); with a torch.cuda.Stream the tensors are
+        recorded on it."""
+        import torch
+        given = (("dirs", dirs, torch.float32), ("ao", ao, torch.float32), ("counts", counts, torch.int32))
+        if ao is None and counts is None:
+            raise ValueError("render_ao: nothing to compute (at least one buffer is needed)")
+        for name, t, dtype in given:
+            if t is None and name != "dirs":
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("render_ao: %s must be a torch tensor, got %s" % (name, type(t).__name__))
+            if t.dtype != dtype:
+                raise ValueError("render_ao: %s must be %s, got %s" % (name, str(dtype).replace("torch.", ""), t.dtype))
+            if name == "dirs":
+                if t.dim() != 2 or t.shape[1] != 3:
+                    raise ValueError("render_ao: dirs must have shape (K, 3), got %s" % (tuple(t.shape),))
+            elif tuple(t.shape) != (self.height, self.width):
+                raise ValueError("render_ao: %s must have shape %s, got %s" % (name, (self.height, self.width), tuple(t.shape)))
+            if not t.is_contiguous():
+                raise ValueError("render_ao: %s must be contiguous" % name)
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError("render_ao: %s must be on cuda:%d, the scene's device, got %s" % (name, self.device, t.device))
+        r0, r1 = rows if rows is not None else (0, self.height)
+        if isinstance(stream, torch.cuda.Stream):
+            for _, t, _ in given:
+                if t is not None:
+                    t.record_stream(stream)
+        par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
+        _check(self.rtx.rtx_render_ao(self.gpu(), r0, r1, C.byref(par), C.c_void_p(ao.data_ptr()) if ao is not None else None,
+                                      C.c_void_p(counts.data_ptr()) if counts is not None else None,
+                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
+               "rtx_render_ao")
 
     def device_mesh(self, mesh):
         """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,

@@ -20,6 +20,7 @@
 #include "../../include/rtx_scene_edit.h"
 #include "../../include/rtx_query.h"
 #include "../../include/rtx_aov.h"
+#include "../../include/rtx_ao.h"
 #include "rtx_device.h"
 #include "rtx_own.h"
 
@@ -31,6 +32,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_source.hip"
 #include "rtx_rays.hip"
 #include "rtx_aov.hip"
+#include "rtx_ao.hip"
 
 // rtx_sort.hip
 hipError_t rtxSortRayKeys(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, uint32_t* order, uint32_t n, int endBit,
@@ -372,6 +374,12 @@ AovKernel aovKernel(const Variant& v, bool surface)
 {
 	if (v.analytic) return surface ? rtxAovKernel<false, true, -1, true> : rtxAovKernel<false, true, -1, false>;
 	return dispatchVariant(v.boxes, v.cull, surface, [](auto b, auto c, auto sf) -> AovKernel { return rtxAovKernel<true, decltype(b)::value, decltype(c)::value, decltype(sf)::value>; });
+}
+typedef void (*AoKernel)(const Params, const AoArgs);
+AoKernel aoKernel(const Variant& v)
+{
+	if (v.analytic) return rtxAoKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> AoKernel { return rtxAoKernel<true, decltype(b)::value, decltype(c)::value>; });
 }
 // (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
 typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
@@ -2447,6 +2455,38 @@ int rtx_render_aov(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_a
 	p.nTiles = (uint32_t)tiles;
 	const bool surface = out->normal_dev || out->albedo_dev;
 	hipLaunchKernelGGL(aovKernel(variantOf(s), surface), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, *out);
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_render_ao(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_ao_params* par, float* ao, uint32_t* counts, void* stream)
+{
+	RoctxRange range("Ambient occlusion (rtx_render_ao)");
+	if (!s || !par) return fail(RTX_ERR_ARG, "scene/params is NULL");
+	if (!ao && !counts) return fail(RTX_ERR_ARG, "rtx_render_ao: no output (both buffers are NULL)");
+	if (!par->dirs_dev) return fail(RTX_ERR_ARG, "rtx_render_ao: dirs_dev is NULL");
+	if (par->n_dirs < 1 || par->n_dirs > 256) return fail(RTX_ERR_ARG, "rtx_render_ao: n_dirs must be 1 .. 256");
+	if (!(par->radius > 0)) return fail(RTX_ERR_ARG, "rtx_render_ao: radius must be > 0 (+inf: the whole ray)");
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_ao collects no statistics (rtx_counters_enable)");
+	const uint32_t W = s->params.view.width, H = s->params.view.height;
+	if (rowEnd > H) rowEnd = H;
+	if (rowBegin >= rowEnd) return RTX_OK;
+	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
+	if (lastRow <= rowBegin) return RTX_OK;
+	HIPCHK(hipSetDevice(s->device));
+	hipStream_t st = (hipStream_t)stream;
+	if (int ro = renderOn(s, st)) return ro;
+	// rtx_render_aov's launch: a plain grid over the tiles; neither the tile lists nor the tile costs are read or written, and no event
+	// is recorded
+	Params p = s->params;
+	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
+	p.tilesX = (W - 1 + 7) / 8;
+	p.tileRow0 = rowBegin / 8;
+	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
+	if (tiles >= (1u << 30)) return fail(RTX_ERR_ARG, "frame too large");
+	p.nTiles = (uint32_t)tiles;
+	const AoArgs a = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
+	hipLaunchKernelGGL(aoKernel(variantOf(s)), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, a);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
