@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from tests import util_occlusion as OC
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -256,6 +258,17 @@ def matrix_reference(oracle, ra, path, key):
     return _matrix_oracle[key]
 
 
+def occlusion_ranges(hit, tnear):
+    """The ranges the margin rays are asked with as occlusion queries: none (the whole ray), +inf, every ray's own nearest hit and its
+    neighbours (util_occlusion.tmax_mix: t, nextafter(t, +-), 0.5 t, 1.5 t, +inf), and FLT_MAX, +inf, NaN, 0 and 1e-30 in turn within every
+    wave -- a lane with an unbounded range then shares its bundle's largest range with lanes that can see nothing."""
+    n = len(tnear)
+    turn = np.array([OC.FLT_MAX, np.inf, np.nan, 0.0, 1e-30], f32)[(np.arange(n) % 64) % 5]
+    mix = OC.tmax_mix(hit, tnear)
+    assert (hit & (mix == tnear)).sum() > 10 and (hit & (mix < tnear)).sum() > 10 and (hit & (mix > tnear)).sum() > 10
+    return [("none", None), ("+inf", float("inf")), ("mix", mix), ("FLT_MAX / +inf / NaN / 0 / 1e-30 in turn", np.ascontiguousarray(turn))]
+
+
 @pytest.mark.parametrize("scene,plain,boxes,cull", MATRIX)
 def test_variant_matrix_rays_and_frames(ra, oracle, tmp_path, scene, plain, boxes, cull):
     """The margin rays through rtx_trace_rays (trace_reorder 0: a wave of 64 stays the bundle it was built as) and frames in one and in
@@ -275,6 +288,20 @@ def test_variant_matrix_rays_and_frames(ra, oracle, tmp_path, scene, plain, boxe
     assert not bad.any(), "%d of %d rays differ, first %d: ray %s oracle %s %s gpu %s %s" % (
         int(bad.sum()), len(rays), int(np.argmax(bad)), rays[np.argmax(bad)], rh[np.argmax(bad)], rc[np.argmax(bad)], gh[np.argmax(bad)], gc[np.argmax(bad)])
     assert (rh[:, 0] >= 0).sum() > len(rays) // 50
+    # the same rays as occlusion queries (rtxRayOccludedKernel: the one entry point with a range per ray, walked in shadow mode under the
+    # wave's largest range): no object here is Transparent, so the oracle's records above say what is occluded
+    hit, tnear = rh[:, 0] > 0, rh[:, 3].astype(f32)
+    assert hit.sum() > len(rays) // 50
+    rays_dev = torch.from_numpy(rays).cuda()
+    for label, tmax in occlusion_ranges(hit, tnear):
+        arg = torch.from_numpy(tmax).cuda() if isinstance(tmax, np.ndarray) else tmax
+        got = g.occluded(rays_dev, arg)
+        torch.cuda.synchronize()
+        want = OC.expected(hit, tnear, f32(np.inf) if tmax is None else tmax)
+        bad = got.cpu().numpy() != want
+        assert not bad.any(), "occluded, ranges %s: %d of %d rays differ, first %d: ray %s oracle %s range %r" % (
+            label, int(bad.sum()), len(rays), int(np.argmax(bad)), rays[np.argmax(bad)], rh[np.argmax(bad)],
+            np.broadcast_to(np.asarray(np.inf if tmax is None else tmax, f32), tnear.shape)[np.argmax(bad)])
     for mode in (1, 0, 1):          # one launch (cold, then warm: slow tiles split), three launches
         fb = torch.zeros((96, 128, 3), dtype=torch.float32, device="cuda")
         mask = torch.zeros((96, 128), dtype=torch.uint8, device="cuda")
