@@ -56,10 +56,18 @@ RTX_AOV_SYMBOLS = ["rtx_render_aov"]
 # the extension of include/rtx_ao.h: ambient occlusion of a frame (not part of the drop-in boundary)
 RTX_AO_SYMBOLS = ["rtx_render_ao"]
 
+# the extension of include/rtx_surface.h: surface data at the hits of caller-supplied rays (not part of the drop-in boundary)
+RTX_SURFACE_SYMBOLS = ["rtx_surface_rays"]
+
 
 class AovBuffers(C.Structure):
     """rtx_aov_buffers (include/rtx_aov.h): six device pointers, any of them NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth_dev", "object_dev", "triangle_dev", "uv_dev", "normal_dev", "albedo_dev")]
+
+
+class SurfaceBuffers(C.Structure):
+    """rtx_surface_buffers (include/rtx_surface.h): five device pointers, any of them NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("hits_dev", "position_dev", "normal_dev", "albedo_dev", "specular_dev")]
 
 
 class AoParams(C.Structure):
@@ -126,6 +134,7 @@ def load():
     rtx.rtx_occluded_rays.argtypes = [vp, u32, vp, vp, vp, vp]
     rtx.rtx_render_aov.argtypes = [vp, u32, u32, C.POINTER(AovBuffers), vp]
     rtx.rtx_render_ao.argtypes = [vp, u32, u32, C.POINTER(AoParams), vp, vp, vp]
+    rtx.rtx_surface_rays.argtypes = [vp, u32, vp, C.POINTER(SurfaceBuffers), vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -204,7 +213,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -845,6 +854,45 @@ class Scene:
                                        C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
                "rtx_trace_rays")
         return h, c
+
+    def surface_rays(self, rays, hits=False, position=False, normal=True, albedo=True, specular=False, stream=None):
+        """rtx_surface_rays: Render::trace of the rays of a device tensor and getSurfaceData at their hits, on the device -- what a caller
+        needs to shade a hit or to build the next ray from it.  rays: as for trace_rays.  Returns a dict of the channels asked for, new
+        float32 tensors on the rays' device: "hits" (n, 8), trace_rays' record; "position" (n, 3), orig + dir * tNear; "normal" (n, 3),
+        the shading normal (vertex normals, normal map); "albedo" (n, 3), the object's colour or its diffuse map's texel, at a miss the
+        sky / background colour of the direction; "specular" (n,), the object's specular coefficient or its specular map's value.
+        position, normal and specular are 0 at a miss.  The object's other constants are in device_objects(), indexed by hits[:, 1].
+        Asynchronous on `stream`, which is handled as in trace_rays."""
+        import torch
+        asked = [(name, shape) for name, on, shape in (("hits", hits, (8,)), ("position", position, (3,)), ("normal", normal, (3,)),
+                                                       ("albedo", albedo, (3,)), ("specular", specular, ())) if on]
+        if not asked:
+            raise ValueError("surface_rays: nothing to compute (every channel is off)")
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("surface_rays: rays must be a torch tensor, got %s" % type(rays).__name__)
+        if rays.dtype != torch.float32:
+            raise ValueError("surface_rays: rays must be float32, got %s" % rays.dtype)
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("surface_rays: rays must have shape (n, 6), got %s" % (tuple(rays.shape),))
+        if not rays.is_contiguous():
+            raise ValueError("surface_rays: rays must be contiguous")
+        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError("surface_rays: rays must be on cuda:%d, the scene's device, got %s" % (self.device, rays.device))
+        n = rays.shape[0]
+        if n > 0xFFFFFFC0:
+            raise ValueError("surface_rays: at most %d rays per call, got %d" % (0xFFFFFFC0, n))
+        alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+        with torch.cuda.stream(alloc_on):
+            out = {name: torch.empty((n,) + shape, dtype=torch.float32, device=rays.device) for name, shape in asked}
+        if n == 0:
+            return out
+        if alloc_on is not None:
+            rays.record_stream(alloc_on)
+        bufs = SurfaceBuffers(*[out[name].data_ptr() if name in out else None for name in ("hits", "position", "normal", "albedo", "specular")])
+        _check(self.rtx.rtx_surface_rays(self.gpu(), n, C.c_void_p(rays.data_ptr()), C.byref(bufs),
+                                         C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
+               "rtx_surface_rays")
+        return out
 
     def occluded(self, rays, tmax=None, stream=None):
         """rtx_occluded_rays: is anything between a ray's origin and its range?  Render::trace of a shadow ray whose info.tNear starts at

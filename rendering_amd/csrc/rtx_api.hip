@@ -21,6 +21,7 @@
 #include "../../include/rtx_query.h"
 #include "../../include/rtx_aov.h"
 #include "../../include/rtx_ao.h"
+#include "../../include/rtx_surface.h"
 #include "rtx_device.h"
 #include "rtx_own.h"
 
@@ -33,6 +34,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_rays.hip"
 #include "rtx_aov.hip"
 #include "rtx_ao.hip"
+#include "rtx_surface.hip"
 
 // rtx_sort.hip
 hipError_t rtxSortRayKeys(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, uint32_t* order, uint32_t n, int endBit,
@@ -210,6 +212,7 @@ struct rtx_scene {
 	DevArray<char> raySortTemp;
 	DevArray<uint32_t> rayWork;
 	int rayHitBlocks[2] = { 0, 0 };
+	int raySurfaceBlocks[2] = { 0, 0 };                        // rtx_surface_rays' kernel
 	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
@@ -362,6 +365,12 @@ RayKernel rayHitKernel(const Variant& v)
 {
 	if (v.analytic) return rtxRayHitKernel<false, true, -1>;
 	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayKernel { return rtxRayHitKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+typedef void (*RaySurfaceKernel)(const Params, const uint32_t*, const rtx_surface_buffers);
+RaySurfaceKernel raySurfaceKernel(const Variant& v)
+{
+	if (v.analytic) return rtxRaySurfaceKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RaySurfaceKernel { return rtxRaySurfaceKernel<true, decltype(b)::value, decltype(c)::value>; });
 }
 RayKernel rayColourKernel(const Variant& v)
 {
@@ -1785,6 +1794,7 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 		k.pruneBoxes = value < 0 ? -1 : (value != 0 ? 1 : 0);
 		chooseBoxPrune(s);
 		s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;      // (the hit kernel's occupancy is the variant's)
+		s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
 		for (auto& b : s->rayOccludedBlocks) b[0] = b[1] = 0;
 	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
@@ -2306,6 +2316,9 @@ namespace {
 constexpr uint32_t kTraceReorderMin = 1u << 20;
 // rtx_occluded_rays' own threshold for the same rule (profiles/occluded_rays_time.json)
 constexpr uint32_t kOccludedReorderMin = kTraceReorderMin;
+// ... and rtx_surface_rays': its times follow rtx_trace_rays' hits-only times within 0.1 ms at every setting of the knob, so it keeps that
+// call's threshold (profiles/surface_time.json)
+constexpr uint32_t kSurfaceReorderMin = kTraceReorderMin;
 
 // The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
 // for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
@@ -2425,6 +2438,41 @@ int rtx_occluded_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const flo
 	const uint32_t waves = (n + 63) / 64;
 	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
 	hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, tmax_dev, occluded_dev);
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_surface_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_surface_buffers* out, void* stream)
+{
+	RoctxRange range("Surface rays (rtx_surface_rays)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	if (!out->hits_dev && !out->position_dev && !out->normal_dev && !out->albedo_dev && !out->specular_dev)
+		return fail(RTX_ERR_ARG, "rtx_surface_rays: no output (all five buffers are NULL)");
+	if (n == 0) return RTX_OK;
+	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
+	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
+	hipStream_t st = (hipStream_t)stream;
+	Params p;
+	const uint32_t* order = nullptr;
+	if (int rc = beginRays(s, n, rays_dev, kSurfaceReorderMin, st, p, &order)) return rc;
+	const uint32_t waves = (n + 63) / 64;
+	const Variant v = variantOf(s);
+	p.workCounter = s->rayWork;
+	if (!out->position_dev && !out->normal_dev && !out->albedo_dev && !out->specular_dev) {
+		// the hit records alone: rtx_trace_rays' launch (no surface fetch is compiled into that kernel)
+		const RayKernel k = rayHitKernel(v);
+		int& perCU = s->rayHitBlocks[v.cull ? 1 : 0];
+		if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
+		const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
+		hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, out->hits_dev);
+	}
+	else {
+		const RaySurfaceKernel k = raySurfaceKernel(v);
+		int& perCU = s->raySurfaceBlocks[v.cull ? 1 : 0];
+		if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
+		const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
+		hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, *out);
+	}
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
