@@ -245,6 +245,50 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr(t):
+    """A tensor's device address as a C argument; None is NULL."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check_tensor(who, name, t, dtype, shape, device=None):
+    """Argument `name` of the wrapper `who` (the prefix of every message) is a contiguous torch tensor of `dtype` and `shape` -- a tuple whose
+    entries are sizes, or names such as "n" for a size that is free -- on cuda:`device` (None: the wrapper checks the device itself)."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+    if t.dtype != dtype:
+        raise ValueError("%s: %s must be %s, got %s" % (who, name, str(dtype).replace("torch.", ""), t.dtype))
+    if t.dim() != len(shape) or any(want != have for want, have in zip(shape, t.shape) if not isinstance(want, str)):
+        raise ValueError("%s: %s must have shape %s, got %s" % (who, name, str(shape).replace("'", ""), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    if device is not None and (t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != device):
+        raise ValueError("%s: %s must be on cuda:%d, the scene's device, got %s" % (who, name, device, t.device))
+
+
+def _check_rays(who, rays, device):
+    """The rays of the wrapper `who`: a contiguous float32 tensor (n, 6) on cuda:`device` of at most 0xFFFFFFC0 rays.  Returns n."""
+    import torch
+    _check_tensor(who, "rays", rays, torch.float32, ("n", 6), device)
+    if rays.shape[0] > 0xFFFFFFC0:
+        raise ValueError("%s: at most %d rays per call, got %d" % (who, 0xFFFFFFC0, rays.shape[0]))
+    return rays.shape[0]
+
+
+def _query_stream(stream, device, inputs):
+    """(alloc_on, pointer) of the stream a query call runs on: `stream`, or torch's current stream of `device` for None.  With a
+    torch.cuda.Stream, alloc_on is that stream -- the outputs are allocated on it and the tensors of `inputs` (None entries skipped) are
+    recorded on it while it uses them (torch's caching allocator); a raw hipStream_t handle is used as given (alloc_on None), so the
+    caller keeps the tensors alive and unreused until it has finished with them."""
+    import torch
+    alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+    if alloc_on is not None:
+        for t in inputs:
+            if t is not None:
+                t.record_stream(alloc_on)
+    return alloc_on, C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if stream is None else Scene._stream_ptr(stream)
+
+
 def set_ac_build(mode, device=0):
     """Where the host loader builds acceleration structures from now on: "host", "device" (rtx_bvh_build) or
     "auto" (the device when one is visible).  Both give the same structure bit for bit."""
@@ -827,32 +871,13 @@ class Scene:
         import torch
         if not (hits or colours):
             raise ValueError("trace_rays: nothing to compute (hits and colours are both off)")
-        if not isinstance(rays, torch.Tensor):
-            raise ValueError("trace_rays: rays must be a torch tensor, got %s" % type(rays).__name__)
-        if rays.dtype != torch.float32:
-            raise ValueError("trace_rays: rays must be float32, got %s" % rays.dtype)
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise ValueError("trace_rays: rays must have shape (n, 6), got %s" % (tuple(rays.shape),))
-        if not rays.is_contiguous():
-            raise ValueError("trace_rays: rays must be contiguous")
-        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError("trace_rays: rays must be on cuda:%d, the scene's device, got %s" % (self.device, rays.device))
-        n = rays.shape[0]
-        if n > 0xFFFFFFC0:
-            raise ValueError("trace_rays: at most %d rays per call, got %d" % (0xFFFFFFC0, n))
-        # the outputs belong to the stream they are written on (torch's caching allocator), and so do the rays while it reads them
-        alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+        n = _check_rays("trace_rays", rays, self.device)
+        alloc_on, st = _query_stream(stream, rays.device, (rays,))
         with torch.cuda.stream(alloc_on):
             h = torch.empty((n, 8), dtype=torch.float32, device=rays.device) if hits else None
             c = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if colours else None
-        if n == 0:
-            return h, c
-        if alloc_on is not None:
-            rays.record_stream(alloc_on)
-        _check(self.rtx.rtx_trace_rays(self.gpu(), n, C.c_void_p(rays.data_ptr()), C.c_void_p(h.data_ptr()) if h is not None else None,
-                                       C.c_void_p(c.data_ptr()) if c is not None else None,
-                                       C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
-               "rtx_trace_rays")
+        if n:
+            _check(self.rtx.rtx_trace_rays(self.gpu(), n, _ptr(rays), _ptr(h), _ptr(c), st), "rtx_trace_rays")
         return h, c
 
     def surface_rays(self, rays, hits=False, position=False, normal=True, albedo=True, specular=False, stream=None):
@@ -868,30 +893,13 @@ class Scene:
                                                        ("albedo", albedo, (3,)), ("specular", specular, ())) if on]
         if not asked:
             raise ValueError("surface_rays: nothing to compute (every channel is off)")
-        if not isinstance(rays, torch.Tensor):
-            raise ValueError("surface_rays: rays must be a torch tensor, got %s" % type(rays).__name__)
-        if rays.dtype != torch.float32:
-            raise ValueError("surface_rays: rays must be float32, got %s" % rays.dtype)
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise ValueError("surface_rays: rays must have shape (n, 6), got %s" % (tuple(rays.shape),))
-        if not rays.is_contiguous():
-            raise ValueError("surface_rays: rays must be contiguous")
-        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError("surface_rays: rays must be on cuda:%d, the scene's device, got %s" % (self.device, rays.device))
-        n = rays.shape[0]
-        if n > 0xFFFFFFC0:
-            raise ValueError("surface_rays: at most %d rays per call, got %d" % (0xFFFFFFC0, n))
-        alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+        n = _check_rays("surface_rays", rays, self.device)
+        alloc_on, st = _query_stream(stream, rays.device, (rays,))
         with torch.cuda.stream(alloc_on):
             out = {name: torch.empty((n,) + shape, dtype=torch.float32, device=rays.device) for name, shape in asked}
-        if n == 0:
-            return out
-        if alloc_on is not None:
-            rays.record_stream(alloc_on)
-        bufs = SurfaceBuffers(*[out[name].data_ptr() if name in out else None for name in ("hits", "position", "normal", "albedo", "specular")])
-        _check(self.rtx.rtx_surface_rays(self.gpu(), n, C.c_void_p(rays.data_ptr()), C.byref(bufs),
-                                         C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
-               "rtx_surface_rays")
+        if n:
+            bufs = SurfaceBuffers(*[out[name].data_ptr() if name in out else None for name in ("hits", "position", "normal", "albedo", "specular")])
+            _check(self.rtx.rtx_surface_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_surface_rays")
         return out
 
     def occluded(self, rays, tmax=None, stream=None):
@@ -901,47 +909,22 @@ class Scene:
         device, a Python float (one range for every ray) or None (+inf: the whole ray).  Returns a new torch.uint8 tensor (n,) of 0 / 1
         on that device.  Asynchronous on `stream`, which is handled as in trace_rays (a tmax tensor is recorded on it like the rays)."""
         import torch
-        if not isinstance(rays, torch.Tensor):
-            raise ValueError("occluded: rays must be a torch tensor, got %s" % type(rays).__name__)
-        if rays.dtype != torch.float32:
-            raise ValueError("occluded: rays must be float32, got %s" % rays.dtype)
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise ValueError("occluded: rays must have shape (n, 6), got %s" % (tuple(rays.shape),))
-        if not rays.is_contiguous():
-            raise ValueError("occluded: rays must be contiguous")
-        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError("occluded: rays must be on cuda:%d, the scene's device, got %s" % (self.device, rays.device))
-        n = rays.shape[0]
-        if n > 0xFFFFFFC0:
-            raise ValueError("occluded: at most %d rays per call, got %d" % (0xFFFFFFC0, n))
+        n = _check_rays("occluded", rays, self.device)
         if isinstance(tmax, torch.Tensor):
-            if tmax.dtype != torch.float32:
-                raise ValueError("occluded: tmax must be float32, got %s" % tmax.dtype)
-            if tuple(tmax.shape) != (n,):
-                raise ValueError("occluded: tmax must have shape (%d,), got %s" % (n, tuple(tmax.shape)))
-            if not tmax.is_contiguous():
-                raise ValueError("occluded: tmax must be contiguous")
+            _check_tensor("occluded", "tmax", tmax, torch.float32, (n,))
             if tmax.device != rays.device:
                 raise ValueError("occluded: tmax must be on the rays' device %s, got %s" % (rays.device, tmax.device))
         elif tmax is not None and not isinstance(tmax, (int, float)):
             raise ValueError("occluded: tmax must be a torch tensor, a float or None, got %s" % type(tmax).__name__)
-        alloc_on = stream if isinstance(stream, torch.cuda.Stream) else None
+        alloc_on, st = _query_stream(stream, rays.device, (rays, tmax if isinstance(tmax, torch.Tensor) else None))
         with torch.cuda.stream(alloc_on):
             out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
             if tmax is not None and not isinstance(tmax, torch.Tensor):
                 tmax = torch.full((n,), float(tmax), dtype=torch.float32, device=rays.device)
                 if stream is not None and alloc_on is None:
                     torch.cuda.current_stream(rays.device).synchronize()      # (a raw handle: torch cannot order the fill before it)
-        if n == 0:
-            return out
-        if alloc_on is not None:
-            rays.record_stream(alloc_on)
-            if tmax is not None:
-                tmax.record_stream(alloc_on)
-        _check(self.rtx.rtx_occluded_rays(self.gpu(), n, C.c_void_p(rays.data_ptr()), C.c_void_p(tmax.data_ptr()) if tmax is not None else None,
-                                          C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
-               "rtx_occluded_rays")
+        if n:
+            _check(self.rtx.rtx_occluded_rays(self.gpu(), n, _ptr(rays), _ptr(tmax), _ptr(out), st), "rtx_occluded_rays")
         return out
 
     def render_aov(self, depth=None, object_id=None, triangle_id=None, uv=None, normal=None, albedo=None, rows=None, stream=None):
@@ -957,28 +940,12 @@ class Scene:
         if all(t is None for _, t, _, _ in given):
             raise ValueError("render_aov: nothing to compute (at least one buffer is needed)")
         for name, t, dtype, tail in given:
-            if t is None:
-                continue
-            shape = (self.height, self.width) + tail
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("render_aov: %s must be a torch tensor, got %s" % (name, type(t).__name__))
-            if t.dtype != dtype:
-                raise ValueError("render_aov: %s must be %s, got %s" % (name, str(dtype).replace("torch.", ""), t.dtype))
-            if tuple(t.shape) != shape:
-                raise ValueError("render_aov: %s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if not t.is_contiguous():
-                raise ValueError("render_aov: %s must be contiguous" % name)
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
-                raise ValueError("render_aov: %s must be on cuda:%d, the scene's device, got %s" % (name, self.device, t.device))
+            if t is not None:
+                _check_tensor("render_aov", name, t, dtype, (self.height, self.width) + tail, self.device)
         r0, r1 = rows if rows is not None else (0, self.height)
-        if isinstance(stream, torch.cuda.Stream):
-            for _, t, _, _ in given:
-                if t is not None:
-                    t.record_stream(stream)
+        _, st = _query_stream(stream, self.device, [t for _, t, _, _ in given])
         bufs = AovBuffers(*[t.data_ptr() if t is not None else None for _, t, _, _ in given])
-        _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(bufs),
-                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
-               "rtx_render_aov")
+        _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(bufs), st), "rtx_render_aov")
 
     def render_ao(self, dirs, radius=float("inf"), ao=None, counts=None, rows=None, stream=None):
         """rtx_render_ao: ambient occlusion of the frame in one launch.  For every pixel of pass 1 whose primary ray hits, each direction
@@ -989,35 +956,16 @@ class Scene:
         Asynchronous on `stream` (None: torch's current stream of the scene's device); with a torch.cuda.Stream the tensors are
         recorded on it."""
         import torch
-        given = (("dirs", dirs, torch.float32), ("ao", ao, torch.float32), ("counts", counts, torch.int32))
         if ao is None and counts is None:
             raise ValueError("render_ao: nothing to compute (at least one buffer is needed)")
-        for name, t, dtype in given:
-            if t is None and name != "dirs":
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("render_ao: %s must be a torch tensor, got %s" % (name, type(t).__name__))
-            if t.dtype != dtype:
-                raise ValueError("render_ao: %s must be %s, got %s" % (name, str(dtype).replace("torch.", ""), t.dtype))
-            if name == "dirs":
-                if t.dim() != 2 or t.shape[1] != 3:
-                    raise ValueError("render_ao: dirs must have shape (K, 3), got %s" % (tuple(t.shape),))
-            elif tuple(t.shape) != (self.height, self.width):
-                raise ValueError("render_ao: %s must have shape %s, got %s" % (name, (self.height, self.width), tuple(t.shape)))
-            if not t.is_contiguous():
-                raise ValueError("render_ao: %s must be contiguous" % name)
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
-                raise ValueError("render_ao: %s must be on cuda:%d, the scene's device, got %s" % (name, self.device, t.device))
+        _check_tensor("render_ao", "dirs", dirs, torch.float32, ("K", 3), self.device)
+        for name, t, dtype in (("ao", ao, torch.float32), ("counts", counts, torch.int32)):
+            if t is not None:
+                _check_tensor("render_ao", name, t, dtype, (self.height, self.width), self.device)
         r0, r1 = rows if rows is not None else (0, self.height)
-        if isinstance(stream, torch.cuda.Stream):
-            for _, t, _ in given:
-                if t is not None:
-                    t.record_stream(stream)
+        _, st = _query_stream(stream, self.device, (dirs, ao, counts))
         par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
-        _check(self.rtx.rtx_render_ao(self.gpu(), r0, r1, C.byref(par), C.c_void_p(ao.data_ptr()) if ao is not None else None,
-                                      C.c_void_p(counts.data_ptr()) if counts is not None else None,
-                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)),
-               "rtx_render_ao")
+        _check(self.rtx.rtx_render_ao(self.gpu(), r0, r1, C.byref(par), _ptr(ao), _ptr(counts), st), "rtx_render_ao")
 
     def device_mesh(self, mesh):
         """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,

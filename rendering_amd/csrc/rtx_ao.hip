@@ -6,6 +6,8 @@
 // wave-uniform loop over the directions.  Direction k comes through the scalar unit and is the same for all 64 lanes, so every bundle the
 // walk is handed is 64 parallel rays that leave one 8x8 patch of surface: no ray is stored or read, nothing is sorted.  The origins are not
 // the camera's, so these traces use the general source class (0).  No state machine, no park area, no recursion frames, no queue.
+// Both halves are written out here: on the shared steps of rtx_rays.hip (surfaceAtHit) and with the any-hit trace as a helper of its own this
+// kernel measured 1 % slower at 4096^2.
 #pragma clang fp contract(off)
 
 struct AoArgs {
@@ -79,9 +81,4 @@ __global__ void __launch_bounds__(256) rtxAoKernel(const Params P, const AoArgs 
 	if (A.ao) A.ao[i] = nTraced ? (float)nOpen / (float)nTraced : 1.0f;
 }
 
-// per (box test of the prune records, culling) like the other trace-only kernels; scenes without meshes have the walk-free form
-template __global__ void rtxAoKernel<true, true, 1>(const Params, const AoArgs);
-template __global__ void rtxAoKernel<true, false, 1>(const Params, const AoArgs);
-template __global__ void rtxAoKernel<true, true, 0>(const Params, const AoArgs);
-template __global__ void rtxAoKernel<true, false, 0>(const Params, const AoArgs);
-template __global__ void rtxAoKernel<false, true, -1>(const Params, const AoArgs);
+RTX_QUERY_INSTANCES(rtxAoKernel, (const Params, const AoArgs))

@@ -1,11 +1,11 @@
 // First-hit buffers of a frame (rtx_render_aov, include/rtx_aov.h): for every pixel of pass 1 the channels of
 // Render::trace of its primary ray and of getSurfaceData at the hit -- depth, object id, triangle id, uv, normal, albedo.
 //
-// A kernel of its own after the pattern of rtxNormalsKernel's mode 0: one 8x8 tile per wave over a plain grid, the pixel's ray from
+// One 8x8 tile per wave over a plain grid (the pattern of rtxNormalsKernel's mode 0), the pixel's ray from
 // primaryRay (never stored), traceWave in its trace-only form with source class 1 (the camera's copies of the prune records, which only
 // rays that start at view.camPos may use).  No state machine, no park area, no recursion frames, no queue.
-// SURFACE = false: only the hit record is written; shadePrimary and its fetches (uv, normals, tangents, maps) are not compiled in, which
-// keeps the kernel in the register class of rtxRayHitKernel.  SURFACE = true: shadePrimary's N and objColor are written as well.
+// SURFACE = false: only the hit record is written; surfaceAtHit of rtx_rays.hip (shadePrimary and its fetches: uv, normals, tangents, maps) is not
+// compiled in, which keeps the kernel in the register class of rtxRayHitKernel.  SURFACE = true: its normal and albedo are written as well.
 #pragma clang fp contract(off)
 
 template <bool MESH, bool BOXES, int CULLK, bool SURFACE>
@@ -38,26 +38,13 @@ __global__ void __launch_bounds__(256) rtxAovKernel(const Params P, const rtx_ao
 	}
 	if (out.uv_dev) { float* p = out.uv_dev + i * 2; p[0] = hit ? h.u : -1.f; p[1] = hit ? h.v : -1.f; }
 	if (SURFACE) {
-		V3 n = mk(0, 0, 0), a;
-		if (hit) {
-			Lane s;
-			s.ro = o; s.rd = d;
-			shadePrimary(P, s, h);      // (only the lanes that hit are here: its loop is over their objects)
-			n = s.N; a = s.objColor;
-		}
-		else a = skyColor(P, d);
-		if (out.normal_dev) { float* p = out.normal_dev + i * 3; p[0] = n.x; p[1] = n.y; p[2] = n.z; }
-		if (out.albedo_dev) { float* p = out.albedo_dev + i * 3; p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+		V3 p, n, a;
+		float ks;
+		surfaceAtHit(P, h, o, d, p, n, a, ks);
+		if (out.normal_dev) store3(out.normal_dev + i * 3, n);
+		if (out.albedo_dev) store3(out.albedo_dev + i * 3, a);
 	}
 }
-
-// per (box test of the prune records, culling) like the other trace-only kernels, each with and without the surface fetch; scenes without
-// meshes have the walk-free form
-#define RTX_AOV_INSTANCES(S)                                                                     \
-template __global__ void rtxAovKernel<true, true, 1, S>(const Params, const rtx_aov_buffers);   \
-template __global__ void rtxAovKernel<true, false, 1, S>(const Params, const rtx_aov_buffers);  \
-template __global__ void rtxAovKernel<true, true, 0, S>(const Params, const rtx_aov_buffers);   \
-template __global__ void rtxAovKernel<true, false, 0, S>(const Params, const rtx_aov_buffers);  \
-template __global__ void rtxAovKernel<false, true, -1, S>(const Params, const rtx_aov_buffers);
-RTX_AOV_INSTANCES(false) RTX_AOV_INSTANCES(true)
-#undef RTX_AOV_INSTANCES
+// (each with and without the surface fetch)
+RTX_QUERY_INSTANCES(rtxAovKernel, (const Params, const rtx_aov_buffers), false)
+RTX_QUERY_INSTANCES(rtxAovKernel, (const Params, const rtx_aov_buffers), true)

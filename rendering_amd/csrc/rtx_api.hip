@@ -35,6 +35,8 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_aov.hip"
 #include "rtx_ao.hip"
 #include "rtx_surface.hip"
+#undef RTX_QUERY_INSTANCES
+#undef RTX_MESH_INSTANCES
 
 // rtx_sort.hip
 hipError_t rtxSortRayKeys(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, uint32_t* order, uint32_t n, int endBit,
@@ -402,6 +404,21 @@ OccludedKernel rayOccludedKernel(const Variant& v, bool sceneOrder)
 int askBlocksPerCU(int& perCU, const void* kernel)
 {
 	if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, 0)); perCU = std::max(perCU, 1); }
+	return RTX_OK;
+}
+
+// A batch of caller-supplied rays on its way to the kernels of rtx_rays.hip (startRays): the argument block of the launches, the rays' order,
+// the stream and the number of 64-ray groups.
+struct RayCall { Params p; const uint32_t* order; hipStream_t st; uint32_t waves; };
+
+// A launch of persistent waves for such a batch: as many blocks as the device holds of `kernel` at once (perCU: askBlocksPerCU's
+// answer for it, kept by the scene), at most one wave per group.
+template <typename... KArgs, typename... Args>
+int launchRays(rtx_scene* s, void (*kernel)(KArgs...), int& perCU, const RayCall& c, Args... args)
+{
+	if (int rc = askBlocksPerCU(perCU, (const void*)kernel)) return rc;
+	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (c.waves + 3) / 4);
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, c.st, c.p, c.order, args...);
 	return RTX_OK;
 }
 
@@ -1460,23 +1477,35 @@ namespace {
 // tile costs and the frame-mode measurements of the ordinary frames are neither used nor touched.
 bool showNormals(const rtx_scene* s) { return (s->params.view.flags & RTX_FLAG_SHOW_NORMALS) != 0; }
 
-int normalsPass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, hipStream_t st)
+// The plain grid over the 8x8 tiles of pass 1's pixels in the rows [rowBegin, rowEnd) (clamped to the view), one wave per tile: p's row range,
+// tilesX, tileRow0 and nTiles; the launch takes (nTiles + 3) / 4 blocks.  Neither the tile lists nor the tile costs are read or written.
+// false: the call ends here with rc -- no such pixel (RTX_OK), or a frame too large.
+bool plainTileGrid(const rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, Params& p, int& rc)
 {
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "the debug views collect no statistics (rtx_counters_enable)");
 	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	Params p = s->params;
-	p.fb = fb_dev;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
+	rc = RTX_OK;
+	if (rowEnd > H) rowEnd = H;
+	if (rowBegin >= rowEnd) return false;
 	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
-	if (lastRow <= rowBegin) return RTX_OK;
+	if (lastRow <= rowBegin) return false;
+	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
 	p.tilesX = (W - 1 + 7) / 8;
 	p.tileRow0 = rowBegin / 8;
 	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
-	if (tiles >= (1u << 30)) return fail(RTX_ERR_ARG, "frame too large");
+	if (tiles >= (1u << 30)) { rc = fail(RTX_ERR_ARG, "frame too large"); return false; }
 	p.nTiles = (uint32_t)tiles;
-	int rc = stamp(s, 0, st);
-	if (rc) return rc;
-	hipLaunchKernelGGL(rtxNormalsKernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, 0);
+	return true;
+}
+
+int normalsPass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, hipStream_t st)
+{
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "the debug views collect no statistics (rtx_counters_enable)");
+	Params p = s->params;
+	p.fb = fb_dev;
+	int rc;
+	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
+	if ((rc = stamp(s, 0, st))) return rc;
+	hipLaunchKernelGGL(rtxNormalsKernel, dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, 0);
 	HIPCHK(hipGetLastError());
 	return stamp(s, 0, st);
 }
@@ -2376,6 +2405,21 @@ int beginRays(rtx_scene* s, uint32_t n, const float* rays_dev, uint32_t reorderM
 	return RTX_OK;
 }
 
+// The common start of rtx_trace_rays, rtx_occluded_rays and rtx_surface_rays, after their own checks: the checks of n and rays, then
+// beginRays, which fill c (RayCall).
+// false: the call ends here with rc -- no ray (RTX_OK), or an error.
+bool startRays(rtx_scene* s, uint32_t n, const float* rays_dev, uint32_t reorderMin, void* stream, RayCall& c, int& rc)
+{
+	rc = RTX_OK;
+	if (n == 0) return false;
+	if (!rays_dev) { rc = fail(RTX_ERR_ARG, "rays is NULL"); return false; }
+	if (n > 0xffffffc0u) { rc = fail(RTX_ERR_ARG, "too many rays"); return false; }
+	c.st = (hipStream_t)stream;
+	c.order = nullptr;
+	c.waves = (n + 63) / 64;
+	return (rc = beginRays(s, n, rays_dev, reorderMin, c.st, c.p, &c.order)) == RTX_OK;
+}
+
 } // namespace
 
 int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_dev, float* colours_dev, void* stream)
@@ -2383,34 +2427,19 @@ int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_
 	RoctxRange range("Trace rays (rtx_trace_rays)");
 	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
 	if (!hits_dev && !colours_dev) return fail(RTX_ERR_ARG, "rtx_trace_rays: no output (hits and colours are both NULL)");
-	if (n == 0) return RTX_OK;
-	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
-	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
-	hipStream_t st = (hipStream_t)stream;
-	Params p;
-	const uint32_t* order = nullptr;
-	if (int rc = beginRays(s, n, rays_dev, kTraceReorderMin, st, p, &order)) return rc;
-	const uint32_t waves = (n + 63) / 64;
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, rays_dev, kTraceReorderMin, stream, c, rc)) return rc;
 	const Variant v = variantOf(s);
-	if (showNormals(s)) {
-		p.workCounter = s->rayWork;
-		const uint32_t blocks = std::min<uint32_t>((uint32_t)s->blocksPass1, (waves + 3) / 4);
-		hipLaunchKernelGGL(rtxRayNormalsKernel, dim3(blocks), dim3(256), 0, st, p, order, hits_dev, colours_dev);
-	}
+	// (the recursion frames of the pass-1 area hold blocksPass1 blocks: the grid of the kernels that shade)
+	const uint32_t blocksShade = std::min<uint32_t>((uint32_t)s->blocksPass1, (c.waves + 3) / 4);
+	c.p.workCounter = s->rayWork;
+	if (showNormals(s)) hipLaunchKernelGGL(rtxRayNormalsKernel, dim3(blocksShade), dim3(256), 0, c.st, c.p, c.order, hits_dev, colours_dev);
 	else {
-		if (hits_dev) {
-			const RayKernel k = rayHitKernel(v);
-			int& perCU = s->rayHitBlocks[v.cull ? 1 : 0];
-			if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
-			p.workCounter = s->rayWork;
-			const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
-			hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, hits_dev);
-		}
+		if (hits_dev && (rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, hits_dev))) return rc;
 		if (colours_dev) {
-			// (the recursion frames of the pass-1 area hold blocksPass1 blocks)
-			p.workCounter = s->rayWork + 16;
-			const uint32_t blocks = std::min<uint32_t>((uint32_t)s->blocksPass1, (waves + 3) / 4);
-			hipLaunchKernelGGL(rayColourKernel(v), dim3(blocks), dim3(256), 0, st, p, order, colours_dev);
+			c.p.workCounter = s->rayWork + 16;
+			hipLaunchKernelGGL(rayColourKernel(v), dim3(blocksShade), dim3(256), 0, c.st, c.p, c.order, colours_dev);
 		}
 	}
 	HIPCHK(hipGetLastError());
@@ -2421,23 +2450,15 @@ int rtx_occluded_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const flo
 {
 	RoctxRange range("Occluded rays (rtx_occluded_rays)");
 	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
-	if (n == 0) return RTX_OK;
-	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
-	if (!occluded_dev) return fail(RTX_ERR_ARG, "rtx_occluded_rays: no output (occluded is NULL)");
-	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
-	hipStream_t st = (hipStream_t)stream;
-	Params p;
-	const uint32_t* order = nullptr;
-	if (int rc = beginRays(s, n, rays_dev, kOccludedReorderMin, st, p, &order)) return rc;
+	// (this call has always looked at n and rays first: an empty batch needs no output, and "rays is NULL" comes before this message)
+	if (n != 0 && rays_dev && !occluded_dev) return fail(RTX_ERR_ARG, "rtx_occluded_rays: no output (occluded is NULL)");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, rays_dev, kOccludedReorderMin, stream, c, rc)) return rc;
 	const Variant v = variantOf(s);
 	const bool sceneOrder = s->knobs.occludedSceneOrder != 0;
-	const OccludedKernel k = rayOccludedKernel(v, sceneOrder);
-	int& perCU = s->rayOccludedBlocks[v.cull ? 1 : 0][sceneOrder ? 1 : 0];
-	if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
-	p.workCounter = s->rayWork;
-	const uint32_t waves = (n + 63) / 64;
-	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
-	hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, tmax_dev, occluded_dev);
+	c.p.workCounter = s->rayWork;
+	if ((rc = launchRays(s, rayOccludedKernel(v, sceneOrder), s->rayOccludedBlocks[v.cull ? 1 : 0][sceneOrder ? 1 : 0], c, tmax_dev, occluded_dev))) return rc;
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
@@ -2446,33 +2467,17 @@ int rtx_surface_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_
 {
 	RoctxRange range("Surface rays (rtx_surface_rays)");
 	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	if (!out->hits_dev && !out->position_dev && !out->normal_dev && !out->albedo_dev && !out->specular_dev)
-		return fail(RTX_ERR_ARG, "rtx_surface_rays: no output (all five buffers are NULL)");
-	if (n == 0) return RTX_OK;
-	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
-	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
-	hipStream_t st = (hipStream_t)stream;
-	Params p;
-	const uint32_t* order = nullptr;
-	if (int rc = beginRays(s, n, rays_dev, kSurfaceReorderMin, st, p, &order)) return rc;
-	const uint32_t waves = (n + 63) / 64;
+	const bool surface = out->position_dev || out->normal_dev || out->albedo_dev || out->specular_dev;
+	if (!out->hits_dev && !surface) return fail(RTX_ERR_ARG, "rtx_surface_rays: no output (all five buffers are NULL)");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, rays_dev, kSurfaceReorderMin, stream, c, rc)) return rc;
 	const Variant v = variantOf(s);
-	p.workCounter = s->rayWork;
-	if (!out->position_dev && !out->normal_dev && !out->albedo_dev && !out->specular_dev) {
-		// the hit records alone: rtx_trace_rays' launch (no surface fetch is compiled into that kernel)
-		const RayKernel k = rayHitKernel(v);
-		int& perCU = s->rayHitBlocks[v.cull ? 1 : 0];
-		if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
-		const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
-		hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, out->hits_dev);
-	}
-	else {
-		const RaySurfaceKernel k = raySurfaceKernel(v);
-		int& perCU = s->raySurfaceBlocks[v.cull ? 1 : 0];
-		if (int rc = askBlocksPerCU(perCU, (const void*)k)) return rc;
-		const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (waves + 3) / 4);
-		hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, p, order, *out);
-	}
+	c.p.workCounter = s->rayWork;
+	// the hit records alone: rtx_trace_rays' launch (no surface fetch is compiled into that kernel)
+	if (!surface) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
+	else rc = launchRays(s, raySurfaceKernel(v), s->raySurfaceBlocks[v.cull ? 1 : 0], c, *out);
+	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
@@ -2484,25 +2489,16 @@ int rtx_render_aov(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_a
 	if (!out->depth_dev && !out->object_dev && !out->triangle_dev && !out->uv_dev && !out->normal_dev && !out->albedo_dev)
 		return fail(RTX_ERR_ARG, "rtx_render_aov: no output (all six buffers are NULL)");
 	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_aov collects no statistics (rtx_counters_enable)");
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
-	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
-	if (lastRow <= rowBegin) return RTX_OK;
+	// A plain grid over the tiles, as the normals view; no event is recorded (rtx_last_kernel_ms and the frame-mode measurements keep
+	// what the ordinary frames left).
+	Params p = s->params;
+	int rc;
+	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
 	HIPCHK(hipSetDevice(s->device));
 	hipStream_t st = (hipStream_t)stream;
 	if (int ro = renderOn(s, st)) return ro;
-	// A plain grid over the tiles, as the normals view: neither the tile lists nor the tile costs are read or written, and no event is
-	// recorded (rtx_last_kernel_ms and the frame-mode measurements keep what the ordinary frames left).
-	Params p = s->params;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.tilesX = (W - 1 + 7) / 8;
-	p.tileRow0 = rowBegin / 8;
-	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
-	if (tiles >= (1u << 30)) return fail(RTX_ERR_ARG, "frame too large");
-	p.nTiles = (uint32_t)tiles;
 	const bool surface = out->normal_dev || out->albedo_dev;
-	hipLaunchKernelGGL(aovKernel(variantOf(s), surface), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, *out);
+	hipLaunchKernelGGL(aovKernel(variantOf(s), surface), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, *out);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }
@@ -2516,25 +2512,15 @@ int rtx_render_ao(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_ao
 	if (par->n_dirs < 1 || par->n_dirs > 256) return fail(RTX_ERR_ARG, "rtx_render_ao: n_dirs must be 1 .. 256");
 	if (!(par->radius > 0)) return fail(RTX_ERR_ARG, "rtx_render_ao: radius must be > 0 (+inf: the whole ray)");
 	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_ao collects no statistics (rtx_counters_enable)");
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
-	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
-	if (lastRow <= rowBegin) return RTX_OK;
+	// (the plain grid of rtx_render_aov; no event is recorded)
+	Params p = s->params;
+	int rc;
+	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
 	HIPCHK(hipSetDevice(s->device));
 	hipStream_t st = (hipStream_t)stream;
 	if (int ro = renderOn(s, st)) return ro;
-	// rtx_render_aov's launch: a plain grid over the tiles; neither the tile lists nor the tile costs are read or written, and no event
-	// is recorded
-	Params p = s->params;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.tilesX = (W - 1 + 7) / 8;
-	p.tileRow0 = rowBegin / 8;
-	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
-	if (tiles >= (1u << 30)) return fail(RTX_ERR_ARG, "frame too large");
-	p.nTiles = (uint32_t)tiles;
 	const AoArgs a = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
-	hipLaunchKernelGGL(aoKernel(variantOf(s)), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p, a);
+	hipLaunchKernelGGL(aoKernel(variantOf(s)), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, a);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

@@ -151,12 +151,49 @@ __global__ void __launch_bounds__(256) rtxRayKeyKernel(const float* rays, uint32
 
 namespace {
 
+// ---- The steps the query kernels share (this file's and those of rtx_surface.hip and rtx_aov.hip, which come after it) ----
+
 // Entry k of the order: the index of the ray lane k takes (order == nullptr: the rays as handed over).
 __device__ __forceinline__ void loadRay(const Params& P, const uint32_t* order, uint32_t k, bool valid, uint32_t& i, V3& o, V3& d)
 {
 	i = valid ? (order ? order[k] : k) : 0u;
 	o = mk(0, 0, 0); d = mk(0, 0, -1);
 	if (valid) { o = load3(P.probeRays + (size_t)i * 6); d = load3(P.probeRays + (size_t)i * 6 + 3); }
+}
+
+// The loop of a persistent wave over the P.nProbe rays at P.probeRays: the next 64 entries of the order off the launch's queue
+// (P.workCounter) until it is empty, one ray per lane.  body(valid, i, o, d) -- valid: the lane has a ray (the last group may be short);
+// i: the ray's own index, where its results go.  The whole wave is in body, so that it can walk its rays as one bundle.
+// (rtxRayOccludedKernel and rtxRayNormalsKernel have this loop written out: DESIGN.md 3.14.)
+template <typename Body>
+__device__ __forceinline__ void forEachRayWave(const Params& P, const uint32_t* order, Body&& body)
+{
+	const uint32_t lane = __lane_id();
+	const uint32_t nWork = (P.nProbe + 63) / 64;
+	for (;;) {
+		const uint32_t work = nextWork(P.workCounter);
+		if (work >= nWork) break;
+		const uint32_t k = work * 64 + lane;
+		const bool valid = k < P.nProbe;
+		uint32_t i; V3 o, d;
+		loadRay(P, order, k, valid, i, o, d);
+		body(valid, i, o, d);
+	}
+}
+
+// getSurfaceData at the first hit h of the ray (o, d): hit point, shading normal, albedo and specular coefficient of the lanes that hit
+// (shadePrimary: its loop is over their objects); the others get the sky / background colour of their direction as albedo and zeros.
+// What a caller does not use is not computed.
+__device__ __forceinline__ void surfaceAtHit(const Params& P, const Hit& h, const V3& o, const V3& d, V3& p, V3& n, V3& albedo, float& ks)
+{
+	p = mk(0, 0, 0); n = mk(0, 0, 0); ks = 0;
+	if (h.obj >= 0) {
+		Lane s;
+		s.ro = o; s.rd = d;
+		shadePrimary(P, s, h);
+		p = s.P; n = s.N; albedo = s.objColor; ks = s.specCoef;
+	}
+	else albedo = skyColor(P, d);
 }
 
 // rtx_cast_rays' hit record (rtxProbeKernel)
@@ -168,28 +205,35 @@ __device__ __forceinline__ void storeHit(const Params& P, const Hit& h, float* o
 	out[3] = h.t; out[4] = hit ? h.u : -1.f; out[5] = hit ? h.v : -1.f; out[6] = 0; out[7] = 0;
 }
 
+// one 12-byte store
+__device__ __forceinline__ void store3(float* out, const V3& v) { out[0] = v.x; out[1] = v.y; out[2] = v.z; }
+
 } // namespace
+
+// The kernels of a family for every scene kind: mesh scenes per (box test of the prune records, culling); scenes without meshes the
+// walk-free form (as rtxPass1Kernel<false, false>).  After the kernel's argument list come its further template arguments, if any.
+#define RTX_MESH_INSTANCES(KERNEL, ARGS, ...)                       \
+template __global__ void KERNEL<true, true, 1, ##__VA_ARGS__> ARGS;    \
+template __global__ void KERNEL<true, false, 1, ##__VA_ARGS__> ARGS;   \
+template __global__ void KERNEL<true, true, 0, ##__VA_ARGS__> ARGS;    \
+template __global__ void KERNEL<true, false, 0, ##__VA_ARGS__> ARGS;
+#define RTX_QUERY_INSTANCES(KERNEL, ARGS, ...)                      \
+RTX_MESH_INSTANCES(KERNEL, ARGS, ##__VA_ARGS__)                        \
+template __global__ void KERNEL<false, true, -1, ##__VA_ARGS__> ARGS;
 
 // Render::trace alone (hits only): no castRay state machine, no LDS park area, no recursion frames.  P.workCounter: this launch's queue
 // head; P.nProbe rays at P.probeRays.
 template <bool MESH, bool BOXES, int CULLK>
 __global__ void __launch_bounds__(256) rtxRayHitKernel(const Params P, const uint32_t* order, float* hits)
 {
-	const uint32_t lane = __lane_id();
-	const uint32_t nWork = (P.nProbe + 63) / 64;
 	Counts cnt = {};
-	for (;;) {
-		const uint32_t work = nextWork(P.workCounter);
-		if (work >= nWork) break;
-		const uint32_t k = work * 64 + lane;
-		const bool valid = k < P.nProbe;
-		uint32_t i; V3 o, d;
-		loadRay(P, order, k, valid, i, o, d);
+	forEachRayWave(P, order, [&](bool valid, uint32_t i, const V3& o, const V3& d) {
 		Hit h;
 		traceWave<false, MESH, false, BOXES, CULLK>(P, valid, false, o, d, kFltMax, h, cnt);
 		if (valid) storeHit(P, h, hits + (size_t)i * 8);
-	}
+	});
 }
+RTX_QUERY_INSTANCES(rtxRayHitKernel, (const Params, const uint32_t*, float*))
 
 // rtx_occluded_rays (include/rtx_query.h): Render::trace of a ShadowRay whose info.tNear starts at the ray's range --
 // one byte per ray, 1 iff some opaque object reports tNear < tmax.  That is "the minimum of tNear over the opaque objects < tmax", which
@@ -198,6 +242,7 @@ __global__ void __launch_bounds__(256) rtxRayHitKernel(const Params P, const uin
 // order (knob occluded_scene_order, for A/B runs).  A lane that is answered takes no further part (traceWave: live / consider), and an
 // object no lane has a question for is not entered (its ballot).  tmax == nullptr: +inf for every ray.
 // No hit record is kept or stored: of the Hit only obj >= 0 is read, so t, tri, u and v of the nearest triangle are dead outside the walk.
+// The loop is forEachRayWave's, written out: inside the helper this kernel measured up to 4.6 % slower.
 template <bool MESH, bool BOXES, int CULLK, bool ORDER>
 __global__ void __launch_bounds__(256) rtxRayOccludedKernel(const Params P, const uint32_t* order, const float* tmax, uint8_t* occluded)
 {
@@ -243,32 +288,30 @@ __global__ void __launch_bounds__(256) rtxRayOccludedKernel(const Params P, cons
 		if (valid) occluded[i] = (asked && !open) ? 1 : 0;
 	}
 }
+RTX_MESH_INSTANCES(rtxRayOccludedKernel, (const Params, const uint32_t*, const float*, uint8_t*), false)
+RTX_QUERY_INSTANCES(rtxRayOccludedKernel, (const Params, const uint32_t*, const float*, uint8_t*), true)
 
 // Render::castRay(ray, scene, 0): the pass-1 kernels' state machine (castRayWave) with CAM = false -- no ray is known to start at the
 // camera.  Recursion frames: the pass-1 area of rtx_scene::frames, indexed by the global lane (the grid is at most blocksPass1).
+// Mesh scenes also per PLAIN.
 template <bool MESH, bool BOXES, int CULLK, bool PLAIN>
 __global__ void __launch_bounds__(256, MESH ? (PLAIN ? RTX_WAVES_PLAIN : RTX_WAVES) : RTX_WAVES_ANALYTIC) rtxRayColourKernel(const Params P, const uint32_t* order, float* colours)
 {
 	if (!PLAIN) fillPowTab();
 	const uint32_t gl = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t lane = __lane_id();
-	const uint32_t nWork = (P.nProbe + 63) / 64;
 	Counts cnt = {};
-	for (;;) {
-		const uint32_t work = nextWork(P.workCounter);
-		if (work >= nWork) break;
-		const uint32_t k = work * 64 + lane;
-		const bool valid = k < P.nProbe;
-		uint32_t i; V3 o, d;
-		loadRay(P, order, k, valid, i, o, d);
+	forEachRayWave(P, order, [&](bool valid, uint32_t i, const V3& o, const V3& d) {
 		V3 c;
 		if constexpr (PLAIN) c = castRayPlainWave<false, false, BOXES, false, CULLK>(P, valid, o, d, gl, cnt);
 		else c = castRayWave<false, MESH, false, BOXES, false, CULLK, PLAIN>(P, valid, o, d, gl, cnt);
-		if (valid) { float* pc = colours + (size_t)i * 3; pc[0] = c.x; pc[1] = c.y; pc[2] = c.z; }
-	}
+		if (valid) store3(colours + (size_t)i * 3, c);
+	});
 }
+RTX_QUERY_INSTANCES(rtxRayColourKernel, (const Params, const uint32_t*, float*), false)
+RTX_MESH_INSTANCES(rtxRayColourKernel, (const Params, const uint32_t*, float*), true)
 
-// RTX_FLAG_SHOW_NORMALS: rtxNormalsKernel's mode 2 through the order; either output may be NULL.
+// RTX_FLAG_SHOW_NORMALS: rtxNormalsKernel's mode 2 through the order; either output may be NULL.  (forEachRayWave's loop, written out: inside
+// the helper this kernel measured about 1 % slower)
 __global__ void __launch_bounds__(256) rtxRayNormalsKernel(const Params P, const uint32_t* order, float* hits, float* colours)
 {
 	const uint32_t lane = __lane_id();
@@ -286,30 +329,6 @@ __global__ void __launch_bounds__(256) rtxRayNormalsKernel(const Params P, const
 		if (valid && colours) { float* pc = colours + (size_t)i * 3; pc[0] = c.x; pc[1] = c.y; pc[2] = c.z; }
 	}
 }
-
-// the kernels of every scene kind: mesh scenes per (box test of the prune records, culling), their colours also per PLAIN; scenes without
-// meshes one of each (as rtxPass1Kernel<false, false>)
-template __global__ void rtxRayHitKernel<true, true, 1>(const Params, const uint32_t*, float*);
-template __global__ void rtxRayHitKernel<true, false, 1>(const Params, const uint32_t*, float*);
-template __global__ void rtxRayHitKernel<true, true, 0>(const Params, const uint32_t*, float*);
-template __global__ void rtxRayHitKernel<true, false, 0>(const Params, const uint32_t*, float*);
-template __global__ void rtxRayHitKernel<false, true, -1>(const Params, const uint32_t*, float*);
-#define RTX_RAY_COLOUR_INSTANCES(PL)                                                                         \
-template __global__ void rtxRayColourKernel<true, true, 1, PL>(const Params, const uint32_t*, float*);     \
-template __global__ void rtxRayColourKernel<true, false, 1, PL>(const Params, const uint32_t*, float*);    \
-template __global__ void rtxRayColourKernel<true, true, 0, PL>(const Params, const uint32_t*, float*);     \
-template __global__ void rtxRayColourKernel<true, false, 0, PL>(const Params, const uint32_t*, float*);
-RTX_RAY_COLOUR_INSTANCES(false) RTX_RAY_COLOUR_INSTANCES(true)
-#undef RTX_RAY_COLOUR_INSTANCES
-template __global__ void rtxRayColourKernel<false, true, -1, false>(const Params, const uint32_t*, float*);
-#define RTX_RAY_OCCLUDED_INSTANCES(ORD)                                                                                       \
-template __global__ void rtxRayOccludedKernel<true, true, 1, ORD>(const Params, const uint32_t*, const float*, uint8_t*);   \
-template __global__ void rtxRayOccludedKernel<true, false, 1, ORD>(const Params, const uint32_t*, const float*, uint8_t*);  \
-template __global__ void rtxRayOccludedKernel<true, true, 0, ORD>(const Params, const uint32_t*, const float*, uint8_t*);   \
-template __global__ void rtxRayOccludedKernel<true, false, 0, ORD>(const Params, const uint32_t*, const float*, uint8_t*);
-RTX_RAY_OCCLUDED_INSTANCES(false) RTX_RAY_OCCLUDED_INSTANCES(true)
-#undef RTX_RAY_OCCLUDED_INSTANCES
-template __global__ void rtxRayOccludedKernel<false, true, -1, true>(const Params, const uint32_t*, const float*, uint8_t*);
 
 // The queue heads of the trace launches ([0] hits, [16] colours), the box of rtxRayBoxKernel ([32, 37) minima as ~0, [37, 42) maxima as 0)
 // and its spreads ([44, 54): five doubles, 0).
