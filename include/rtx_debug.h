@@ -20,6 +20,23 @@ int rtx_set_frame_mode(rtx_scene* scene, int mode); /* -1 measure and choose (de
 int rtx_mesh_flatten_probe(const rtx_mesh* mesh, uint32_t* n_wide, void* wide_out, void* prune_out, uint32_t cap_wide, float* root_rec8);
 int rtx_wide_node_slots(void);      /* slots of a wide node: 8 */
 
+/* Host only (no device is touched): the one-launch-or-three policy of rtx_render_frame (csrc/rtx_frame_plan.h, decideFrameMode).  forced -1 / 0 / 1
+ * (rtx_set_frame_mode combined with the knob), has_list: the call renders some row; of its tile list: fused_gave_up, listed tiles, warm (its
+ * costs are known), frame_samples2 / frame_ms2 (frames measured in three launches and in one, the best time of either), frames_seen;
+ * rule_tiles: the knob frame_rule_tiles of the scene's kind.  *mode 0 three launches, 1 one; *reprobe: the frame's time replaces what was
+ * known of its way; *probing: the frame is bracketed by its own pair of events.  tests/test_frame_plan_cpu.py. */
+int rtx_frame_mode_probe(int forced, int has_list, int fused_gave_up, uint32_t listed, uint32_t rule_tiles, int warm, const uint32_t* frame_samples2,
+                         const float* frame_ms2, uint32_t frames_seen, int* mode, int* reprobe, int* probing);
+
+/* Host only (no device is touched): the pass-1 tile list of the rows [row_begin, row_end) of a width x height view under the row ownership
+ * (band_height, n_parts, part, halo: rtx_set_row_ownership), with the 64 x 1 strips of lone halo rows when strips != 0 and the frame's size allows
+ * them, and the tile rectangle rect4 = {tx0, tx1, ty0, ty1} whose tiles go first in their queues: the words the device is made to write
+ * (csrc/rtx_frame_plan.h: TileGrid, planTileList, expectedTileList) -- [0, 8) the first entry of each of the eight queues, [8, 16) their
+ * lengths, then the entries (ty << 16 | tx, or 0x10000000 | strip << 16 | y).  *need = the words; written to out when cap >= *need (out may
+ * be NULL to ask for the length).  tests/test_frame_plan_cpu.py. */
+int rtx_tile_list_probe(uint32_t width, uint32_t height, uint32_t band_height, uint32_t n_parts, uint32_t part, int halo, uint32_t row_begin, uint32_t row_end,
+                        int strips, const uint32_t* rect4, uint32_t* out, size_t cap, size_t* need);
+
 /* Host only: the P of the source copies of the prune records (rtx_device.h PruneRec, csrc/rtx_source.hip sourceP; DESIGN_HISTORY.md 3.1d)
  * for n triangles given as (v0, e1, e2) = 9 floats each, the source point S3, its radius sigma and cam != 0 when the rays start
  * at S (the camera) rather than pass through it (a point light).  The function the device kernels run, for the CPU tests of the

@@ -41,6 +41,7 @@ RTX_SYMBOLS = [
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
     "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read", "rtx_live_device_memory",
     "rtx_scene_lights_read", "rtx_scene_mesh_prune_copy_read", "rtx_scene_objects_read",
+    "rtx_frame_mode_probe", "rtx_tile_list_probe",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
@@ -121,6 +122,8 @@ def load():
     rtx.rtx_cost_grid_read.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     rtx.rtx_mesh_flatten_probe.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp, C.c_uint32, vp]
     rtx.rtx_source_p_probe.argtypes = [vp, u32, vp, C.c_double, i32, vp]
+    rtx.rtx_frame_mode_probe.argtypes = [i32, i32, i32, u32, u32, i32, vp, vp, u32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    rtx.rtx_tile_list_probe.argtypes = [u32, u32, u32, u32, u32, i32, u32, u32, i32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     rtx.rtx_frame_mode.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     rtx.rtx_quantize_bgr8.argtypes = [vp, vp, vp, vp]
     rtx.rtx_render_frame_host.argtypes = [vp, i32, vp]
@@ -487,6 +490,31 @@ def source_p_probe(v0, e1, e2, S, sigma, cam):
     S = np.ascontiguousarray(S, np.float64)
     out = np.zeros(len(t), np.float32)
     _check(rtx.rtx_source_p_probe(_np_ptr(t), len(t), _np_ptr(S), float(sigma), 1 if cam else 0, _np_ptr(out)), "rtx_source_p_probe")
+    return out
+
+
+def frame_mode_probe(forced, has_list, fused_gave_up, listed, rule_tiles, warm, frame_samples, frame_ms, frames_seen):
+    """Host only: (mode, reprobe, probing) of rtx_render_frame's one-launch-or-three policy (rtx_frame_mode_probe; csrc/rtx_frame_plan.h)."""
+    rtx, _ = load()
+    n = np.ascontiguousarray(frame_samples, np.uint32); ms = np.ascontiguousarray(frame_ms, np.float32)
+    assert n.shape == (2,) and ms.shape == (2,)
+    mode, reprobe, probing = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    _check(rtx.rtx_frame_mode_probe(int(forced), int(has_list), int(fused_gave_up), int(listed), int(rule_tiles), int(warm), _np_ptr(n), _np_ptr(ms),
+                                    int(frames_seen), C.byref(mode), C.byref(reprobe), C.byref(probing)), "rtx_frame_mode_probe")
+    return mode.value, bool(reprobe.value), bool(probing.value)
+
+
+def tile_list_probe(width, height, ownership, rows, strips, rect):
+    """Host only: the words of the pass-1 tile list (header of 16, then the eight queues) of the rows `rows` of a width x height view under
+    ownership = (band_height, n_parts, part, halo), with the mesh tile rectangle rect = (tx0, tx1, ty0, ty1) (rtx_tile_list_probe)."""
+    rtx, _ = load()
+    r = np.ascontiguousarray(rect, np.uint32)
+    assert r.shape == (4,)
+    args = [int(width), int(height)] + [int(x) for x in ownership] + [int(rows[0]), int(rows[1]), 1 if strips else 0, _np_ptr(r)]
+    need = C.c_size_t(0)
+    _check(rtx.rtx_tile_list_probe(*args, None, 0, C.byref(need)), "rtx_tile_list_probe")
+    out = np.zeros(need.value, np.uint32)
+    _check(rtx.rtx_tile_list_probe(*args, _np_ptr(out), out.size, C.byref(need)), "rtx_tile_list_probe")
     return out
 
 

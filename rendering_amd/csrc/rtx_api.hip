@@ -23,6 +23,7 @@
 #include "../../include/rtx_ao.h"
 #include "../../include/rtx_surface.h"
 #include "rtx_device.h"
+#include "rtx_frame_plan.h"
 #include "rtx_own.h"
 
 using namespace rtxd;
@@ -193,11 +194,9 @@ struct rtx_scene {
 		bool fusedGaveUp = false;         // the single launch once ended with an error for this view: three launches from then on
 		hipStream_t builtOn = nullptr; Event builtEv;      // the stream rtxTileListKernel wrote the list on, and its completion
 		// the entry is about to hold another list, or its view's geometry has changed: what was measured on it no longer applies
-		void forget()
-		{
-			key.clear(); costValid = false;
-			frameMs[0] = frameMs[1] = -1.f; frameSamples[0] = frameSamples[1] = 0; framesSeen = 0; generation++; fusedGaveUp = false;
-		}
+		void forget() { key.clear(); costValid = false; forgetMeasurements(); }
+		// ... or the kernel family has changed (rtx_scene_set_lights): only the frame-mode measurements go
+		void forgetMeasurements() { frameMs[0] = frameMs[1] = -1.f; frameSamples[0] = frameSamples[1] = 0; framesSeen = 0; generation++; fusedGaveUp = false; }
 	};
 	// the last frame rendered in one launch (rtx_frame_status renders it again in three if the launch gave up)
 	// (only while nothing it depends on has changed: the view and the row ownership it was rendered with are part of it, and
@@ -1245,91 +1244,46 @@ void meshTileRect(const rtx_scene* s, uint32_t tilesX, uint32_t tilesYFull, uint
 	}
 }
 
-// A strip entry is 0x10000000 | strip << 16 | y: it needs y < 2^15, strip < 2^12, and plain entries (ty << 16 | tx) that never
-// set bit 28, i.e. tile rows below 4096.  Larger frames are listed as tiles only and the kernels are told so (Params::stripBit).
-bool stripsFit(const View& v) { return v.height <= 32768u && v.width <= 262144u; }
+using rtxplan::TileGrid; using rtxplan::TilePlan; using rtxplan::stripsFit;
 
-// The eight per-XCD queues of one pass-1 launch.  Only tiles with a row this launch renders are listed.
-// strips (the three-launch path): a tile row of which this launch renders a single pixel row -- the halo row of a band
-// that belongs to another device -- is listed as 64 x 1 pixel strips (0x10000000 | strip << 16 | y) instead of 8 x 8
-// tiles with one live row each: a wave's time goes into walking its bundle whatever the number of live lanes, and the
-// halo rows are a quarter of the tile rows of a 64-row band.
-int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t tilesX, uint32_t tileRow0, uint32_t tilesY, rtx_scene::TileQueues** out, bool strips, hipStream_t st)
+// The steps of buildTileList, in its order.  The key: what a list is built for (view, row range, row ownership).
+void tileListKey(const Params& p, uint32_t rowBegin, uint32_t lastRow, uint32_t tilesX, bool strips, std::vector<uint32_t>& key)
 {
-	const Params& p = s->params;
-	if (!stripsFit(p.view)) strips = false;
-	std::vector<uint32_t> key = { rowBegin, lastRow, tilesX, p.bandH, p.nParts, p.part, p.halo, p.view.width, p.view.height, strips ? 1u : 0u };
+	key = { rowBegin, lastRow, tilesX, p.bandH, p.nParts, p.part, p.halo, p.view.width, p.view.height, strips ? 1u : 0u };
 	for (int i = 0; i < 16; i++) { uint32_t w; memcpy(&w, &p.view.camM[i], 4); key.push_back(w); }
 	for (int i = 0; i < 3; i++) { uint32_t w; memcpy(&w, &p.view.camPos[i], 4); key.push_back(w); }
 	{ uint32_t w; memcpy(&w, &p.view.scale, 4); key.push_back(w); memcpy(&w, &p.view.aspect, 4); key.push_back(w); }
+}
+
+// The cached list with this key (*out; none: nullptr), ordered in front of what `st` is given next.
+int findTileList(rtx_scene* s, const std::vector<uint32_t>& key, hipStream_t st, rtx_scene::TileQueues** out)
+{
+	*out = nullptr;
 	for (auto& q : s->tileQueues)
 		if (q.list && q.key == key) {
 			// (written on another stream -- the null stream of prepareView is covered by evPrepDone, a caller's second render stream is not: ADVICE r5)
 			if (q.builtEv && q.builtOn != st && q.builtOn != nullptr && st != nullptr) HIPCHK(hipStreamWaitEvent(st, q.builtEv, 0));
 			q.lastUse = ++s->tileUse; *out = &q; return RTX_OK;
 		}
-	// new entry (the least recently used one is recycled once there are 16; callers keep pointers to entries across calls
-	// that may add one: the vector never reallocates)
+	return RTX_OK;
+}
+
+// new entry (the least recently used one is recycled once there are 16; callers keep pointers to entries across calls
+// that may add one: the vector never reallocates)
+rtx_scene::TileQueues* recycleTileList(rtx_scene* s)
+{
 	if (s->tileQueues.capacity() < 16) s->tileQueues.reserve(16);
 	if (s->tileQueues.size() < 16) s->tileQueues.emplace_back();
 	rtx_scene::TileQueues* e = &s->tileQueues[0];
 	for (auto& q : s->tileQueues) { if (!q.list) { e = &q; break; } if (q.lastUse < e->lastUse) e = &q; }
 	e->forget();
-	const uint32_t H = p.view.height;
-	auto rowOwnedH = [&](uint32_t y) { return p.bandH == 0 || (y / p.bandH) % p.nParts == p.part; };
-	auto rowRenderedH = [&](uint32_t y) {
-		if (rowOwnedH(y)) return true;
-		if (!p.halo) return false;
-		return (y > 0 && rowOwnedH(y - 1)) || rowOwnedH(y + 1);
-	};
-	uint32_t rect[4];
-	meshTileRect(s, tilesX, (H + 7) / 8, rect);
-	// The plan: per tile row what it is listed as, its queue and class bases (rtx_kernels.hip, rtxTileListKernel).  O(rows) here, the entries are written
-	// on the device -- a new view used to cost the host a loop over every tile (262 144 at 4096^2) and a synchronous 1-MB copy.
-	const uint32_t W1 = p.view.width - 1;                        // (the last column is never rendered)
-	const uint32_t nStrips = (W1 + 63) / 64;
-	const uint32_t in0 = std::min(rect[0], tilesX), in1 = std::min(rect[1], tilesX);
-	uint32_t sIn0 = nStrips, sIn1 = 0;                            // strips sx with min(sx * 8 + 8, tilesX) > rect[0] && sx * 8 < rect[1]: a contiguous range
-	for (uint32_t sx = 0; sx < nStrips; sx++) {
-		const uint32_t tx0 = sx * 8, tx1 = std::min(tx0 + 8, tilesX);
-		if (tx1 > rect[0] && tx0 < rect[1]) { sIn0 = std::min(sIn0, sx); sIn1 = std::max(sIn1, sx + 1); }
-	}
-	std::vector<uint32_t> plan(16 + 4 * (size_t)tilesY, 0u);
-	uint32_t cnt[8][2] = {};
-	std::vector<uint8_t> rowQueue(tilesY);
-	for (uint32_t t = 0; t < tilesY; t++) {
-		const uint32_t ty = tileRow0 + t;
-		uint32_t live = 0, only = 0;
-		for (uint32_t y = std::max(ty * 8, rowBegin); y < std::min(ty * 8 + 8, lastRow); y++) if (rowRenderedH(y)) { live++; only = y; }
-		if (!live) continue;
-		// queue = XCD: bands of 8 tile rows are dealt round the eight queues.  When the rows are shared among devices it is
-		// the bands of THIS device that are dealt round (band p, p + nParts, ... of the frame would otherwise all land in
-		// queue p % 8 for 8 devices, and every wave of the chip would pop from one address); a halo row goes with the band
-		// it serves.
-		uint32_t xq = (t / 8) & 7u;
-		if (p.bandH) {
-			uint32_t b = only / p.bandH;
-			if (!rowOwnedH(only)) b = (only > 0 && rowOwnedH(only - 1)) ? (only - 1) / p.bandH : (only + 1) / p.bandH;
-			xq = ((b / p.nParts) * (p.bandH / 64 ? p.bandH / 64 : 1) + (only % p.bandH) / 64) & 7u;
-		}
-		const bool inY = ty >= rect[2] && ty < rect[3];
-		const bool strip = strips && live == 1;
-		const uint32_t n = strip ? nStrips : tilesX;
-		const uint32_t nIn = !inY ? 0u : (strip ? (sIn1 > sIn0 ? sIn1 - sIn0 : 0u) : (in1 > in0 ? in1 - in0 : 0u));
-		plan[16 + 4 * t] = (strip ? 2u : 1u) | (inY ? 0x100u : 0u);
-		plan[17 + 4 * t] = strip ? only : ty;
-		plan[18 + 4 * t] = cnt[xq][0]; plan[19 + 4 * t] = cnt[xq][1];      // (relative to the class: made absolute below)
-		cnt[xq][0] += nIn; cnt[xq][1] += n - nIn;
-		rowQueue[t] = (uint8_t)xq;
-	}
-	uint32_t qBase[8], total = 16;
-	for (int x = 0; x < 8; x++) { qBase[x] = total; plan[x] = total; plan[8 + x] = cnt[x][0] + cnt[x][1]; total += cnt[x][0] + cnt[x][1]; }
-	for (uint32_t t = 0; t < tilesY; t++) {
-		if (!plan[16 + 4 * t]) continue;
-		const uint32_t x = rowQueue[t];
-		plan[18 + 4 * t] += qBase[x]; plan[19 + 4 * t] += qBase[x] + cnt[x][0];
-	}
-	const size_t listWords = total;
+	return e;
+}
+
+// Room for a list of listWords in entry e's part of the slab, and for its ordered copy.
+int ensureListSlabs(rtx_scene* s, rtx_scene::TileQueues* e, size_t listWords)
+{
+	const Params& p = s->params;
 	// (every list of this view fits 16 + the frame's tiles: a strip row has fewer entries than a tile row.  Sized for that at once, so that the
 	// second list of a frame -- tiles after strips, an owned band after the whole frame -- never grows the slab under a `tq` the caller holds: ADVICE r5)
 	const size_t frameWords = 16 + (size_t)((p.view.width + 7) / 8) * ((p.view.height + 7) / 8);
@@ -1348,67 +1302,78 @@ int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t ti
 		HIPCHK(hipDeviceSynchronize());
 		HIPCHK(s->orderedList.reserve(16 * std::max(listWords, frameWords)));
 	}
-	// The plan goes through a ring of pinned host buffers the kernel reads directly; a slot is taken again eight lists later (its event says whether the
-	// kernel that read it has run: it has, unless eight views were set without the device getting a turn).  The list that is recycled may still be read
-	// by an earlier launch: the kernel runs on the stream `st` the CALLER renders on (every render entry point passes its own; prepareView the null stream,
-	// ordered by prepBegin / prepEnd), behind that launch.
-	{
-		if (!s->planRing[0].host) {
-			// all eight slots in one pinned allocation, on first use (rtx_scene_create: not on the path of a new view), each good for 2 048 tile rows
-			const size_t each = 16 + 4 * 2048;
-			HIPCHK(s->planRingBase.reserve(8 * each));
-			for (int k = 0; k < 8; k++) {
-				s->planRing[k].host = s->planRingBase.host() + k * each; s->planRing[k].dev = s->planRingBase.dev() + k * each; s->planRing[k].capWords = each;
-				HIPCHK(s->planRing[k].done.create(hipEventDisableTiming));
-			}
+	return RTX_OK;
+}
+
+// The plan goes through a ring of pinned host buffers the kernel reads directly; a slot is taken again eight lists later (its event says whether the
+// kernel that read it has run: it has, unless eight views were set without the device getting a turn).  The list that is recycled may still be read
+// by an earlier launch: the kernel runs on the stream `st` the CALLER renders on (every render entry point passes its own; prepareView the null stream,
+// ordered by prepBegin / prepEnd), behind that launch.
+int launchTileList(rtx_scene* s, rtx_scene::TileQueues* e, const TilePlan& pl, uint32_t tilesX, uint32_t tilesY, hipStream_t st)
+{
+	if (!s->planRing[0].host) {
+		// all eight slots in one pinned allocation, on first use (rtx_scene_create: not on the path of a new view), each good for 2 048 tile rows
+		const size_t each = 16 + 4 * 2048;
+		HIPCHK(s->planRingBase.reserve(8 * each));
+		for (int k = 0; k < 8; k++) {
+			s->planRing[k].host = s->planRingBase.host() + k * each; s->planRing[k].dev = s->planRingBase.dev() + k * each; s->planRing[k].capWords = each;
+			HIPCHK(s->planRing[k].done.create(hipEventDisableTiming));
 		}
-		rtx_scene::PlanSlot& slot = s->planRing[s->planNext++ & 7u];
-		if (slot.used) HIPCHK(hipEventSynchronize(slot.done));
-		if (plan.size() > slot.capWords) {
-			// (its part of the common allocation is simply left behind)
-			slot.host = slot.dev = nullptr; slot.capWords = 0;
-			const size_t want = std::max<size_t>(plan.size(), 16 + 4 * 1100);
-			HIPCHK(slot.own.reserve(want));
-			slot.host = slot.own.host(); slot.dev = slot.own.dev(); slot.capWords = want;
-		}
-		HIPCHK(slot.done.create(hipEventDisableTiming));
-		memcpy(slot.host, plan.data(), plan.size() * sizeof(uint32_t));
-		const uint32_t cols = std::max(std::max(tilesX, nStrips), 16u);
-		hipLaunchKernelGGL(rtxTileListKernel, dim3((cols + 255) / 256, std::max(tilesY, 1u)), dim3(256), 0, st, (const uint32_t*)slot.dev, tilesX, nStrips, in0, in1, sIn0, sIn1, e->list);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(slot.done, st));
-		slot.used = true;
-		HIPCHK(e->builtEv.create(hipEventDisableTiming));
-		HIPCHK(hipEventRecord(e->builtEv, st));
-		e->builtOn = st;
 	}
-	if (s->verifyLists) {
-		// (tests: the straightforward construction on the host -- one entry after the other, the way rounds 1-4 built the list -- against what the device wrote)
-		std::vector<uint32_t> q[8][2];
-		for (uint32_t t = 0; t < tilesY; t++) {
-			const uint32_t kind = plan[16 + 4 * t];
-			if (!kind) continue;
-			const uint32_t xq = rowQueue[t], val = plan[17 + 4 * t];
-			const bool inY = (kind & 0x100u) != 0;
-			if ((kind & 0xffu) == 2u)
-				for (uint32_t sx = 0; sx * 64 < W1; sx++) {
-					const uint32_t tx0 = sx * 8, tx1 = std::min(tx0 + 8, tilesX);
-					q[xq][(inY && tx1 > rect[0] && tx0 < rect[1]) ? 0 : 1].push_back(0x10000000u | sx << 16 | val);
-				}
-			else for (uint32_t tx = 0; tx < tilesX; tx++) q[xq][(inY && tx >= rect[0] && tx < rect[1]) ? 0 : 1].push_back(val << 16 | tx);
-		}
-		std::vector<uint32_t> want(16), got(listWords);
-		for (int x = 0; x < 8; x++) {
-			want[x] = (uint32_t)want.size();
-			want[8 + x] = (uint32_t)(q[x][0].size() + q[x][1].size());
-			want.insert(want.end(), q[x][0].begin(), q[x][0].end());
-			want.insert(want.end(), q[x][1].begin(), q[x][1].end());
-		}
-		HIPCHK(hipStreamSynchronize(st));
-		HIPCHK(hipMemcpy(got.data(), e->list, listWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		if (want != got) return fail(RTX_ERR_DEVICE, "buildTileList: the list written on the device differs from the host's construction");
+	rtx_scene::PlanSlot& slot = s->planRing[s->planNext++ & 7u];
+	if (slot.used) HIPCHK(hipEventSynchronize(slot.done));
+	if (pl.words.size() > slot.capWords) {
+		// (its part of the common allocation is simply left behind)
+		slot.host = slot.dev = nullptr; slot.capWords = 0;
+		const size_t want = std::max<size_t>(pl.words.size(), 16 + 4 * 1100);
+		HIPCHK(slot.own.reserve(want));
+		slot.host = slot.own.host(); slot.dev = slot.own.dev(); slot.capWords = want;
 	}
-	e->listed = (uint32_t)(listWords - 16);
+	HIPCHK(slot.done.create(hipEventDisableTiming));
+	memcpy(slot.host, pl.words.data(), pl.words.size() * sizeof(uint32_t));
+	const uint32_t cols = std::max(std::max(tilesX, pl.nStrips), 16u);
+	hipLaunchKernelGGL(rtxTileListKernel, dim3((cols + 255) / 256, std::max(tilesY, 1u)), dim3(256), 0, st, (const uint32_t*)slot.dev, tilesX, pl.nStrips, pl.in0, pl.in1, pl.sIn0, pl.sIn1, e->list);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(slot.done, st));
+	slot.used = true;
+	HIPCHK(e->builtEv.create(hipEventDisableTiming));
+	HIPCHK(hipEventRecord(e->builtEv, st));
+	e->builtOn = st;
+	return RTX_OK;
+}
+
+// knob verify_lists: what the device wrote against the host's construction (rtx_frame_plan.h, expectedTileList)
+int verifyTileList(rtx_scene* s, const rtx_scene::TileQueues* e, const TilePlan& pl, uint32_t tilesX, uint32_t tilesY, const uint32_t rect[4], hipStream_t st)
+{
+	const std::vector<uint32_t> want = rtxplan::expectedTileList(s->params.view.width, tilesX, tilesY, rect, pl);
+	std::vector<uint32_t> got(pl.listWords);
+	HIPCHK(hipStreamSynchronize(st));
+	HIPCHK(hipMemcpy(got.data(), e->list, pl.listWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (want != got) return fail(RTX_ERR_DEVICE, "buildTileList: the list written on the device differs from the host's construction");
+	return RTX_OK;
+}
+
+// The eight per-XCD queues of one pass-1 launch.  Only tiles with a row this launch renders are listed.
+// strips (the three-launch path): a tile row of which this launch renders a single pixel row -- the halo row of a band
+// that belongs to another device -- is listed as 64 x 1 pixel strips (0x10000000 | strip << 16 | y) instead of 8 x 8
+// tiles with one live row each: a wave's time goes into walking its bundle whatever the number of live lanes, and the
+// halo rows are a quarter of the tile rows of a 64-row band.
+int buildTileList(rtx_scene* s, uint32_t rowBegin, uint32_t lastRow, uint32_t tilesX, uint32_t tileRow0, uint32_t tilesY, rtx_scene::TileQueues** out, bool strips, hipStream_t st)
+{
+	const Params& p = s->params;
+	if (!stripsFit(p.view.width, p.view.height)) strips = false;
+	std::vector<uint32_t> key;
+	tileListKey(p, rowBegin, lastRow, tilesX, strips, key);
+	int rc = findTileList(s, key, st, out);
+	if (rc || *out) return rc;
+	rtx_scene::TileQueues* e = recycleTileList(s);
+	uint32_t rect[4];
+	meshTileRect(s, tilesX, (p.view.height + 7) / 8, rect);
+	const TilePlan plan = rtxplan::planTileList(p.view.width, { p.bandH, p.nParts, p.part, p.halo }, rowBegin, lastRow, tilesX, tileRow0, tilesY, strips, rect);
+	if ((rc = ensureListSlabs(s, e, plan.listWords))) return rc;
+	if ((rc = launchTileList(s, e, plan, tilesX, tilesY, st))) return rc;
+	if (s->verifyLists && (rc = verifyTileList(s, e, plan, tilesX, tilesY, rect, st))) return rc;
+	e->listed = (uint32_t)(plan.listWords - 16);
 	e->needValid = false;      // (computed on the device when the single launch first uses this list: renderFrameFused)
 	e->key = key;
 	e->lastUse = ++s->tileUse;
@@ -1454,15 +1419,15 @@ int prepareView(rtx_scene* s)
 	if ((rc = estimateCosts(s))) return rc;
 	const View& v = s->params.view;
 	if (v.width > 0xffffu || v.height > 0xffffu || s->params.bandH) return RTX_OK;
-	const uint32_t tilesX = (v.width - 1 + 7) / 8, lastRow = v.height - 1;
-	if (lastRow == 0) return RTX_OK;
+	const TileGrid g(v.width, v.height, 0, v.height);
+	if (g.noRenderedRow()) return RTX_OK;
 	rtx_scene::TileQueues* tq = nullptr;
-	if ((rc = buildTileList(s, 0, lastRow, tilesX, 0, (lastRow + 7) / 8, &tq, true, nullptr))) return rc;
+	if ((rc = buildTileList(s, 0, g.lastRow, g.tilesX, 0, g.tilesY, &tq, true, nullptr))) return rc;
 	// the list and the buffers of the single launch: only where rtx_render_frame may take it (frames of more tiles render in three launches by rule)
 	const uint32_t ruleTiles = s->analytic ? s->knobs.frameRuleTilesAnalytic : s->knobs.frameRuleTiles;
 	if (tq->listed > ruleTiles && s->knobs.frameMode != 1 && s->frameModeForced != 1) return RTX_OK;
-	if ((rc = buildTileList(s, 0, lastRow, tilesX, 0, (lastRow + 7) / 8, &tq, false, nullptr))) return rc;
-	const size_t tiles = (size_t)((v.width + 7) / 8) * ((v.height + 7) / 8);
+	if ((rc = buildTileList(s, 0, g.lastRow, g.tilesX, 0, g.tilesY, &tq, false, nullptr))) return rc;
+	const size_t tiles = (size_t)g.tilesXFull * g.tilesYFull;
 	size_t perQueue = 0;
 	if (tiles < (1u << 24) && (rc = ensureFrameBuffers(s, tiles, &perQueue))) return rc;
 	return RTX_OK;
@@ -1477,23 +1442,16 @@ namespace {
 // tile costs and the frame-mode measurements of the ordinary frames are neither used nor touched.
 bool showNormals(const rtx_scene* s) { return (s->params.view.flags & RTX_FLAG_SHOW_NORMALS) != 0; }
 
-// The plain grid over the 8x8 tiles of pass 1's pixels in the rows [rowBegin, rowEnd) (clamped to the view), one wave per tile: p's row range,
-// tilesX, tileRow0 and nTiles; the launch takes (nTiles + 3) / 4 blocks.  Neither the tile lists nor the tile costs are read or written.
+// The plain grid over the 8x8 tiles of pass 1's pixels in the rows [rowBegin, rowEnd) (clamped to the view), one wave per tile: p's TileGrid;
+// the launch takes (nTiles + 3) / 4 blocks.  Neither the tile lists nor the tile costs are read or written.
 // false: the call ends here with rc -- no such pixel (RTX_OK), or a frame too large.
 bool plainTileGrid(const rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, Params& p, int& rc)
 {
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
+	const TileGrid g(s->params.view.width, s->params.view.height, rowBegin, rowEnd);
 	rc = RTX_OK;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return false;
-	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
-	if (lastRow <= rowBegin) return false;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.tilesX = (W - 1 + 7) / 8;
-	p.tileRow0 = rowBegin / 8;
-	const size_t tiles = (size_t)p.tilesX * ((lastRow + 7) / 8 - p.tileRow0);
-	if (tiles >= (1u << 30)) { rc = fail(RTX_ERR_ARG, "frame too large"); return false; }
-	p.nTiles = (uint32_t)tiles;
+	if (g.noRows() || g.noRenderedRow()) return false;
+	if (g.nTiles >= (1u << 30)) { rc = fail(RTX_ERR_ARG, "frame too large"); return false; }
+	g.writeTo(p);
 	return true;
 }
 
@@ -1517,7 +1475,7 @@ int normalsSsaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, uint32
 	Params p = s->params;
 	p.fb = fb_dev;
 	p.ssaaMask = mask_dev;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
+	p.rowBegin = rowBegin; p.rowEnd = rowEnd;      // (clamped by rtx_render_ssaa's TileGrid)
 	const size_t waves = ((size_t)(rowEnd - rowBegin) * W + 15) / 16;
 	if (waves >= (1ull << 32)) return fail(RTX_ERR_ARG, "frame too large");
 	int rc = stamp(s, 2, st);
@@ -1527,48 +1485,57 @@ int normalsSsaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, uint32
 	return stamp(s, 2, st);
 }
 
+// The tile list of the next launch in the order of rtxTileOrderKernel, into s->orderedList: the count of the cost classes (only where the queues
+// are long), then the placement.  What differs between the callers: pass 1 orders its strips and has the queue heads zeroed, the single
+// launch splits slow tiles (classes, cost sum, waves, limits); the defaults are the kernel's.
+struct TileOrderArgs {
+	const uint8_t* classes = nullptr; const unsigned long long* costSum = nullptr; uint32_t nWaves = 1, splitPercent = 0, splitFloor = 0; uint32_t* thresholds = nullptr;
+	uint32_t tilesX = 0, stripLimit = 0xffffffffu; uint32_t* heads = nullptr; uint32_t stripBit = 0;
+};
+void orderTiles(rtx_scene* s, const rtx_scene::TileQueues* tq, const TileOrderArgs& a, hipStream_t st)
+{
+	const unsigned pieces = tq->listed > 16384u ? 32u : 1u;      // (short queues: one block each, one launch)
+	if (pieces > 1) hipLaunchKernelGGL(rtxTileOrderKernel<false>, dim3(pieces, 8), dim3(256), 0, st, s->orderWork, tq->list, s->tileCost, s->params.tilesXFull, s->orderedList, a.classes,
+	                   a.costSum, a.nWaves, a.splitPercent, a.splitFloor, a.thresholds, a.tilesX, a.stripLimit, (uint32_t*)nullptr, a.stripBit);
+	hipLaunchKernelGGL(rtxTileOrderKernel<true>, dim3(pieces, 8), dim3(256), 0, st, s->orderWork, tq->list, s->tileCost, s->params.tilesXFull, s->orderedList, a.classes,
+	                   a.costSum, a.nWaves, a.splitPercent, a.splitFloor, a.thresholds, a.tilesX, a.stripLimit, a.heads, a.stripBit);      // (also zeroes the queue heads it is given)
+}
+
+// (the open event pair of `which` is dropped with the launch that failed)
+void dropOpenStamp(rtx_scene* s, int which) { if (s->evUsed[which] & 1) s->evUsed[which]--; }
+
 } // namespace
 
 int rtx_render_pass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, void* stream)
 {
 	RoctxRange range("Render scene (rtx_render_pass1)");
 	if (!s || !fb_dev) return fail(RTX_ERR_ARG, "scene/fb is NULL");
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
+	const TileGrid g(s->params.view.width, s->params.view.height, rowBegin, rowEnd);
+	if (g.noRows()) return RTX_OK;
 	int rc = ensureWork(s);
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (int ro = renderOn(s, st)) return ro;
-	if (showNormals(s)) return normalsPass1(s, rowBegin, rowEnd, fb_dev, st);
+	if (showNormals(s)) return normalsPass1(s, rowBegin, g.rowEnd, fb_dev, st);
+	if (g.noRenderedRow()) return RTX_OK;
 	Params p = s->params;
 	p.fb = fb_dev;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.tilesX = (W - 1 + 7) / 8;
-	p.tileRow0 = rowBegin / 8;
-	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
-	if (lastRow <= rowBegin) return RTX_OK;
-	const uint32_t tilesY = (lastRow + 7) / 8 - p.tileRow0;
-	p.nTiles = p.tilesX * tilesY;
-	p.tilesY = tilesY;
+	g.writeTo(p);
 #if RTX_DBG
 	p.pad3 = s->knobs.dbgTile;
 #endif
 	p.workCounter = s->work + 128;            // eight per-XCD queue heads, 64 bytes apart
 	if (p.view.width > 0x7fff8u || p.view.height > 0x7fff8u) return fail(RTX_ERR_ARG, "frame too large");
 	rtx_scene::TileQueues* tq = nullptr;
-	if ((rc = buildTileList(s, rowBegin, lastRow, p.tilesX, p.tileRow0, tilesY, &tq, true, st))) return rc;
+	if ((rc = buildTileList(s, rowBegin, g.lastRow, g.tilesX, g.tileRow0, g.tilesY, &tq, true, st))) return rc;
 	p.tileList = tq->list;
-	p.stripBit = stripsFit(p.view) ? 0x10000000u : 0u;
+	p.stripBit = stripsFit(p.view.width, p.view.height) ? 0x10000000u : 0u;
 	if (tq->costValid || s->costsUsable) {
 		// the previous launch rendered exactly these tiles from this view (or their costs are estimated: estimateCosts): start with the expensive ones
-		const uint32_t stripLimit = s->knobs.stripLimit;
 		// (a strip of a halo row that took more than 1 ms is listed as its tiles again: rtxTileOrderKernel)
-		const unsigned pieces = tq->listed > 16384u ? 32u : 1u;      // (short queues: one block each, one launch)
-		if (pieces > 1) hipLaunchKernelGGL(rtxTileOrderKernel<false>, dim3(pieces, 8), dim3(256), 0, st, s->orderWork, tq->list, s->tileCost, s->params.tilesXFull, s->orderedList, (const uint8_t*)nullptr,
-		                   (const unsigned long long*)nullptr, 1u, 0u, 0u, (uint32_t*)nullptr, p.tilesX, stripLimit, (uint32_t*)nullptr, p.stripBit);
-		hipLaunchKernelGGL(rtxTileOrderKernel<true>, dim3(pieces, 8), dim3(256), 0, st, s->orderWork, tq->list, s->tileCost, s->params.tilesXFull, s->orderedList, (const uint8_t*)nullptr,
-		                   (const unsigned long long*)nullptr, 1u, 0u, 0u, (uint32_t*)nullptr, p.tilesX, stripLimit, s->work + 128, p.stripBit);      // (also zeroes the queue heads)
+		TileOrderArgs a;
+		a.tilesX = g.tilesX; a.stripLimit = s->knobs.stripLimit; a.heads = s->work + 128; a.stripBit = p.stripBit;
+		orderTiles(s, tq, a, st);
 		p.tileList = s->orderedList;
 	}
 	else HIPCHK(hipMemsetAsync(s->work + 128, 0, 128 * sizeof(uint32_t), st));
@@ -1587,32 +1554,27 @@ int rtx_render_pass1(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb
 static int renderFrameFused(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, uint8_t* mask_dev, void* stream, bool costsKnown)
 {
 	RoctxRange range("one launch (rtxFrameKernel)");
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
+	const uint32_t W = s->params.view.width;
+	const TileGrid g(W, s->params.view.height, rowBegin, rowEnd);
+	if (g.noRows()) return RTX_OK;
+	rowEnd = g.rowEnd;
 	int rc = ensureWork(s);
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	Params p = s->params;
 	p.fb = fb_dev;
 	p.maskOut = mask_dev;
-	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.tilesX = (W - 1 + 7) / 8;
-	p.tileRow0 = rowBegin / 8;
+	g.writeTo(p);
 	if (p.view.width > 0xffffu || p.view.height > 0xffffu) return fail(RTX_ERR_ARG, "frame too large");
 	// the mask of the rows is defined everywhere: 0 where no tile computes it (rows of other parts, the last row / column)
 	const size_t maskBytes = (size_t)(rowEnd - rowBegin) * W;
 	const bool maskInClear = maskBytes <= (4u << 20);      // (a small frame: cleared by rtxFrameClearKernel below)
-	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);   // exclusive; row H-1 is never rendered
-	if (!maskInClear || lastRow <= rowBegin) HIPCHK(hipMemsetAsync(mask_dev + (size_t)rowBegin * W, 0, maskBytes, st));
-	if (lastRow <= rowBegin) return RTX_OK;
-	const uint32_t tilesY = (lastRow + 7) / 8 - p.tileRow0;
-	p.nTiles = p.tilesX * tilesY;
-	p.tilesY = tilesY;
-	p.tilesYFull = (H + 7) / 8;
+	if (!maskInClear || g.noRenderedRow()) HIPCHK(hipMemsetAsync(mask_dev + (size_t)rowBegin * W, 0, maskBytes, st));
+	if (g.noRenderedRow()) return RTX_OK;
+	p.tilesYFull = g.tilesYFull;
 	p.workCounter = s->work + 128;            // eight per-XCD queue heads, 64 bytes apart
 	rtx_scene::TileQueues* tq = nullptr;
-	if ((rc = buildTileList(s, rowBegin, lastRow, p.tilesX, p.tileRow0, tilesY, &tq, false, st))) return rc;
+	if ((rc = buildTileList(s, rowBegin, g.lastRow, g.tilesX, g.tileRow0, g.tilesY, &tq, false, st))) return rc;
 	const size_t tiles = (size_t)p.tilesXFull * p.tilesYFull;
 	size_t perQueue = 0;
 	if ((rc = ensureFrameBuffers(s, tiles, &perQueue))) return rc;
@@ -1660,12 +1622,11 @@ static int renderFrameFused(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, fl
 	if (ordered) {
 		// the previous launch rendered exactly these tiles from this view: start with the ones that were expensive
 		hipLaunchKernelGGL(rtxTileClassKernel, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, st, s->tileCost, p.tilesXFull, p.tilesYFull, s->tileClass, (unsigned long long*)(s->work + 16));
-		const uint32_t splitPercent = s->knobs.splitPercent, splitFloor = 2000u;            // floor: 20 us (100 MHz)
-		const unsigned pieces = tq->listed > 16384u ? 32u : 1u;      // (short queues: one block each, one launch)
-		if (pieces > 1) hipLaunchKernelGGL(rtxTileOrderKernel<false>, dim3(pieces, 8), dim3(256), 0, st, s->orderWork, tq->list, s->tileCost, s->params.tilesXFull, s->orderedList, (const uint8_t*)s->tileClass,
-		                   (const unsigned long long*)(s->work + 16), (uint32_t)s->blocksFrame * 4u, splitPercent, splitFloor, s->work + 18);
-		hipLaunchKernelGGL(rtxTileOrderKernel<true>, dim3(pieces, 8), dim3(256), 0, st, s->orderWork, tq->list, s->tileCost, s->params.tilesXFull, s->orderedList, (const uint8_t*)s->tileClass,
-		                   (const unsigned long long*)(s->work + 16), (uint32_t)s->blocksFrame * 4u, splitPercent, splitFloor, s->work + 18);
+		TileOrderArgs a;
+		a.classes = s->tileClass; a.costSum = (const unsigned long long*)(s->work + 16); a.nWaves = (uint32_t)s->blocksFrame * 4u;
+		a.splitPercent = s->knobs.splitPercent; a.splitFloor = 2000u;            // floor: 20 us (100 MHz)
+		a.thresholds = s->work + 18;
+		orderTiles(s, tq, a, st);
 		p.tileList = s->orderedList;
 	}
 	tq->costValid = true;
@@ -1683,9 +1644,10 @@ static int renderFrameFused(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, fl
 // of other parts alone, so under row ownership they are zeroed first.
 static int renderFrameSplit(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, uint8_t* mask_dev, void* stream)
 {
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
+	const uint32_t W = s->params.view.width;
+	const TileGrid g(W, s->params.view.height, rowBegin, rowEnd);
+	if (g.noRows()) return RTX_OK;
+	rowEnd = g.rowEnd;
 	if (s->params.bandH) HIPCHK(hipMemsetAsync(mask_dev + (size_t)rowBegin * W, 0, (size_t)(rowEnd - rowBegin) * W, (hipStream_t)stream));
 	int rc = rtx_render_pass1(s, rowBegin, rowEnd, fb_dev, stream);
 	if (!rc) rc = rtx_sobel(s, fb_dev, rowBegin, rowEnd, mask_dev, stream);
@@ -1693,41 +1655,9 @@ static int renderFrameSplit(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, fl
 	return rc;
 }
 
-// One launch or three?  The single launch overlaps the stages and splits the slowest tiles -- it wins when the frame is
-// bounded by its slowest tiles (small and medium frames, a shard of a large one), by up to 3x; its per-tile bookkeeping
-// (a dozen device-scope round trips of ~5 us) loses to three plain launches when the frame is throughput-bound and its
-// tiles are cheap.  Which case a view is in is measured, not guessed: the frames are bracketed by events that later
-// calls read back without waiting; both ways are tried on warm frames, the faster one is kept and the other one is
-// tried again every 64 frames.  The pixels are the same either way.
-int rtx_render_frame(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, uint8_t* mask_dev, void* stream)
+// finished frames: take their durations
+static void collectFrameProbes(rtx_scene* s)
 {
-	RoctxRange range("Render scene + MSAA (rtx_render_frame)");
-	if (!s || !fb_dev || !mask_dev) return fail(RTX_ERR_ARG, "scene/fb/mask is NULL");
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_frame has no instrumented variant: use rtx_render_pass1 / rtx_sobel / rtx_render_ssaa for statistics");
-	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
-	int rc = ensureWork(s);
-	if (rc) return rc;
-	hipStream_t st = (hipStream_t)stream;
-	if (int ro = renderOn(s, st)) return ro;
-	if (showNormals(s)) {
-		// the debug view in three launches, outside the measurements and tile lists of the ordinary frames
-		s->lastFused.valid = false;
-		if ((rc = stamp(s, 3, st))) return rc;
-		if ((rc = renderFrameSplit(s, rowBegin, rowEnd, fb_dev, mask_dev, stream))) { if (s->evUsed[3] & 1) s->evUsed[3]--; return rc; }
-		if ((rc = stamp(s, 3, st))) return rc;
-		s->lastFrameMode = 0;
-		return RTX_OK;
-	}
-	const uint32_t lastRow = (rowEnd < H - 1 ? rowEnd : H - 1);
-	rtx_scene::TileQueues* tq = nullptr;
-	if (lastRow > rowBegin) {
-		const uint32_t tilesX = (W - 1 + 7) / 8, tileRow0 = rowBegin / 8;
-		// (the list of the three-launch path: its entry also keeps what was measured for this view)
-		if ((rc = buildTileList(s, rowBegin, lastRow, tilesX, tileRow0, (lastRow + 7) / 8 - tileRow0, &tq, true, st))) return rc;
-	}
-	// finished frames: take their durations
 	for (auto& pr : s->probes) {
 		if (!pr.pending || hipEventQuery(pr.b) != hipSuccess) continue;
 		pr.pending = false;
@@ -1743,58 +1673,70 @@ int rtx_render_frame(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb
 		}
 	}
 	(void)hipGetLastError();
-	int mode;
-	const int forced = s->frameModeForced >= 0 ? s->frameModeForced : s->knobs.frameMode;
-	const bool warm = tq && tq->costValid;
-	const uint32_t ruleTiles = s->analytic ? s->knobs.frameRuleTilesAnalytic : s->knobs.frameRuleTiles;
-	bool reprobe = false;
-	if (forced >= 0) mode = forced;
-	else if (!tq || tq->fusedGaveUp) mode = 0;
-	// By rule, not by measurement, where the single launch has never won: frames of more than 65 536 listed tiles
-	// (8 192 without meshes) are throughput-bound over cheap tiles -- 4096^2: 4.5 ms in one launch against 4.0 in three, 8192^2 18.1
-	// against 15.2 -- and probing there cost the headline two slow frames at the start and one in every 64.
-	else if (tq->listed > ruleTiles) mode = 0;
-	// no measured costs yet: by size -- the single launch where the frame is bounded by its slowest tiles; without meshes (cheap,
-	// even tiles: cfg3 at 1080p 2.0 ms in one launch, 1.1 in three) only for small frames
-	else if (!warm) mode = tq->listed <= ruleTiles ? 1 : 0;
-	// not measured twice each yet: in turn
-	else if (tq->frameSamples[0] < 2 || tq->frameSamples[1] < 2) mode = (int)(tq->framesSeen & 1u);
-	else {
-		mode = tq->frameMs[1] <= tq->frameMs[0] ? 1 : 0;
-		// (the other way is tried again every 64 frames -- every 1024 when it lost by more than a fifth)
-		const float lo = std::min(tq->frameMs[0], tq->frameMs[1]), hi = std::max(tq->frameMs[0], tq->frameMs[1]);
-		if (((tq->framesSeen & 63u) == 63u && hi <= 1.2f * lo) || (tq->framesSeen & 1023u) == 1023u) { mode ^= 1; reprobe = true; }
-		else if ((tq->framesSeen & 63u) == 62u) reprobe = true;      // (the frame before: the current way's time is refreshed as well)
+}
+
+// One launch or three?  The single launch overlaps the stages and splits the slowest tiles -- it wins when the frame is
+// bounded by its slowest tiles (small and medium frames, a shard of a large one), by up to 3x; its per-tile bookkeeping
+// (a dozen device-scope round trips of ~5 us) loses to three plain launches when the frame is throughput-bound and its
+// tiles are cheap.  Which case a view is in is measured, not guessed: the frames are bracketed by events that later
+// calls read back without waiting; both ways are tried on warm frames, the faster one is kept and the other one is
+// tried again every 64 frames (rtx_frame_plan.h, decideFrameMode).  The pixels are the same either way.
+int rtx_render_frame(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, float* fb_dev, uint8_t* mask_dev, void* stream)
+{
+	RoctxRange range("Render scene + MSAA (rtx_render_frame)");
+	if (!s || !fb_dev || !mask_dev) return fail(RTX_ERR_ARG, "scene/fb/mask is NULL");
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_frame has no instrumented variant: use rtx_render_pass1 / rtx_sobel / rtx_render_ssaa for statistics");
+	const TileGrid g(s->params.view.width, s->params.view.height, rowBegin, rowEnd);
+	if (g.noRows()) return RTX_OK;
+	rowEnd = g.rowEnd;
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	hipStream_t st = (hipStream_t)stream;
+	if (int ro = renderOn(s, st)) return ro;
+	if (showNormals(s)) {
+		// the debug view in three launches, outside the measurements and tile lists of the ordinary frames
+		s->lastFused.valid = false;
+		if ((rc = stamp(s, 3, st))) return rc;
+		if ((rc = renderFrameSplit(s, rowBegin, rowEnd, fb_dev, mask_dev, stream))) { dropOpenStamp(s, 3); return rc; }
+		if ((rc = stamp(s, 3, st))) return rc;
+		s->lastFrameMode = 0;
+		return RTX_OK;
 	}
-	// The frame is bracketed by its own pair of events only while the choice is being made or re-examined (the frame that
-	// tries the other way every 64 frames and the one before it): an event costs the queue ~5 us.
-	const bool byRule = tq && tq->listed > ruleTiles;
-	const bool probing = forced < 0 && tq && !byRule && (!warm || tq->frameSamples[0] < 2 || tq->frameSamples[1] < 2 || (tq->framesSeen & 63u) >= 62u);
+	rtx_scene::TileQueues* tq = nullptr;
+	// (the list of the three-launch path: its entry also keeps what was measured for this view)
+	if (!g.noRenderedRow() && (rc = buildTileList(s, rowBegin, g.lastRow, g.tilesX, g.tileRow0, g.tilesY, &tq, true, st))) return rc;
+	collectFrameProbes(s);
+	const int forced = s->frameModeForced >= 0 ? s->frameModeForced : s->knobs.frameMode;
+	const uint32_t ruleTiles = s->analytic ? s->knobs.frameRuleTilesAnalytic : s->knobs.frameRuleTiles;
+	const bool warm = tq && tq->costValid;
+	const uint32_t noSamples[2] = { 0, 0 }; const float noMs[2] = { -1.f, -1.f };      // (no row is rendered: no list, nothing measured)
+	const rtxplan::FrameModeChoice c = tq ? rtxplan::decideFrameMode(forced, true, tq->fusedGaveUp, tq->listed, ruleTiles, warm, tq->frameSamples, tq->frameMs, tq->framesSeen)
+	                                      : rtxplan::decideFrameMode(forced, false, false, 0u, ruleTiles, false, noSamples, noMs, 0u);
 	rtx_scene::FrameProbe* pr = nullptr;
-	if (probing) {
+	if (c.probing) {
 		pr = &s->probes[s->probeNext++ & 7u];
 		HIPCHK(pr->a.create()); HIPCHK(pr->b.create());
 		pr->pending = false;
 		HIPCHK(hipEventRecord(pr->a, st));
 	}
 	if ((rc = stamp(s, 3, st))) return rc;
-	if (mode == 1) {
+	if (c.mode == 1) {
 		rc = renderFrameFused(s, rowBegin, rowEnd, fb_dev, mask_dev, stream, warm);
 		// what rtx_frame_status needs to render the frame again should the single launch have given up
 		s->lastFused = { true, rowBegin, rowEnd, fb_dev, mask_dev, stream, tq ? (size_t)(tq - s->tileQueues.data()) : ~(size_t)0, tq ? tq->generation : 0u,
 		                 s->viewSerial, s->params.bandH, s->params.nParts, s->params.part, s->params.halo };
 	}
 	else { s->lastFused.valid = false; rc = renderFrameSplit(s, rowBegin, rowEnd, fb_dev, mask_dev, stream); }
-	if (rc) { if (s->evUsed[3] & 1) s->evUsed[3]--; return rc; }      // (the open event pair is dropped with the frame)
+	if (rc) { dropOpenStamp(s, 3); return rc; }
 	if ((rc = stamp(s, 3, st))) return rc;
 	if (pr) {
 		HIPCHK(hipEventRecord(pr->b, st));
 		// (a cold frame is not a sample: it is slower either way)
-		pr->mode = warm ? mode : -1; pr->queue = (size_t)(tq - s->tileQueues.data()); pr->generation = tq->generation; pr->pending = true; pr->refresh = reprobe;
+		pr->mode = warm ? c.mode : -1; pr->queue = (size_t)(tq - s->tileQueues.data()); pr->generation = tq->generation; pr->pending = true; pr->refresh = c.reprobe;
 	}
 	if (tq) tq->framesSeen++;
 	if (tq) tq->costValid = true;      // (either way the tile costs of this view are now known)
-	s->lastFrameMode = mode;
+	s->lastFrameMode = c.mode;
 	s->lastFrameQueue = tq ? (size_t)(tq - s->tileQueues.data()) : ~(size_t)0;
 	return RTX_OK;
 }
@@ -1929,8 +1871,9 @@ int rtx_sobel(rtx_scene* s, const float* fb_dev, uint32_t rowBegin, uint32_t row
 	RoctxRange range("Sobel filter (rtx_sobel)");
 	if (!s || !fb_dev || !mask_dev) return fail(RTX_ERR_ARG, "scene/fb/mask is NULL");
 	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
+	const TileGrid g(W, H, rowBegin, rowEnd);
+	if (g.noRows()) return RTX_OK;
+	rowEnd = g.rowEnd;
 	int rc = ensureWork(s);
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
@@ -1953,8 +1896,9 @@ int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, ui
 	RoctxRange range("MSAA (rtx_render_ssaa)");
 	if (!s || !fb_dev || !mask_dev) return fail(RTX_ERR_ARG, "scene/fb/mask is NULL");
 	const uint32_t W = s->params.view.width, H = s->params.view.height;
-	if (rowEnd > H) rowEnd = H;
-	if (rowBegin >= rowEnd) return RTX_OK;
+	const TileGrid g(W, H, rowBegin, rowEnd);
+	if (g.noRows()) return RTX_OK;
+	rowEnd = g.rowEnd;
 	int rc = ensureWork(s);
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream;
@@ -1962,14 +1906,14 @@ int rtx_render_ssaa(rtx_scene* s, const uint8_t* mask_dev, uint32_t rowBegin, ui
 	if (showNormals(s)) return normalsSsaa(s, mask_dev, rowBegin, rowEnd, fb_dev, st);
 	// (work[1], the queue head, and work[10], the slot budget used, are zeroed by rtxSsaaScatterKernel; [8], [9]: the layout
 	// decision and its count, see below)
-	if ((uint32_t)s->tileCap < s->params.tilesXFull * ((H + 7) / 8) || W > 0xffffu || H > 0xffffu) return fail(RTX_ERR_ARG, "frame too large for the SSAA pixel list");
+	if ((uint32_t)s->tileCap < s->params.tilesXFull * g.tilesYFull || W > 0xffffu || H > 0xffffu) return fail(RTX_ERR_ARG, "frame too large for the SSAA pixel list");
 	if ((rc = stamp(s, 2, st))) return rc;
 	Params p = s->params;
 	p.fb = fb_dev;
 	p.workCounter = s->work + 1;
 	p.ssaaMask = mask_dev;
 	p.rowBegin = rowBegin; p.rowEnd = rowEnd;
-	p.nTiles = p.tilesXFull * ((H + 7) / 8);
+	p.nTiles = p.tilesXFull * g.tilesYFull;
 	p.ssaaScan = s->items;
 	p.frames = s->frames + s->framesArea;
 	p.ssaaPixels = s->ssaaPixels;
@@ -2302,6 +2246,36 @@ int rtx_mesh_flatten_probe(const rtx_mesh* m, uint32_t* n_wide, void* wide_out, 
 	const size_t n = std::min<size_t>(cap_wide, flat.wide.size());
 	if (wide_out && n) memcpy(wide_out, flat.wide.data(), n * sizeof(WideNode));
 	if (prune_out && n) memcpy(prune_out, flat.prune.data(), n * sizeof(PruneBlock));
+	return RTX_OK;
+}
+
+// Host only: the policy of rtx_render_frame (rtx_frame_plan.h, decideFrameMode) for the CPU tests.
+int rtx_frame_mode_probe(int forced, int has_list, int fused_gave_up, uint32_t listed, uint32_t rule_tiles, int warm, const uint32_t* frame_samples2,
+                         const float* frame_ms2, uint32_t frames_seen, int* mode, int* reprobe, int* probing)
+{
+	if (!frame_samples2 || !frame_ms2 || !mode || !reprobe || !probing) return fail(RTX_ERR_ARG, "rtx_frame_mode_probe: NULL argument");
+	const rtxplan::FrameModeChoice c = rtxplan::decideFrameMode(forced, has_list != 0, fused_gave_up != 0, listed, rule_tiles, warm != 0, frame_samples2, frame_ms2, frames_seen);
+	*mode = c.mode; *reprobe = c.reprobe ? 1 : 0; *probing = c.probing ? 1 : 0;
+	return RTX_OK;
+}
+
+// Host only: the tile list buildTileList would have the device write (TileGrid, stripsFit, planTileList, expectedTileList) for the CPU tests.
+int rtx_tile_list_probe(uint32_t width, uint32_t height, uint32_t band_height, uint32_t n_parts, uint32_t part, int halo, uint32_t rowBegin, uint32_t rowEnd,
+                        int strips, const uint32_t* rect4, uint32_t* out, size_t cap, size_t* need)
+{
+	if (!rect4 || !need) return fail(RTX_ERR_ARG, "rtx_tile_list_probe: rect/need is NULL");
+	if (width < 2 || height < 2) return fail(RTX_ERR_ARG, "view: width/height must be >= 2");
+	if (band_height != 0 && (n_parts == 0 || part >= n_parts)) return fail(RTX_ERR_ARG, "bad ownership");
+	const TileGrid g(width, height, rowBegin, rowEnd);
+	// (no rendered row: no tile row, eight empty queues)
+	const TilePlan plan = rtxplan::planTileList(width, { band_height, n_parts ? n_parts : 1, part, halo ? 1u : 0u }, rowBegin, g.lastRow, g.tilesX, g.tileRow0, g.tilesY,
+	                                            strips != 0 && rtxplan::stripsFit(width, height), rect4);
+	const std::vector<uint32_t> list = rtxplan::expectedTileList(width, g.tilesX, g.tilesY, rect4, plan);
+	// (the header the device copies from the plan is the construction's)
+	if (list.size() != plan.listWords || !std::equal(plan.words.begin(), plan.words.begin() + 16, list.begin()))
+		return fail(RTX_ERR_ARG, "rtx_tile_list_probe: the plan's header differs from the host's construction");
+	*need = list.size();
+	if (out && cap >= list.size()) memcpy(out, list.data(), list.size() * sizeof(uint32_t));
 	return RTX_OK;
 }
 

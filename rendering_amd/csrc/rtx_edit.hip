@@ -342,7 +342,7 @@ int rtx_scene_set_lights(rtx_scene* s, uint32_t n, const rtx_light* lights)
 	if (s->plain != wasPlain) {
 		// (another kernel family: pass 1's grid, and what was measured of the frame modes with the old one)
 		if ((rc = askResidentBlocks(s))) return rc;
-		for (auto& q : s->tileQueues) { q.frameMs[0] = q.frameMs[1] = -1.f; q.frameSamples[0] = q.frameSamples[1] = 0; q.framesSeen = 0; q.generation++; q.fusedGaveUp = false; }
+		for (auto& q : s->tileQueues) q.forgetMeasurements();
 	}
 	if ((rc = ensureWork(s))) return rc;
 

@@ -93,6 +93,7 @@ def test_frame_row_ranges_and_bands(ra, torch_cuda):
     """Row ranges (the other rows keep what they held) and the row bands of a sharded frame, one launch against three."""
     torch = torch_cuda
     g = ra.Scene("scenes/cfg2_smooth_4k.scene", 160, 200)
+    g.set_knob("verify_lists", 1)      # (every list the calls below cause is also compared with the host's construction)
     for rows in ((0, 200), (0, 64), (37, 150), (192, 200), (199, 200)):
         ref_fb, ref_mask = stages(torch, g, rows=rows)
         for it in range(2):
@@ -169,6 +170,7 @@ def test_halo_strips_and_their_expansion(ra, torch_cuda, monkeypatch):
     torch = torch_cuda
     W, H = 200, 330
     g = ra.Scene("scenes/cfg2_smooth_4k.scene", W, H)
+    g.set_knob("verify_lists", 1)      # (every list the calls below cause is also compared with the host's construction)
     g.set_frame_mode(SPLIT)
     full, full_mask = stages(torch, g)
     for limit in (None, "0"):
