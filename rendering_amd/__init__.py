@@ -60,6 +60,9 @@ RTX_AO_SYMBOLS = ["rtx_render_ao"]
 # the extension of include/rtx_surface.h: surface data at the hits of caller-supplied rays (not part of the drop-in boundary)
 RTX_SURFACE_SYMBOLS = ["rtx_surface_rays"]
 
+# the extension of include/rtx_light.h: direct light at the hits of caller-supplied rays (not part of the drop-in boundary)
+RTX_LIGHT_SYMBOLS = ["rtx_light_rays"]
+
 
 class AovBuffers(C.Structure):
     """rtx_aov_buffers (include/rtx_aov.h): six device pointers, any of them NULL."""
@@ -69,6 +72,12 @@ class AovBuffers(C.Structure):
 class SurfaceBuffers(C.Structure):
     """rtx_surface_buffers (include/rtx_surface.h): five device pointers, any of them NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("hits_dev", "position_dev", "normal_dev", "albedo_dev", "specular_dev")]
+
+
+class LightBuffers(C.Structure):
+    """rtx_light_buffers (include/rtx_light.h): the scene's number of lights and six device pointers, any of them NULL."""
+    _fields_ = [("n_lights", C.c_uint32)] + [(n, C.c_void_p) for n in ("hits_dev", "diffuse_dev", "specular_dev", "light_diffuse_dev",
+                                                                       "light_specular_dev", "light_open_dev")]
 
 
 class AoParams(C.Structure):
@@ -138,6 +147,8 @@ def load():
     rtx.rtx_render_aov.argtypes = [vp, u32, u32, C.POINTER(AovBuffers), vp]
     rtx.rtx_render_ao.argtypes = [vp, u32, u32, C.POINTER(AoParams), vp, vp, vp]
     rtx.rtx_surface_rays.argtypes = [vp, u32, vp, C.POINTER(SurfaceBuffers), vp]
+    if hasattr(rtx, "rtx_light_rays"):      # (a library without it is reported by exported_symbols)
+        rtx.rtx_light_rays.argtypes = [vp, u32, vp, C.POINTER(LightBuffers), vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -216,7 +227,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -928,6 +939,35 @@ class Scene:
         if n:
             bufs = SurfaceBuffers(*[out[name].data_ptr() if name in out else None for name in ("hits", "position", "normal", "albedo", "specular")])
             _check(self.rtx.rtx_surface_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_surface_rays")
+        return out
+
+    def light_rays(self, rays, diffuse=True, specular=True, hits=False, per_light=False, stream=None):
+        """rtx_light_rays: the direct light at the first hits of the rays of a device tensor, on the device -- castRay's sums over the
+        lights with their shadow rays, bit for bit (include/rtx_light.h).  rays: as for trace_rays.  Returns a dict of new tensors on the
+        rays' device: "diffuse" (n, 3) and "specular" (n, 3), float32, the sums a Diffuse hit's colour (albedo * diffuse) and a Phong hit's
+        ((albedo * ambient + diffuse * kd) + specular * ks) are made of; "hits" (n, 8), trace_rays' record; with per_light also
+        "light_diffuse" (n, L, 3) and "light_specular" (n, L, 3), float32, what each of the scene's L lights adds to the sums, and
+        "light_open" (n, L), int32, how many of the light's shadow rays arrive (0 / 1; up to its number of samples for an area light).
+        Everything is 0 at a miss, and the sums are 0 on a scene without lights (L = 0).  Asynchronous on `stream`, which is handled as in
+        trace_rays."""
+        import torch
+        if not (diffuse or specular or hits or per_light):
+            raise ValueError("light_rays: nothing to compute (every channel is off)")
+        n = _check_rays("light_rays", rays, self.device)
+        nl = self.n_lights if per_light else 0
+        asked = [(name, shape, dtype) for name, on, shape, dtype in (
+            ("hits", hits, (8,), torch.float32), ("diffuse", diffuse, (3,), torch.float32), ("specular", specular, (3,), torch.float32),
+            ("light_diffuse", per_light, (nl, 3), torch.float32), ("light_specular", per_light, (nl, 3), torch.float32),
+            ("light_open", per_light, (nl,), torch.int32)) if on]
+        alloc_on, st = _query_stream(stream, rays.device, (rays,))
+        with torch.cuda.stream(alloc_on):
+            out = {name: torch.empty((n,) + shape, dtype=dtype, device=rays.device) for name, shape, dtype in asked}
+        # (a scene without lights: the per-light tensors are empty, and the library takes no pointer for them)
+        ptrs = [out[name].data_ptr() if name in out and out[name].numel() else None
+                for name in ("hits", "diffuse", "specular", "light_diffuse", "light_specular", "light_open")]
+        if n and any(p is not None for p in ptrs):
+            bufs = LightBuffers(nl, *ptrs)
+            _check(self.rtx.rtx_light_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_light_rays")
         return out
 
     def occluded(self, rays, tmax=None, stream=None):

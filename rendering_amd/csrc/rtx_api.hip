@@ -22,6 +22,7 @@
 #include "../../include/rtx_aov.h"
 #include "../../include/rtx_ao.h"
 #include "../../include/rtx_surface.h"
+#include "../../include/rtx_light.h"
 #include "rtx_device.h"
 #include "rtx_frame_plan.h"
 #include "rtx_own.h"
@@ -36,6 +37,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_aov.hip"
 #include "rtx_ao.hip"
 #include "rtx_surface.hip"
+#include "rtx_light.hip"
 #undef RTX_QUERY_INSTANCES
 #undef RTX_MESH_INSTANCES
 
@@ -214,6 +216,7 @@ struct rtx_scene {
 	DevArray<uint32_t> rayWork;
 	int rayHitBlocks[2] = { 0, 0 };
 	int raySurfaceBlocks[2] = { 0, 0 };                        // rtx_surface_rays' kernel
+	int rayLightBlocks[2] = { 0, 0 };                          // rtx_light_rays' kernel
 	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
@@ -372,6 +375,12 @@ RaySurfaceKernel raySurfaceKernel(const Variant& v)
 {
 	if (v.analytic) return rtxRaySurfaceKernel<false, true, -1>;
 	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RaySurfaceKernel { return rtxRaySurfaceKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+typedef void (*RayLightKernel)(const Params, const uint32_t*, const rtx_light_buffers);
+RayLightKernel rayLightKernel(const Variant& v)
+{
+	if (v.analytic) return rtxRayLightKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayLightKernel { return rtxRayLightKernel<true, decltype(b)::value, decltype(c)::value>; });
 }
 RayKernel rayColourKernel(const Variant& v)
 {
@@ -1766,6 +1775,7 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 		chooseBoxPrune(s);
 		s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;      // (the hit kernel's occupancy is the variant's)
 		s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
+		s->rayLightBlocks[0] = s->rayLightBlocks[1] = 0;
 		for (auto& b : s->rayOccludedBlocks) b[0] = b[1] = 0;
 	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
@@ -2322,6 +2332,8 @@ constexpr uint32_t kOccludedReorderMin = kTraceReorderMin;
 // ... and rtx_surface_rays': its times follow rtx_trace_rays' hits-only times within 0.1 ms at every setting of the knob, so it keeps that
 // call's threshold (profiles/surface_time.json)
 constexpr uint32_t kSurfaceReorderMin = kTraceReorderMin;
+// ... and rtx_light_rays': its first half is rtx_surface_rays' 
+constexpr uint32_t kLightReorderMin = kTraceReorderMin;
 
 // The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
 // for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
@@ -2451,6 +2463,29 @@ int rtx_surface_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_
 	// the hit records alone: rtx_trace_rays' launch (no surface fetch is compiled into that kernel)
 	if (!surface) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
 	else rc = launchRays(s, raySurfaceKernel(v), s->raySurfaceBlocks[v.cull ? 1 : 0], c, *out);
+	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_light_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_light_buffers* out, void* stream)
+{
+	RoctxRange range("Light rays (rtx_light_rays)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	const bool perLight = out->light_diffuse_dev || out->light_specular_dev || out->light_open_dev;
+	const bool light = out->diffuse_dev || out->specular_dev || perLight;
+	if (!out->hits_dev && !light) return fail(RTX_ERR_ARG, "rtx_light_rays: no output (all six buffers are NULL)");
+	// (a per-light buffer sized before rtx_scene_set_lights would be written past its end, or with another stride)
+	if (perLight && out->n_lights != s->params.nLights) return fail(RTX_ERR_ARG, "rtx_light_rays: n_lights is not the scene's number of lights");
+	if (perLight && s->params.nLights == 0) return fail(RTX_ERR_ARG, "rtx_light_rays: per-light buffers on a scene without lights");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, rays_dev, kLightReorderMin, stream, c, rc)) return rc;
+	const Variant v = variantOf(s);
+	c.p.workCounter = s->rayWork;
+	// the hit records alone: rtx_trace_rays' launch
+	if (!light) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
+	else rc = launchRays(s, rayLightKernel(v), s->rayLightBlocks[v.cull ? 1 : 0], c, *out);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
