@@ -107,6 +107,20 @@ __device__ __forceinline__ void loadRef(const RTX_AS1 f4v* A, const RTX_AS1 f4v*
 	c.e2y = vc.x; c.e2z = vc.y;
 }
 __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+// x < 0 per lane, compared where it is asked for: one v_cmp into a scalar pair that serves as the condition itself -- never a value that is kept, hoisted or spilled
+__device__ __forceinline__ bool negNow(float x)
+{
+	uint64_t m;
+	asm volatile("v_cmp_gt_f32_e64 %0, 0, %1" : "=s"(m) : "v"(x));
+	return __builtin_amdgcn_inverse_ballot_w64(m);
+}
+// the lanes with |x| < bound, likewise
+__device__ __forceinline__ uint64_t absBelowNow(float x, float bound)
+{
+	uint64_t m;
+	asm volatile("v_cmp_lt_f32_e64 %0, |%1|, %2" : "=s"(m) : "v"(x), "s"(bound));
+	return m;
+}
 
 constexpr float kFltMax = 3.402823466e+38f;
 // (double)x < 1e-8 for a float x  <=>  x < 0x322bcc78 (the smallest float >= the double 1e-8);
@@ -1205,7 +1219,16 @@ __device__ __forceinline__ void meshWalk(const u32x16& mp, const Bundle& B, bool
 // neither carries the other's walks), -1 read from the view at run time (the instrumented and the probe kernels)
 // KINDS: the objects looked at -- 0 all of them, in scene order (every kernel that needs the nearest hit, and castRayWave's shadow rays);
 // 1 only the spheres and planes, 2 only the meshes (rtxRayOccludedKernel: an occlusion answer does not depend on the order of the objects)
-template <bool STATS, bool MESH = true, bool FEWRAYS = false, bool BOXES = true, int CULLK = -1, int KINDS = 0>
+// UNIO: the caller's origin is one point for the whole wave, held in scalar registers (castRayPlainWave's primary rays from the camera).  A VALU instruction
+// reads one scalar register, so every (box - o) of a node visit whose box is a scalar too took a copy of o into a vector register first: 22 v_mov per visit.
+// The walk is handed the origin in three vector registers instead, filled once per walk.
+// LEAN (the PLAIN pass-1 kernel, six waves per SIMD): wave-level state that used to sit in spill lanes across the walk (v_writelane / v_readlane, VALU
+// instructions both) is said so that it need not be kept (profiles/round_state_spills.txt):
+//   - the signs of 1 / dir (three lane masks) are compared where a root-box test or a binary walk reads them (negNow: one v_cmp each);
+//   - which lanes are regular (a fourth mask) is looked at again in the rare round that has an irregular lane at all, and is `all of them` otherwise;
+//   - meshRegular, wideOk, oneOrigin and that `some lane is irregular` travel as bits of one scalar word instead of one 64-bit condition each.
+// The same lanes walk together in the same order: no float operation and no result changes.  The other kernels keep the plain form -- their machine code is unchanged.
+template <bool STATS, bool MESH = true, bool FEWRAYS = false, bool BOXES = true, int CULLK = -1, int KINDS = 0, bool UNIO = false, bool LEAN = false>
 __device__ __forceinline__ void traceWave(const Params& P, bool active, bool shadow, V3 o, V3 d, float tmax,
                                           Hit& h, Counts& cnt, uint32_t src = 0)
 {
@@ -1216,7 +1239,9 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 	const bool cull = CULLK < 0 ? (uni(P.view.flags) & 1u) != 0 : CULLK != 0;
 	// AccelerationStructure::intersectBox's per-ray part (objects.cpp:543-544), hoisted out of the walk
 	const float ix = 1 / d.x, iy = 1 / d.y, iz = 1 / d.z;
-	const bool sx = ix < 0, sy = iy < 0, sz = iz < 0;
+	// (LEAN: not kept -- negNow where they are read.  The constants below are placeholders that only the REGULAR walks are handed, which never read the signs:
+	// meshWalk looks at them in its binary form alone.  A REGULAR path that came to need them has to take negNow as the two binary calls below do)
+	const bool sx = LEAN ? false : ix < 0, sy = LEAN ? false : iy < 0, sz = LEAN ? false : iz < 0;
 	bool live = active;
 	const uint32_t nObj = uni(P.nObjects);
 	for (uint32_t oi = 0; oi < nObj; oi = uni(oi + 1)) {
@@ -1245,30 +1270,45 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 			// apart from the others, in the binary form; the rest of the wave keeps the wide walk (one such lane used to demote all 64)
 			const bool laneRegular = fabsf(ix) < __builtin_inff() && fabsf(iy) < __builtin_inff() && fabsf(iz) < __builtin_inff() &&
 			                         fabsf(o.x) < 0x1p100f && fabsf(o.y) < 0x1p100f && fabsf(o.z) < 0x1p100f;
-			const bool meshRegular = (mflags & 2u) != 0;
-			const bool wideOk = (mflags & 4u) != 0;
+			const bool meshRegular0 = (mflags & 2u) != 0;
+			const bool wideOk0 = (mflags & 4u) != 0;
 			if ((mflags & 1u) != 0) {
 				const float xlo = (F(rec2[2]) - o.x) * ix, xhi = (F(rec2[3]) - o.x) * ix, ylo = (F(rec2[4]) - o.y) * iy, yhi = (F(rec2[5]) - o.y) * iy;
 				const float zlo = (F(rec2[6]) - o.z) * iz, zhi = (F(rec2[7]) - o.z) * iz;
-				float tmin = sx ? xhi : xlo, tmx = sx ? xlo : xhi;
-				const float tymin = sy ? yhi : ylo, tymax = sy ? ylo : yhi;
+				const bool bsx = LEAN ? negNow(ix) : sx, bsy = LEAN ? negNow(iy) : sy, bsz = LEAN ? negNow(iz) : sz;
+				float tmin = bsx ? xhi : xlo, tmx = bsx ? xlo : xhi;
+				const float tymin = bsy ? yhi : ylo, tymax = bsy ? ylo : yhi;
 				bool fail = (tmin > tymax) || (tymin > tmx);
 				if (tymin > tmin) tmin = tymin;
 				if (tymax < tmx) tmx = tymax;
-				const float tzmin = sz ? zhi : zlo, tzmax = sz ? zlo : zhi;
+				const float tzmin = bsz ? zhi : zlo, tzmax = bsz ? zlo : zhi;
 				fail = fail || (tmin > tzmax) || (tzmin > tmx);
 				if (STATS) cnt.box += __popcll(ballot(consider && fail));       // (their root-box test is still a test of the reference)
 				pending = consider && !fail;
 			}
 			// (src == 1: the ray starts at the camera, o == view.camPos bit for bit -- castRayWave)
-			const bool oneOrigin = !STATS && ballot(pending && src != 1u) == 0;
+			const bool oneOrigin0 = !STATS && ballot(pending && src != 1u) == 0;
+			// LEAN: the four wave-uniform conditions of the bundle loop as bits of ONE scalar word, read through an opaque copy where they are used
+			// (bit 16: some pending ray is irregular.  Clear -- the usual case -- every lane of `pending` is regular and laneRegular itself is not needed again)
+			uint32_t fw = (mflags & 6u) | (oneOrigin0 ? 8u : 0u) | (ballot(pending && !laneRegular) != 0 ? 16u : 0u);
 			while (ballot(pending) != 0) {
 				bool cl = pending;
+				uint32_t f = fw;
+				if (LEAN) asm volatile("" : "+s"(f));
+				const bool meshRegular = LEAN ? (f & 2u) != 0 : meshRegular0, wideOk = LEAN ? (f & 4u) != 0 : wideOk0, oneOrigin = (LEAN && !UNIO) ? (f & 8u) != 0 : oneOrigin0;
 				// the regular rays first, as one bundle (or more: the split below); what is left afterwards are the irregular ones
 				bool regular = false;
 				if (meshRegular) {
-					const uint64_t regM = ballot(pending && laneRegular);
-					if (regM != 0) { cl = pending && laneRegular; regular = true; }
+					bool lr = laneRegular;
+					if (LEAN) {
+						lr = true;
+						if ((f & 16u) != 0) {      // (rare: some pending ray has a zero direction component or a huge origin -- looked at again, not kept)
+							lr = __builtin_amdgcn_inverse_ballot_w64(absBelowNow(ix, __builtin_inff()) & absBelowNow(iy, __builtin_inff()) & absBelowNow(iz, __builtin_inff()) &
+							                                          absBelowNow(o.x, 0x1p100f) & absBelowNow(o.y, 0x1p100f) & absBelowNow(o.z, 0x1p100f));
+						}
+					}
+					const uint64_t regM = ballot(pending && lr);
+					if (regM != 0) { cl = pending && lr; regular = true; }
 				}
 				// what the split rule needs of the object's second line, fetched again per bundle (a hit in the scalar cache, requested ahead of the reductions below)
 				// instead of being kept in -- i.e. spilled from -- sixteen SGPRs across the walk of the previous bundle
@@ -1300,13 +1340,15 @@ __device__ __forceinline__ void traceWave(const Params& P, bool active, bool sha
 						if (ballot(cl && !(src == s0 && l2 >= 0.9802f && l2 <= 1.002f)) == 0) srcSel = s0;
 					}
 				}
-				if (!STATS && cull && regular && wideOk) meshWalk<STATS, true, true, true, FEWRAYS, BOXES>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt, srcSel);
+				V3 ow = o;
+				if (UNIO) asm volatile("" : "+v"(ow.x), "+v"(ow.y), "+v"(ow.z));      // (opaque: the walk cannot see that the three are scalars)
+				if (!STATS && cull && regular && wideOk) meshWalk<STATS, true, true, true, FEWRAYS, BOXES>(rec3, B, cl, shadow, ow, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt, srcSel);
 				// culling off (options.h:27, objects.cpp:75-79): the same wide walk; its filter mirrors by the sign of det (bundleRejects1), its plane records
 				// keep what may show either face (pruneEval8<.., false>)
-				else if (!STATS && regular && wideOk) meshWalk<STATS, false, true, true, FEWRAYS, BOXES>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt, srcSel);
-				else if (cull && regular) meshWalk<STATS, true, true, false, FEWRAYS>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
-				else if (cull) meshWalk<STATS, true, false, false, FEWRAYS>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
-				else meshWalk<STATS, false, false, false, FEWRAYS>(rec3, B, cl, shadow, o, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
+				else if (!STATS && regular && wideOk) meshWalk<STATS, false, true, true, FEWRAYS, BOXES>(rec3, B, cl, shadow, ow, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt, srcSel);
+				else if (cull && regular) meshWalk<STATS, true, true, false, FEWRAYS>(rec3, B, cl, shadow, ow, d, ix, iy, iz, sx, sy, sz, h.t, bt, bu, bv, btri, cnt);
+				else if (cull) meshWalk<STATS, true, false, false, FEWRAYS>(rec3, B, cl, shadow, ow, d, ix, iy, iz, LEAN ? negNow(ix) : sx, LEAN ? negNow(iy) : sy, LEAN ? negNow(iz) : sz, h.t, bt, bu, bv, btri, cnt);
+				else meshWalk<STATS, false, false, false, FEWRAYS>(rec3, B, cl, shadow, ow, d, ix, iy, iz, LEAN ? negNow(ix) : sx, LEAN ? negNow(iy) : sy, LEAN ? negNow(iz) : sz, h.t, bt, bu, bv, btri, cnt);
 				if (cl && bt < kFltMax && bt < h.t) { h.obj = (int)oi; h.t = bt; h.tri = btri; h.u = bu; h.v = bv; }   // scene.cpp:740-745
 				pending = pending && !cl;
 			}
@@ -1812,12 +1854,17 @@ __device__ __forceinline__ V3 castRayPlainWave(const Params& P0, bool valid, V3 
 		if (valid) s.diff = skyColor(freshParams(P0), d);
 		return s.diff;
 	}
+	// traceWave's two forms for the pass-1 kernel, the instantiation with CAM (the colour kernel of rtx_trace_rays has CAM = false and keeps the plain forms: with LEAN one
+	// of its four variants went from 16 to 32 B of scratch).  The pass-1 kernel with the box records and culling off keeps the plain forms too: with either of the two it
+	// went from 16 to 32 B of scratch per lane -- two more scratch operations per round in the light loop -- and gained nothing measurable (profiles/round_state_ab.txt)
+	constexpr bool SCALAR_STATE = CAM && !(BOXES && CULLK == 0);
+	constexpr bool UNIO = SCALAR_STATE, LEAN = SCALAR_STATE;
 	// ---- the primary ray
 	Hit h;
 	parked[0][t] = d.x; parked[1][t] = d.y; parked[2][t] = d.z;
 	if (!CAM) { parked[3][t] = o.x; parked[4][t] = o.y; parked[5][t] = o.z; }
 	asm volatile("" ::: "memory");
-	traceWave<STATS, true, FEWRAYS, BOXES, CULLK>(freshParams(P0), valid, false, o, d, kFltMax, h, cnt, CAM ? 1u : 0u);
+	traceWave<STATS, true, FEWRAYS, BOXES, CULLK, 0, UNIO, LEAN>(freshParams(P0), valid, false, o, d, kFltMax, h, cnt, CAM ? 1u : 0u);
 	asm volatile("" ::: "memory");
 	const bool hit = h.obj >= 0;      // (a lane that is not valid took no part: no object)
 	{
@@ -1869,7 +1916,7 @@ __device__ __forceinline__ V3 castRayPlainWave(const Params& P0, bool valid, V3 
 				parked[12][t] = I.x; parked[13][t] = I.y; parked[14][t] = I.z;
 				parked[15][t] = m;
 				asm volatile("" ::: "memory");
-				traceWave<STATS, true, FEWRAYS, BOXES, CULLK>(freshParams(P0), active, true, so, nL, dist, h, cnt, src);
+				traceWave<STATS, true, FEWRAYS, BOXES, CULLK, 0, false, LEAN>(freshParams(P0), active, true, so, nL, dist, h, cnt, src);
 				asm volatile("" ::: "memory");
 				s.P = mk(parked[0][t], parked[1][t], parked[2][t]);
 				s.N = mk(parked[3][t], parked[4][t], parked[5][t]);
