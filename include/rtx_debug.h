@@ -140,6 +140,17 @@ int rtx_scene_objects_read(rtx_scene* scene, uint32_t* n_objects, rtx_object* ob
  * destroyed -- which a test can check on a GPU it shares with others.  Either pointer may be NULL. */
 int rtx_live_device_memory(size_t* allocations, size_t* bytes);
 
+/* The placement and triangle assembly of include/rtx_deform.h on host arrays, without a scene and without a tree: pos n_pos x 3, nrm n_nrm x 3
+ * raw normals or NULL (the topology's stored ones).  device >= 0: exactly the three kernels of csrc/rtx_deform.hip on that device, their
+ * results copied back; device < 0: the same functions (csrc/rtx_place.h) on the CPU, the box by the loader's sequential rule.  tri24_out: n_tris x 9
+ * positions, then n_tris x 9 normals, then n_tris x 6 tangents and bitangents (always computed); lo_hi_out[12]: the vertices' box lo, hi, the root
+ * box lo, hi; flags_out[2]: some input is not finite (nothing else is written then), some placed position is not finite (the triangles are
+ * written all the same: how the NaN cases are compared).  tests/test_deform_cpu.py, tests/test_gpu_deform.py. */
+struct rtx_mesh_topology;
+struct rtx_mesh_pose;
+int rtx_place_probe(int device, const struct rtx_mesh_topology* topology, const float* pos, const float* nrm, const struct rtx_mesh_pose* pose,
+                    float* tri24_out, float* lo_hi_out, uint32_t* flags_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,7 +41,7 @@ RTX_SYMBOLS = [
     "rtx_vec_probe", "rtx_desc_serialize", "rtx_bvh_build_mode", "rtx_bvh_launches", "rtx_comm_unique_id", "rtx_comm_create", "rtx_comm_info", "rtx_comm_destroy", "rtx_comm_agree", "rtx_gather", "rtx_gather_plan",
     "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read", "rtx_live_device_memory",
     "rtx_scene_lights_read", "rtx_scene_mesh_prune_copy_read", "rtx_scene_objects_read",
-    "rtx_frame_mode_probe", "rtx_tile_list_probe",
+    "rtx_frame_mode_probe", "rtx_tile_list_probe", "rtx_place_probe",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
@@ -62,6 +62,20 @@ RTX_SURFACE_SYMBOLS = ["rtx_surface_rays"]
 
 # the extension of include/rtx_light.h: direct light at the hits of caller-supplied rays (not part of the drop-in boundary)
 RTX_LIGHT_SYMBOLS = ["rtx_light_rays"]
+
+# the extension of include/rtx_deform.h: deforming a mesh of a live scene from vertices on the device (not part of the drop-in boundary)
+RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
+
+
+class MeshTopology(C.Structure):
+    """rtx_mesh_topology (include/rtx_deform.h): six counts, then five host pointers."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_tris", "n_pos", "n_nrm", "n_uv", "placed_pos", "placed_nrm")] + \
+               [(n, C.c_void_p) for n in ("corner_pos", "corner_nrm", "corner_uv", "uv", "nrm")]
+
+
+class MeshPose(C.Structure):
+    """rtx_mesh_pose (include/rtx_deform.h)"""
+    _fields_ = [("pos", C.c_float * 3), ("rot_matrix", C.c_float * 16), ("size", C.c_float * 3), ("bias", C.c_float), ("ac_penalty", C.c_int32)]
 
 
 class AovBuffers(C.Structure):
@@ -220,6 +234,19 @@ def load():
     rtx.rtx_scene_objects_read.argtypes = [vp, C.POINTER(C.c_uint32), vp, C.c_uint32, C.POINTER(C.c_uint32)]
     host.rah_object_add.argtypes = [vp, i32, i32, C.c_char_p] + [vp] * 4 + [C.c_char_p] + [vp] * 2 + [C.c_char_p] * 4
     host.rah_object_remove.argtypes = [vp, i32]
+    if hasattr(rtx, "rtx_scene_deform_mesh"):      # (a library without them is reported by exported_symbols)
+        rtx.rtx_scene_set_mesh_topology.argtypes = [vp, u32, C.POINTER(MeshTopology)]
+        rtx.rtx_scene_deform_mesh.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(MeshPose), vp, vp, vp]
+        rtx.rtx_place_probe.argtypes = [i32, C.POINTER(MeshTopology), vp, vp, C.POINTER(MeshPose), vp, vp, vp]
+    host.rah_mesh_counts.argtypes = [vp, i32, vp]
+    host.rah_mesh_vertices.argtypes = [vp, i32, vp, vp]
+    host.rah_mesh_topology.argtypes = [vp, i32, vp, vp, vp, vp]
+    host.rah_mesh_set_vertices.argtypes = [vp, i32, vp, C.c_longlong, vp, C.c_longlong, i32, vp]
+    host.rah_mesh_deform_times.argtypes = [vp, vp]
+    host.rah_mesh_deform_times.restype = None
+    host.rah_euler_matrix.argtypes = [vp, vp]
+    host.rah_euler_matrix.restype = None
+    host.rah_mesh_pose.argtypes = [vp, i32, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -227,7 +254,8 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS if not hasattr(rtx, s)]
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS
+               if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
 
@@ -553,6 +581,47 @@ def vec_probe(op, a, b=None, ior=1.0, device=0):
         bp = _np_ptr(b)
     _check(rtx.rtx_vec_probe(device, op, a.shape[0], _np_ptr(a), bp, ior, _np_ptr(out)), "rtx_vec_probe")
     return out
+
+
+def euler_matrix(rot):
+    """The rotation matrix the loader places a mesh with (Matrix44f::fromEulerDegrees of `rot` in degrees, host libm), float32 (4, 4)."""
+    _, host = load()
+    r = np.ascontiguousarray(np.asarray(rot, np.float32).reshape(3))
+    m = np.zeros((4, 4), np.float32)
+    host.rah_euler_matrix(_np_ptr(r), _np_ptr(m))
+    return m
+
+
+def place_probe(topology, stored_normals, vertices, normals, pose, device=-1):
+    """The placement and triangle assembly of Scene.set_vertices on bare arrays (rtx_place_probe): no scene, no tree.  topology: the dict of
+    Scene.mesh_topology; stored_normals: float32 (n_nrm, 3), used when `normals` is None; vertices float32 (n_pos, 3); normals raw, float32
+    (n_nrm, 3), or None; pose: the dict of Scene.mesh_pose.  device >= 0: the three kernels on that device; device < 0: the same functions on
+    the CPU.  Returns dict(pos (n, 9), nrm (n, 9), tb (n, 6), obj_lo, obj_hi, root_lo, root_hi, bad_input, bad_placed)."""
+    rtx, _ = load()
+    f32 = lambda a, cols: np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, cols))
+    cp = np.ascontiguousarray(topology["corner_pos"], np.uint32).reshape(-1, 3)
+    cn = np.ascontiguousarray(topology["corner_nrm"], np.int32).reshape(-1, 3)
+    cu = np.ascontiguousarray(topology["corner_uv"], np.int32).reshape(-1, 3)
+    uv, sn, P = f32(topology["uv"], 2), f32(stored_normals, 3), f32(vertices, 3)
+    N = f32(normals, 3) if normals is not None else None
+    if N is not None and N.shape != sn.shape:
+        raise ValueError("place_probe: normals must have the stored normals' shape %s, got %s" % (sn.shape, N.shape))
+    nt = cp.shape[0]
+    t = MeshTopology(nt, P.shape[0], sn.shape[0], uv.shape[0], int(topology["placed_pos"]), int(topology["placed_nrm"]),
+                     cp.ctypes.data, cn.ctypes.data, cu.ctypes.data, uv.ctypes.data if uv.size else None, sn.ctypes.data if sn.size else None)
+    ps = MeshPose()
+    ps.pos[:] = [float(x) for x in np.asarray(pose["pos"], np.float32)]
+    ps.size[:] = [float(x) for x in np.asarray(pose["size"], np.float32)]
+    ps.rot_matrix[:] = [float(x) for x in euler_matrix(pose["rot"]).reshape(-1)]
+    ps.bias = float(pose["bias"]); ps.ac_penalty = int(pose["ac_penalty"])
+    tri = np.zeros(max(nt, 1) * 24, np.float32)
+    lo_hi = np.zeros(12, np.float32)
+    flags = np.zeros(2, np.uint32)
+    _check(rtx.rtx_place_probe(device, C.byref(t), _np_ptr(P), _np_ptr(N) if N is not None else None, C.byref(ps), _np_ptr(tri), _np_ptr(lo_hi), _np_ptr(flags)),
+           "rtx_place_probe")
+    return dict(pos=tri[:nt * 9].reshape(nt, 9).copy(), nrm=tri[nt * 9:nt * 18].reshape(nt, 9).copy(), tb=tri[nt * 18:nt * 24].reshape(nt, 6).copy(),
+                obj_lo=lo_hi[0:3].copy(), obj_hi=lo_hi[3:6].copy(), root_lo=lo_hi[6:9].copy(), root_hi=lo_hi[9:12].copy(),
+                bad_input=bool(flags[0]), bad_placed=bool(flags[1]))
 
 
 class Scene:
@@ -1118,6 +1187,104 @@ class Scene:
         ms = np.zeros(4, np.float32)
         self.host.rah_object_move_times(self.h, _np_ptr(ms))
         return dict(zip(("place", "upload", "set_object", "update_mesh"), (float(x) for x in ms)))
+
+    # ---- deforming a mesh (include/rtx_deform.h) ------------------------------------------------
+    def _mesh_counts(self, who, index):
+        if not 0 <= index < self.n_objects:
+            raise ValueError("%s: object index %d out of range (%d objects)" % (who, index, self.n_objects))
+        c = np.zeros(8, np.int64)
+        if self.host.rah_mesh_counts(self.h, index, _np_ptr(c)) != 0:
+            raise ValueError("%s: object %d is not a mesh" % (who, index))
+        return dict(zip(("n_tris", "n_pos", "n_nrm", "n_uv", "placed_pos", "placed_nrm", "has_faces"), (int(x) for x in c)))
+
+    def mesh_vertices(self, index):
+        """(P, N) of mesh `index` (scene-file order of the objects) as stored: the vertices of its OBJ file, float32 (n_pos, 3), and its
+        normals, normalised as the loader normalises them, float32 (n_nrm, 3)."""
+        c = self._mesh_counts("mesh_vertices", index)
+        P, N = np.zeros((c["n_pos"], 3), np.float32), np.zeros((c["n_nrm"], 3), np.float32)
+        self.host.rah_mesh_vertices(self.h, index, _np_ptr(P), _np_ptr(N))
+        return P, N
+
+    def mesh_topology(self, index):
+        """What the loader kept of mesh `index`'s faces: corner_pos uint32 (n_tris, 3), corner_nrm and corner_uv int32 (n_tris, 3) with -1 in
+        column 0 where the face gave none, uv float32 (n_uv, 2), and placed_pos / placed_nrm: how many vertices / normals were read before
+        the first face (only those are placed / rotated, as in the reference)."""
+        c = self._mesh_counts("mesh_topology", index)
+        d = dict(corner_pos=np.zeros((c["n_tris"], 3), np.uint32), corner_nrm=np.zeros((c["n_tris"], 3), np.int32),
+                 corner_uv=np.zeros((c["n_tris"], 3), np.int32), uv=np.zeros((c["n_uv"], 2), np.float32))
+        self.host.rah_mesh_topology(self.h, index, _np_ptr(d["corner_pos"]), _np_ptr(d["corner_nrm"]), _np_ptr(d["corner_uv"]), _np_ptr(d["uv"]))
+        d.update(placed_pos=c["placed_pos"], placed_nrm=c["placed_nrm"])
+        return d
+
+    def mesh_pose(self, index):
+        """pos, rot (degrees), size of mesh `index` and the scene's bias and ac_penalty: what its vertices are placed with."""
+        self._mesh_counts("mesh_pose", index)
+        pos, rot, size = (np.zeros(3, np.float32) for _ in range(3))
+        bias, pen = C.c_float(0), C.c_int(0)
+        self.host.rah_mesh_pose(self.h, index, _np_ptr(pos), _np_ptr(rot), _np_ptr(size), C.byref(bias), C.byref(pen))
+        return dict(pos=pos, rot=rot, size=size, bias=np.float32(bias.value), ac_penalty=pen.value)
+
+    def set_vertices(self, index, vertices, normals=None, stream=None):
+        """Gives mesh `index` new vertices, float32 (n_pos, 3) in its OBJ file's order and space, and with `normals` new raw normals, float32
+        (n_nrm, 3) (None keeps the stored ones): afterwards the scene is, bit for bit, a fresh load of the scene whose mesh reads an OBJ file
+        with these v (and vn) lines.  A torch tensor on the scene's device is used in place -- with a live GPU scene the device places the
+        vertices, assembles the triangles and rebuilds the structure (rtx_scene_deform_mesh), and no triangle crosses the bus; the call waits
+        for `stream` (None: torch's current stream), on which the tensors were produced.  A numpy array or a CPU tensor is uploaded as
+        vertices.  ValueError: a bad index, an object that is not a mesh, a wrong shape, dtype or device; RtxError: a refusal of the library
+        (a value that is not finite, a placed position that is not finite) -- the scene is then as it was."""
+        c = self._mesh_counts("set_vertices", index)
+        keep = []
+
+        def arg(name, a, rows):
+            if a is None:
+                return None, False
+            on_device = False
+            if isinstance(a, np.ndarray):
+                if a.dtype != np.float32:
+                    raise ValueError("set_vertices: %s must be float32, got %s" % (name, a.dtype))
+                shape = a.shape
+            else:
+                import torch
+                if not isinstance(a, torch.Tensor):
+                    raise ValueError("set_vertices: %s must be a numpy array or a torch tensor, got %s" % (name, type(a).__name__))
+                if a.dtype != torch.float32:
+                    raise ValueError("set_vertices: %s must be float32, got %s" % (name, a.dtype))
+                shape = tuple(a.shape)
+                if a.device.type == "cuda":
+                    if (a.device.index if a.device.index is not None else torch.cuda.current_device()) != self.device:
+                        raise ValueError("set_vertices: %s must be on cuda:%d, the scene's device, or on the host, got %s" % (name, self.device, a.device))
+                    on_device = True
+                elif a.device.type != "cpu":
+                    raise ValueError("set_vertices: %s must be on cuda:%d or on the host, got %s" % (name, self.device, a.device))
+            if len(shape) != 2 or shape[1] != 3 or shape[0] != rows:
+                raise ValueError("set_vertices: %s must have shape (%d, 3), got %s" % (name, rows, tuple(shape)))
+            if on_device:
+                a = a.contiguous()
+                keep.append(a)
+                return C.c_void_p(a.data_ptr()), True
+            a = np.ascontiguousarray(a if isinstance(a, np.ndarray) else a.numpy())
+            keep.append(a)
+            return _np_ptr(a), False
+
+        p, p_dev = arg("vertices", vertices, c["n_pos"])
+        if p is None:
+            raise ValueError("set_vertices: vertices is None")
+        n, n_dev = arg("normals", normals, c["n_nrm"])
+        if normals is not None and n_dev != p_dev:
+            raise ValueError("set_vertices: vertices and normals must both be on the device or both on the host")
+        st = None
+        if p_dev:
+            import torch
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)
+        if self.host.rah_mesh_set_vertices(self.h, index, p, c["n_pos"], n, c["n_nrm"] if normals is not None else 0, int(p_dev), st) != 0:
+            raise RtxError("set_vertices: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    def deform_times(self):
+        """Host wall ms of the stages of the last set_vertices: {kernels (placement and assembly on the device with their read-backs),
+        rebuild (rtx_scene_update_mesh: edit_times), mirror (the host's copy of the vertices), total}."""
+        ms = np.zeros(4, np.float32)
+        self.host.rah_mesh_deform_times(self.h, _np_ptr(ms))
+        return dict(zip(("kernels", "rebuild", "mirror", "total"), (float(x) for x in ms)))
 
     def counters_enable(self, on=True):
         _check(self.rtx.rtx_counters_enable(self.gpu(), int(on)), "rtx_counters_enable")

@@ -138,6 +138,8 @@ struct Knobs {
 	uint32_t dbgTile = 0;               // RTX_DBG_TILE=tx,ty (RTX_DBG builds): only this tile
 };
 
+struct rtx_scene_mesh_deform;      // rtx_deform.hip
+
 struct rtx_scene {
 	int device = 0;
 	int numCUs = 0;
@@ -161,6 +163,9 @@ struct rtx_scene {
 	std::vector<rtx_object> objectDescs;
 	DevArray<float> sphereLeafDev;     // the spheres' entry of meshLeaves once an edit has rebuilt it
 	DevArray<char> flatScratch;        // rtx_scene_update_mesh: the device flatten's scratch (rtx_flatten.hip)
+	// per mesh what rtx_scene_deform_mesh needs (include/rtx_deform.h): its topology in device memory and the scratch of its kernels; empty until
+	// rtx_scene_set_mesh_topology, moved with a kept mesh by rtx_scene_set_objects, not counted in rtx_scene_bytes
+	std::vector<std::shared_ptr<rtx_scene_mesh_deform>> meshDeform;
 	float editMs[4] = { 0, 0, 0, 0 };  // the last rtx_scene_update_mesh: build, read-back + flatten + upload, sources + estimate queued, whole call (host wall ms)
 	Params params;                // template of the kernel argument block
 	bool stats = false;
@@ -2579,3 +2584,6 @@ int rtx_vec_probe(int device, int op, uint32_t n, const float* a, const float* b
 
 // editing a live scene (include/rtx_scene_edit.h; uses the scene's internals above and the device build of rtx_bvh.hip)
 #include "rtx_edit.hip"
+
+// deforming a mesh of a live scene from vertices on the device (include/rtx_deform.h; its kernels come after every other one)
+#include "rtx_deform.hip"

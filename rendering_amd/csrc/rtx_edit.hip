@@ -196,9 +196,11 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 	std::vector<rtx_scene::SrcMesh> sms(nMeshes);
 	std::vector<rtx_scene::MeshLeaves> leaves(nMeshes, rtx_scene::MeshLeaves{ nullptr, 0 });
 	std::vector<float> bounds((size_t)nMeshes * 6);
+	std::vector<std::shared_ptr<rtx_scene_mesh_deform>> deform(nMeshes);      // (a kept mesh's topology follows it: include/rtx_deform.h)
 	for (uint32_t mi = 0; mi < nMeshes; mi++) {
 		const rtx_mesh_source& src = sources[mi];
 		if (src.keep >= 0) {
+			if ((size_t)src.keep < s->meshDeform.size()) deform[mi] = s->meshDeform[src.keep];
 			meshes[mi] = s->meshRecs[src.keep]; sms[mi] = s->srcMeshes[src.keep]; leaves[mi] = s->meshLeaves[src.keep];
 			sms[mi].meshIndex = mi;
 			std::copy(s->meshBounds.begin() + (size_t)src.keep * 6, s->meshBounds.begin() + (size_t)src.keep * 6 + 6, bounds.begin() + (size_t)mi * 6);
@@ -234,6 +236,8 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 		if (sources[mi].keep >= 0) { owned[mi].swap(s->meshOwned[sources[mi].keep]); fixed[mi].swap(s->meshFixed[sources[mi].keep]); }
 	s->meshOwned.swap(owned); s->meshFixed.swap(fixed);
 	owned.clear(); fixed.clear();
+	s->meshDeform.swap(deform);
+	deform.clear();
 	s->recordsOwned.swap(records);
 	records.clear();
 	s->sphereLeafDev.reset();

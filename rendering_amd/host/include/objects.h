@@ -95,6 +95,10 @@ public:
 	// allTris from the above with the current pos / rot / size, and the root box of `ac` (the loader's own placement, objects.cpp:282-331)
 	void place(const Options& options);
 	bool treeOnDevice = false;      // the GPU scene holds the structure of allTris and `ac` an older one (Scene::syncTrees)
+	// Scene::setVertices with a live GPU scene: the device placed the new vertices and allTris are an older shape's until something reads them
+	// (Scene::syncTrees places them again); the GPU scene holds corners, uv and stored normals of this mesh (rtx_scene_set_mesh_topology)
+	// (topologyNormalsStale: objN has been replaced since, so a call that keeps the normals sends the topology again)
+	bool trisStale = false, topologyOnDevice = false, topologyNormalsStale = false;
 
 	bool diffuseMapLoaded = false; int diffuseMapWidth = 0, diffuseMapHeight = 0; std::vector<Vec3f> diffuseMap;
 	bool normalMapLoaded = false; int normalMapWidth = 0, normalMapHeight = 0; std::vector<Vec3f> normalMap;

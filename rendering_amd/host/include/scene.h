@@ -93,6 +93,14 @@ public:
 	// one rtx_scene_set_objects (include/rtx_scene_edit.h) that keeps every other mesh as it is; if that fails the objects are put back.
 	size_t addObject(const std::string& type, const ObjectKeys& keys, size_t at = (size_t)-1);
 	void removeObject(size_t index);
+	// Gives mesh `index` the vertices (and, with N, the raw normals) an OBJ file with these v / vn lines would give it: nP x 3 / nN x 3 floats, the
+	// counts the mesh was loaded with.  onDevice: P and N are device pointers, produced on `stream`.  With a live GPU scene the device places the
+	// vertices, assembles the triangles and rebuilds the structure (rtx_scene_deform_mesh, include/rtx_deform.h); the host keeps objP / objN / objLo /
+	// objHi and places its own triangles when something reads them (syncTrees).  Without one the loader's code runs on the host.  Refused, the
+	// scene as it was: a bad index, an object that is no mesh, a wrong count, a vertex, normal or placed position that is not finite.
+	void setVertices(size_t index, const float* P, size_t nP, const float* N, size_t nN, bool onDevice, void* stream);
+	// host wall ms of the last setVertices: {the device call without the rebuild, the rebuild (rtx_scene_update_mesh), the host mirror, whole call}
+	double lastDeformMs[4] = { 0, 0, 0, 0 };
 	void syncTrees();                          // meshes moved on the GPU: their `ac` read back from the device (done by every reader of `ac`)
 	// host wall ms of the last moveObject: {placement (Mesh::place), upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
 	double lastMoveMs[4] = { 0, 0, 0, 0 };

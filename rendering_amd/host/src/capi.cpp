@@ -239,6 +239,87 @@ int rah_object_move(void* h, int obj, const float* pos3, const float* rot3, cons
 	});
 }
 
+namespace {
+Mesh* meshOf(void* h, int obj)
+{
+	Scene* s = (Scene*)h;
+	if (obj < 0 || obj >= (int)s->objects.size() || s->objects[obj]->objectType != ObjectType::Mesh) return nullptr;
+	return static_cast<Mesh*>(s->objects[obj].get());
+}
+}
+
+// What the loader kept of mesh `obj`'s OBJ file: c[8] = {triangles, vertices, normals, uv, vertices read before the first face, normals read
+// before it, has faces, -}.  -1: no such mesh.
+int rah_mesh_counts(void* h, int obj, long long* c)
+{
+	const Mesh* m = meshOf(h, obj);
+	if (!m) return -1;
+	c[0] = (long long)m->corners.size(); c[1] = (long long)m->objP.size(); c[2] = (long long)m->objN.size(); c[3] = (long long)m->objT.size();
+	c[4] = (long long)m->placedP; c[5] = (long long)m->placedN; c[6] = m->hasFaces ? 1 : 0; c[7] = 0;
+	return 0;
+}
+
+// The vertices (n x 3) and normals (n x 3, as stored: normalised) of mesh `obj`; either may be NULL.
+int rah_mesh_vertices(void* h, int obj, float* P, float* N)
+{
+	const Mesh* m = meshOf(h, obj);
+	if (!m) return -1;
+	if (P && !m->objP.empty()) memcpy(P, &m->objP[0].x, m->objP.size() * sizeof(Vec3f));
+	if (N && !m->objN.empty()) memcpy(N, &m->objN[0].x, m->objN.size() * sizeof(Vec3f));
+	return 0;
+}
+
+// The corners of mesh `obj`'s triangles (n x 3 each: position indices; normal and uv indices, [0] = -1 where the face gave none) and its uv (n x 2).
+int rah_mesh_topology(void* h, int obj, uint32_t* cornerPos, int32_t* cornerNrm, int32_t* cornerUv, float* uv)
+{
+	const Mesh* m = meshOf(h, obj);
+	if (!m) return -1;
+	for (size_t i = 0; i < m->corners.size(); ++i)
+		for (int k = 0; k < 3; ++k) {
+			if (cornerPos) cornerPos[i * 3 + k] = m->corners[i].v[k];
+			if (cornerNrm) cornerNrm[i * 3 + k] = m->corners[i].n[k];
+			if (cornerUv) cornerUv[i * 3 + k] = m->corners[i].t[k];
+		}
+	if (uv && !m->objT.empty()) memcpy(uv, &m->objT[0].x, m->objT.size() * sizeof(Vec2f));
+	return 0;
+}
+
+// New vertices (nP x 3) and, with N, raw normals (nN x 3) for mesh `obj` (Scene::setVertices); onDevice: device pointers produced on `stream`.
+// 0, or -1 with rah_last_error: the scene is then as it was.
+int rah_mesh_set_vertices(void* h, int obj, const float* P, long long nP, const float* N, long long nN, int onDevice, void* stream)
+{
+	return guarded<int>(-1, [&] {
+		if (obj < 0 || nP < 0 || nN < 0) { noteError("setVertices: bad index or count"); LOG_ERROR(); }
+		((Scene*)h)->setVertices((size_t)obj, P, (size_t)nP, N, (size_t)nN, onDevice != 0, stream);
+		return 0;
+	});
+}
+
+// host wall ms of the last rah_mesh_set_vertices: {device call without the rebuild, the rebuild, the host mirror, whole call}
+void rah_mesh_deform_times(void* h, float* ms4)
+{
+	for (int k = 0; k < 4; k++) ms4[k] = (float)((Scene*)h)->lastDeformMs[k];
+}
+
+// The rotation matrix the loader places a mesh with (Matrix44f::fromEulerDegrees, row-major): what rtx_mesh_pose::rot_matrix takes.
+void rah_euler_matrix(const float* rot3, float* m16)
+{
+	const Matrix44f R = Matrix44f::fromEulerDegrees(Vec3f(rot3[0], rot3[1], rot3[2]));
+	for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) m16[i * 4 + j] = R[i][j];
+}
+
+// pos3, rot3, size3 of mesh `obj` and the scene's bias and acPenalty: the pose it is placed with.
+int rah_mesh_pose(void* h, int obj, float* pos3, float* rot3, float* size3, float* bias, int* acPenalty)
+{
+	const Mesh* m = meshOf(h, obj);
+	if (!m) return -1;
+	const Scene* s = (Scene*)h;
+	pos3[0] = m->pos.x; pos3[1] = m->pos.y; pos3[2] = m->pos.z; rot3[0] = m->rot.x; rot3[1] = m->rot.y; rot3[2] = m->rot.z;
+	size3[0] = m->size.x; size3[1] = m->size.y; size3[2] = m->size.z;
+	*bias = s->options.bias; *acPenalty = s->options.acPenalty;
+	return 0;
+}
+
 // RTX_OBJ_* of object `obj` (-1: no such object)
 int rah_object_type(void* h, int obj)
 {

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <thread>
 
 #include <hip/hip_runtime_api.h>
@@ -16,6 +17,7 @@
 #include "../../../include/rtx.h"
 #include "../../../include/rtx_debug.h"
 #include "../../../include/rtx_scene_edit.h"
+#include "../../../include/rtx_deform.h"
 #include "stats.h"
 #include "timer.h"
 #include "util.h"
@@ -560,12 +562,14 @@ void Scene::moveObject(size_t index, const float* pos3, const float* rot3, const
 	float keepR = 0, keepR2 = 0;
 	Vec3f keepNormal, keepRot, keepSize, keepBounds[2];
 	std::vector<Triangle> keepTris;
+	bool keepStale = false;
 	if (o.objectType == ObjectType::Sphere) { keepR = static_cast<Sphere&>(o).r; keepR2 = static_cast<Sphere&>(o).r2; }
 	if (o.objectType == ObjectType::Plane) keepNormal = static_cast<Plane&>(o).normal;
 	if (o.objectType == ObjectType::Mesh) {
 		auto& m = static_cast<Mesh&>(o);
 		keepRot = m.rot; keepSize = m.size; keepBounds[0] = m.ac->rootBounds[0]; keepBounds[1] = m.ac->rootBounds[1];
 		keepTris.swap(m.allTris);
+		keepStale = m.trisStale;
 	}
 	auto restore = [&]() {
 		o.pos = keepPos;
@@ -575,6 +579,7 @@ void Scene::moveObject(size_t index, const float* pos3, const float* rot3, const
 			auto& m = static_cast<Mesh&>(o);
 			m.rot = keepRot; m.size = keepSize; m.ac->setBounds(keepBounds[0], keepBounds[1]);
 			m.allTris.swap(keepTris);
+			m.trisStale = keepStale;
 		}
 	};
 	try {
@@ -606,6 +611,7 @@ void Scene::moveObjectApply(size_t index, const float* pos3, const float* rot3, 
 		if (size3) m.size = Vec3f(size3[0], size3[1], size3[2]);
 		const double t0 = now();
 		m.place(options);
+		m.trisStale = false;
 		lastMoveMs[0] = now() - t0;
 		if (!gpu_) {
 			m.treeOnDevice = false;
@@ -648,6 +654,138 @@ void Scene::moveObjectApply(size_t index, const float* pos3, const float* rot3, 
 	m.treeOnDevice = true;
 	float ms[4];
 	if (rtx_scene_edit_times(gpu_, ms) == RTX_OK) { m.ac->buildMs = ms[0]; m.ac->builtOnDevice = true; }
+}
+
+// The vertices (and normals) of a mesh replaced (scene.h).  The host's copy of the inputs gives objP / objN and, by the loader's sequential
+// rule, objLo / objHi; the triangles come from Mesh::place on the host only where the host needs them.
+void Scene::setVertices(size_t index, const float* P, size_t nP, const float* N, size_t nN, bool onDevice, void* stream)
+{
+	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	const double tStart = now();
+	for (double& t : lastDeformMs) t = 0;
+	if (index >= objects.size()) { noteError("setVertices: object index out of range"); LOG_ERROR(); }
+	if (objects[index]->objectType != ObjectType::Mesh) { noteError("setVertices: object " + std::to_string(index) + " is not a mesh"); LOG_ERROR(); }
+	auto& m = static_cast<Mesh&>(*objects[index]);
+	if (!m.ac || !m.hasFaces) { noteError("setVertices: a mesh without faces"); LOG_ERROR(); }
+	if (!P || nP != m.objP.size()) { noteError("setVertices: the mesh has " + std::to_string(m.objP.size()) + " vertices, got " + std::to_string(nP)); LOG_ERROR(); }
+	if (N && nN != m.objN.size()) { noteError("setVertices: the mesh has " + std::to_string(m.objN.size()) + " normals, got " + std::to_string(nN)); LOG_ERROR(); }
+	// the host's copy of the inputs (12 bytes per vertex; the triangles never come down)
+	std::vector<Vec3f> newP(nP), newN(N ? nN : 0);
+	if (onDevice) {
+		hipCheck(hipSetDevice(device), "hipSetDevice");
+		if (stream) hipCheck(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+		if (nP) hipCheck(hipMemcpy(newP.data(), P, nP * sizeof(Vec3f), hipMemcpyDeviceToHost), "hipMemcpy (vertices)");
+		if (N && nN) hipCheck(hipMemcpy(newN.data(), N, nN * sizeof(Vec3f), hipMemcpyDeviceToHost), "hipMemcpy (normals)");
+	}
+	else {
+		if (nP) memcpy(newP.data(), P, nP * sizeof(Vec3f));
+		if (N && nN) memcpy(newN.data(), N, nN * sizeof(Vec3f));
+	}
+	auto finite3 = [](const Vec3f& v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+	for (const Vec3f& v : newP) if (!finite3(v)) { noteError("setVertices: a vertex is not finite"); LOG_ERROR(); }
+	for (const Vec3f& v : newN) if (!finite3(v)) { noteError("setVertices: a normal is not finite"); LOG_ERROR(); }
+	const double tCopied = now();
+	for (Vec3f& n : newN) n.normalize();      // (as the loader stores a vn line)
+	// the running box of the vertices read before the first face (objects.cpp:231-246)
+	const float big = std::numeric_limits<float>::max(), tiny = std::numeric_limits<float>::min();
+	Vec3f lo(big), hi(tiny);
+	for (size_t i = 0; i < m.placedP; ++i) {
+		const Vec3f& v = newP[i];
+		lo.x = std::min(v.x, lo.x); lo.y = std::min(v.y, lo.y); lo.z = std::min(v.z, lo.z);
+		hi.x = std::max(v.x, hi.x); hi.y = std::max(v.y, hi.y); hi.z = std::max(v.z, hi.z);
+	}
+	// what a refusal puts back (by swapping, not copying)
+	const Vec3f keepLo = m.objLo, keepHi = m.objHi, keepBounds[2] = { m.ac->rootBounds[0], m.ac->rootBounds[1] };
+	const bool keepStale = m.trisStale;
+	std::vector<Triangle> keepTris;
+	m.objP.swap(newP);
+	if (N) m.objN.swap(newN);
+	m.objLo = lo; m.objHi = hi;
+	auto restore = [&]() {
+		m.objP.swap(newP);
+		if (N) m.objN.swap(newN);
+		m.objLo = keepLo; m.objHi = keepHi; m.ac->setBounds(keepBounds[0], keepBounds[1]);
+		m.trisStale = keepStale;
+	};
+	const double tMirrored = now();
+	if (!gpu_) {
+		keepTris.swap(m.allTris);
+		try {
+			m.place(options);
+			for (const Triangle& t : m.allTris)
+				if (!finite3(t.a) || !finite3(t.b) || !finite3(t.c)) { noteError("setVertices: a placed position is not finite (a flat axis away from zero)"); LOG_ERROR(); }
+			m.trisStale = false;
+			m.treeOnDevice = false;
+			if (!m.ac->setup(m.allTris, options)) { noteError("setVertices: the acceleration structure could not be built"); LOG_ERROR(); }
+		}
+		catch (...) {
+			m.allTris.swap(keepTris);
+			restore();
+			throw;
+		}
+		lastDeformMs[2] = (tMirrored - tCopied) + (onDevice ? tCopied - tStart : 0);
+		lastDeformMs[3] = now() - tStart;
+		return;
+	}
+	float* dev = nullptr;
+	try {
+		uint32_t meshIndex = 0;
+		for (size_t i = 0; i < index; ++i) meshIndex += objects[i]->objectType == ObjectType::Mesh;
+		hipCheck(hipSetDevice(device), "hipSetDevice");
+		if (!m.topologyOnDevice || (!N && m.topologyNormalsStale)) {
+			// once per mesh: the corners, the uv and the stored normals (again when a call without normals follows one that replaced them)
+			const size_t nt = m.corners.size();
+			std::vector<uint32_t> cv(nt * 3);
+			std::vector<int32_t> cn(nt * 3), ct(nt * 3);
+			for (size_t i = 0; i < nt; ++i)
+				for (int k = 0; k < 3; ++k) { cv[i * 3 + k] = m.corners[i].v[k]; cn[i * 3 + k] = m.corners[i].n[k]; ct[i * 3 + k] = m.corners[i].t[k]; }
+			rtx_mesh_topology t{};
+			t.n_tris = (uint32_t)nt; t.n_pos = (uint32_t)m.objP.size(); t.n_nrm = (uint32_t)m.objN.size(); t.n_uv = (uint32_t)m.objT.size();
+			t.placed_pos = (uint32_t)m.placedP; t.placed_nrm = (uint32_t)m.placedN;
+			t.corner_pos = cv.data(); t.corner_nrm = cn.data(); t.corner_uv = ct.data();
+			t.uv = m.objT.empty() ? nullptr : &m.objT[0].x;
+			// (the normals as they were stored before this call: what a call without normals keeps)
+			const std::vector<Vec3f>& stored = N ? newN : m.objN;
+			t.nrm = stored.empty() ? nullptr : &stored[0].x;
+			gpuCheck(rtx_scene_set_mesh_topology(gpu_, meshIndex, &t), "rtx_scene_set_mesh_topology");
+			m.topologyOnDevice = true;
+			m.topologyNormalsStale = false;
+		}
+		const float* Pdev = P;
+		const float* Ndev = N;
+		if (!onDevice) {
+			// a host array goes up as vertices, never as triangles
+			const size_t nf = (nP + (N ? nN : 0)) * 3;
+			hipCheck(hipMalloc((void**)&dev, std::max<size_t>(nf, 1) * sizeof(float)), "hipMalloc");
+			hipCheck(hipMemcpy(dev, P, nP * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+			if (N && nN) hipCheck(hipMemcpy(dev + nP * 3, N, nN * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+			Pdev = dev; Ndev = N ? dev + nP * 3 : nullptr;
+		}
+		rtx_mesh_pose pose{};
+		put3(pose.pos, m.pos); put3(pose.size, m.size);
+		const Matrix44f R = Matrix44f::fromEulerDegrees(m.rot);
+		for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) pose.rot_matrix[i * 4 + j] = R[i][j];
+		pose.bias = options.bias; pose.ac_penalty = options.acPenalty;
+		const double t0 = now();
+		const int rc = rtx_scene_deform_mesh(gpu_, meshIndex, Pdev, (uint32_t)nP, Ndev, (uint32_t)(N ? nN : 0), &pose, nullptr, nullptr, onDevice ? stream : nullptr);
+		const double t1 = now();
+		gpuCheck(rc, "rtx_scene_deform_mesh");
+		float ms[4] = { 0, 0, 0, 0 };
+		if (rtx_scene_edit_times(gpu_, ms) == RTX_OK) { m.ac->buildMs = ms[0]; m.ac->builtOnDevice = true; }
+		lastDeformMs[1] = ms[3];
+		lastDeformMs[0] = (t1 - t0) - ms[3];
+	}
+	catch (...) {
+		if (dev) (void)hipFree(dev);
+		restore();
+		throw;
+	}
+	if (dev) (void)hipFree(dev);
+	m.treeOnDevice = true;
+	m.trisStale = true;
+	if (N) m.topologyNormalsStale = true;
+	lastDeformMs[2] = tMirrored - tStart;
+	lastDeformMs[3] = now() - tStart;
 }
 
 // The lights as the device should hold them now: one rtx_scene_set_lights (nothing to do before the GPU scene exists: it is created
@@ -797,6 +935,8 @@ void Scene::syncTrees()
 		if (op->objectType != ObjectType::Mesh) continue;
 		auto& m = static_cast<Mesh&>(*op);
 		const int32_t mi = meshIndex++;
+		// (a mesh the device deformed: the host's triangles of its current vertices, by the loader's code)
+		if (m.trisStale) { m.place(options); m.trisStale = false; }
 		if (!m.treeOnDevice || !gpu_) continue;
 		uint32_t counts[2] = { 0, 0 };
 		gpuCheck(rtx_scene_mesh_read(gpu_, (uint32_t)mi, counts, nullptr, nullptr, nullptr, nullptr, nullptr), "rtx_scene_mesh_read");
