@@ -37,6 +37,13 @@ int rtx_frame_mode_probe(int forced, int has_list, int fused_gave_up, uint32_t l
 int rtx_tile_list_probe(uint32_t width, uint32_t height, uint32_t band_height, uint32_t n_parts, uint32_t part, int halo, uint32_t row_begin, uint32_t row_end,
                         int strips, const uint32_t* rect4, uint32_t* out, size_t cap, size_t* need);
 
+/* Host only (no device is touched): the work items of a batch of views (include/rtx_views.h: rtx_render_views) for n_views views of the sizes sizes2 = {width0,
+ * height0, width1, height1, ...}, through the map the kernels use (csrc/rtx_views_plan.h: the first item of every view, viewOfItem,
+ * tileOfItem).  *n_items = their number; items3_out (may be NULL to ask for the number) receives, when cap_items >= *n_items, three words
+ * per item in item order: its view and the tile (tx, ty) of the view -- the pixels [8 tx, 8 tx + 8) x [8 ty, 8 ty + 8).  RTX_ERR_ARG for
+ * the sizes and counts rtx_render_views refuses.  tests/test_render_views_cpu.py. */
+int rtx_views_plan_probe(uint32_t n_views, const uint32_t* sizes2, uint32_t* items3_out, size_t cap_items, size_t* n_items);
+
 /* Host only: the P of the source copies of the prune records (rtx_device.h PruneRec, csrc/rtx_source.hip sourceP; DESIGN_HISTORY.md 3.1d)
  * for n triangles given as (v0, e1, e2) = 9 floats each, the source point S3, its radius sigma and cam != 0 when the rays start
  * at S (the camera) rather than pass through it (a point light).  The function the device kernels run, for the CPU tests of the

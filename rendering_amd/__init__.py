@@ -17,7 +17,7 @@ ROOT = os.path.dirname(HERE)
 LIB_RTX = os.path.join(HERE, "librtx_hip.so")
 LIB_HOST = os.path.join(HERE, "librendering_host.so")
 
-__all__ = ["load", "Scene", "Comm", "RtxError", "device_count", "math_probe", "gather_plan", "exported_symbols", "sphere_directions"]
+__all__ = ["load", "Scene", "Comm", "RtxError", "device_count", "math_probe", "gather_plan", "exported_symbols", "sphere_directions", "cube_cameras"]
 
 
 class RtxError(RuntimeError):
@@ -42,6 +42,7 @@ RTX_SYMBOLS = [
     "rtx_scene_mesh_read", "rtx_scene_mesh_flat_read", "rtx_scene_edit_times", "rtx_kernel_variant", "rtx_ssaa_list_read", "rtx_live_device_memory",
     "rtx_scene_lights_read", "rtx_scene_mesh_prune_copy_read", "rtx_scene_objects_read",
     "rtx_frame_mode_probe", "rtx_tile_list_probe", "rtx_place_probe",
+    "rtx_views_plan_probe",
 ]
 
 # the extension of include/rtx_scene_edit.h: editing a live scene (not part of the drop-in boundary)
@@ -65,6 +66,10 @@ RTX_LIGHT_SYMBOLS = ["rtx_light_rays"]
 
 # the extension of include/rtx_deform.h: deforming a mesh of a live scene from vertices on the device (not part of the drop-in boundary)
 RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
+
+# the extension of include/rtx_views.h: many views of a scene in one call (not part of the drop-in boundary; its probe, rtx_views_plan_probe, is
+# declared in include/rtx_debug.h and listed with the probes above)
+RTX_VIEWS_SYMBOLS = ["rtx_render_views"]
 
 
 class MeshTopology(C.Structure):
@@ -92,6 +97,31 @@ class LightBuffers(C.Structure):
     """rtx_light_buffers (include/rtx_light.h): the scene's number of lights and six device pointers, any of them NULL."""
     _fields_ = [("n_lights", C.c_uint32)] + [(n, C.c_void_p) for n in ("hits_dev", "diffuse_dev", "specular_dev", "light_diffuse_dev",
                                                                        "light_specular_dev", "light_open_dev")]
+
+
+class ViewTarget(C.Structure):
+    """rtx_view_target (include/rtx_views.h): one view of a batch -- size, camera, device buffers."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("cam_pos", C.c_float * 3), ("cam_matrix", C.c_float * 16),
+                ("scale", C.c_float), ("aspect", C.c_float), ("fb_dev", C.c_void_p), ("mask_dev", C.c_void_p)]
+
+
+def cube_cameras(pos):
+    """The six cameras of a cube map at `pos` for Scene.render_views, as (pos, rot, 90): the faces +x, -x, +y, -y, +z, -z (the camera
+    looks along -z of its own frame; rot in degrees, as in a scene file's [camera] block)."""
+    p = tuple(float(x) for x in np.asarray(pos, np.float32).reshape(3))
+    return [(p, rot, 90.0) for rot in ((0.0, 90.0, 0.0), (0.0, -90.0, 0.0), (-90.0, 0.0, 0.0), (90.0, 0.0, 0.0), (0.0, 180.0, 0.0), (0.0, 0.0, 0.0))]
+
+
+def views_plan_probe(sizes):
+    """Host only: the work items of Scene.render_views for views of the sizes [(width, height), ...] (rtx_views_plan_probe): uint32
+    (n_items, 3) of (view, tx, ty) in item order."""
+    rtx, _ = load()
+    sz = np.ascontiguousarray(np.asarray(sizes, np.uint32).reshape(-1, 2))
+    n = C.c_size_t(0)
+    _check(rtx.rtx_views_plan_probe(sz.shape[0], _np_ptr(sz), None, 0, C.byref(n)), "rtx_views_plan_probe")
+    out = np.zeros((n.value, 3), np.uint32)
+    _check(rtx.rtx_views_plan_probe(sz.shape[0], _np_ptr(sz), _np_ptr(out), n.value, C.byref(n)), "rtx_views_plan_probe")
+    return out
 
 
 class AoParams(C.Structure):
@@ -163,6 +193,10 @@ def load():
     rtx.rtx_surface_rays.argtypes = [vp, u32, vp, C.POINTER(SurfaceBuffers), vp]
     if hasattr(rtx, "rtx_light_rays"):      # (a library without it is reported by exported_symbols)
         rtx.rtx_light_rays.argtypes = [vp, u32, vp, C.POINTER(LightBuffers), vp]
+    if hasattr(rtx, "rtx_render_views"):      # (a library without them is reported by exported_symbols)
+        rtx.rtx_render_views.argtypes = [vp, u32, C.POINTER(ViewTarget), i32, vp]
+        rtx.rtx_views_plan_probe.argtypes = [u32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        host.rah_view_target.argtypes = [vp, vp, vp, C.c_float, i32, i32, C.POINTER(ViewTarget)]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -254,7 +288,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -1083,6 +1117,73 @@ class Scene:
         _, st = _query_stream(stream, self.device, [t for _, t, _, _ in given])
         bufs = AovBuffers(*[t.data_ptr() if t is not None else None for _, t, _, _ in given])
         _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(bufs), st), "rtx_render_aov")
+
+    def view_target(self, pos, rot, fov=None, width=None, height=None):
+        """The camera fields and size of one view of a batch (ViewTarget with NULL buffers; rah_view_target): what this scene's own view
+        would hold after set_camera(pos, rot) + resize(width, height) -- with the fov `fov` in degrees instead of the scene's when it is
+        given.  The scene itself is not changed.  Host only."""
+        t = ViewTarget()
+        self._fill_view_target(t, pos, rot, fov, self.width if width is None else int(width), self.height if height is None else int(height))
+        return t
+
+    def _fill_view_target(self, t, pos, rot, fov, w, h):
+        # (plain ctypes, no numpy: render_views does this once per camera)
+        p = (C.c_float * 3)(float(pos[0]), float(pos[1]), float(pos[2])); r = (C.c_float * 3)(float(rot[0]), float(rot[1]), float(rot[2]))
+        if self.host.rah_view_target(self.h, p, r, -1.0 if fov is None else float(fov), w, h, C.byref(t)) != 0:
+            raise ValueError("view_target: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    def render_views(self, cameras, fbs, masks=None, ssaa=False, stream=None):
+        """rtx_render_views: many views of this scene in one call.  cameras: a sequence of (pos, rot) or (pos, rot, fov) -- rot and fov in
+        degrees, fov None or absent: the scene's; cube_cameras(pos) gives the six of a cube map.  fbs: one float32 tensor (N, H, W, 3) or a
+        list of N tensors (H_i, W_i, 3), zeroed by the caller; the sizes of the views are the tensors'.  masks (required with ssaa, else
+        not written): uint8 (N, H, W) or a list of (H_i, W_i).  All contiguous and on this scene's device; no two views share memory.
+        View i receives the bits of set_camera + resize + render_pass1 (ssaa: + sobel + render_ssaa) with its camera and size; bias, ray
+        depth, background and the culling / skybox flags are this scene's current ones for every view.  The scene's own view, its tile
+        costs and its timings are left as they are.  Asynchronous on `stream` (None: torch's current stream of the scene's device); with a
+        torch.cuda.Stream the tensors are recorded on it."""
+        import torch
+        cameras = list(cameras)
+        n = len(cameras)
+        # one tensor for the batch: checked once, the views' addresses follow from its shape (no per-view tensor is made)
+        whole = isinstance(fbs, torch.Tensor)
+        if whole:
+            _check_tensor("render_views", "fbs", fbs, torch.float32, ("N", "H", "W", 3), self.device)
+        if isinstance(masks, torch.Tensor) != whole and masks is not None:
+            raise ValueError("render_views: fbs and masks must both be one tensor or both be lists")
+        if whole and masks is not None:
+            _check_tensor("render_views", "masks", masks, torch.uint8, (fbs.shape[0], fbs.shape[1], fbs.shape[2]), self.device)
+        fb_list = fbs if whole else list(fbs)
+        mask_list = masks if whole or masks is None else list(masks)
+        if len(fb_list) != n:
+            raise ValueError("render_views: %d cameras but %d framebuffers" % (n, len(fb_list)))
+        if ssaa and mask_list is None:
+            raise ValueError("render_views: ssaa needs masks")
+        if mask_list is not None and len(mask_list) != n:
+            raise ValueError("render_views: %d cameras but %d masks" % (n, len(mask_list)))
+        targets = (ViewTarget * max(n, 1))()
+        for i, cam in enumerate(cameras):
+            if len(cam) not in (2, 3):
+                raise ValueError("render_views: camera %d must be (pos, rot) or (pos, rot, fov)" % i)
+            if whole:
+                h, w = int(fbs.shape[1]), int(fbs.shape[2])
+                fb_ptr = fbs.data_ptr() + i * h * w * 12
+                mask_ptr = masks.data_ptr() + i * h * w if masks is not None else None
+            else:
+                fb = fb_list[i]
+                _check_tensor("render_views", "fbs[%d]" % i, fb, torch.float32, ("H", "W", 3), self.device)
+                h, w = int(fb.shape[0]), int(fb.shape[1])
+                fb_ptr, mask_ptr = fb.data_ptr(), None
+                if mask_list is not None:
+                    _check_tensor("render_views", "masks[%d]" % i, mask_list[i], torch.uint8, (h, w), self.device)
+                    mask_ptr = mask_list[i].data_ptr()
+            if h < 1 or w < 1:
+                raise ValueError("render_views: fbs[%d] is empty" % i)
+            t = targets[i]
+            self._fill_view_target(t, cam[0], cam[1], cam[2] if len(cam) == 3 else None, w, h)
+            t.fb_dev = fb_ptr
+            t.mask_dev = mask_ptr
+        _, st = _query_stream(stream, self.device, ([fbs, masks] if whole else fb_list + (mask_list or [])))
+        _check(self.rtx.rtx_render_views(self.gpu(), n, targets, 1 if ssaa else 0, st), "rtx_render_views")
 
     def render_ao(self, dirs, radius=float("inf"), ao=None, counts=None, rows=None, stream=None):
         """rtx_render_ao: ambient occlusion of the frame in one launch.  For every pixel of pass 1 whose primary ray hits, each direction

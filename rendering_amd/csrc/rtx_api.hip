@@ -23,6 +23,7 @@
 #include "../../include/rtx_ao.h"
 #include "../../include/rtx_surface.h"
 #include "../../include/rtx_light.h"
+#include "../../include/rtx_views.h"
 #include "rtx_device.h"
 #include "rtx_frame_plan.h"
 #include "rtx_own.h"
@@ -34,6 +35,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_kernels.hip"
 #include "rtx_source.hip"
 #include "rtx_rays.hip"
+#include "rtx_views.hip"
 #include "rtx_aov.hip"
 #include "rtx_ao.hip"
 #include "rtx_surface.hip"
@@ -223,6 +225,11 @@ struct rtx_scene {
 	int raySurfaceBlocks[2] = { 0, 0 };                        // rtx_surface_rays' kernel
 	int rayLightBlocks[2] = { 0, 0 };                          // rtx_light_rays' kernel
 	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
+	// rtx_render_views (rtx_views.hip): the view table of a batch (records, then the first item of every view) on the device and in the pinned
+	// buffer it is copied from -- viewsStaged: that copy, which the next call waits for before it fills the buffer again --, the heads, and
+	// with SSAA the view of every item and the list of flagged pixels.  They only grow.
+	DevArray<char> viewsTable; PinnedArray<char> viewsStage; Event viewsStaged; bool viewsStagePending = false;
+	DevArray<uint32_t> viewsWork, viewsItemView, viewsList;
 	// first-frame cost estimate (estimateCosts): the leaf arrays of the meshes, the cell grid, whether tileCost holds usable
 	// numbers (estimated or measured) for EVERY tile of the current view
 	struct MeshLeaves { const float* boxes; uint32_t n; };      // 8 floats per non-empty leaf: true box lo, hi, reference count, -
@@ -391,6 +398,18 @@ RayKernel rayColourKernel(const Variant& v)
 {
 	if (v.analytic) return rtxRayColourKernel<false, true, -1, false>;
 	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> RayKernel { return rtxRayColourKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+// rtx_render_views' pass-1 and SSAA kernels: the instances of rtxRayColourKernel
+typedef void (*ViewsKernel)(const ViewsKernArgs);
+ViewsKernel viewsPass1Kernel(const Variant& v)
+{
+	if (v.analytic) return rtxViewsPass1Kernel<false, true, -1, false>;
+	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> ViewsKernel { return rtxViewsPass1Kernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
+}
+ViewsKernel viewsSsaaKernel(const Variant& v)
+{
+	if (v.analytic) return rtxViewsSsaaKernel<false, true, -1, false>;
+	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> ViewsKernel { return rtxViewsSsaaKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
 }
 // (surface: the normal or the albedo is asked for -- only then is shadePrimary part of the kernel)
 typedef void (*AovKernel)(const Params, const rtx_aov_buffers);
@@ -2535,6 +2554,112 @@ int rtx_render_ao(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_ao
 	if (int ro = renderOn(s, st)) return ro;
 	const AoArgs a = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
 	hipLaunchKernelGGL(aoKernel(variantOf(s)), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, a);
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+namespace {
+
+// What rtx_render_views and its probe refuse of a batch's sizes; *items = the batch's tiles.
+int checkViewSizes(uint32_t n, const uint32_t* w, const uint32_t* h, size_t stride, uint64_t* items)
+{
+	if (n > rtxviews::kMaxViews) return fail(RTX_ERR_ARG, "rtx_render_views: more than RTX_VIEWS_MAX_VIEWS views");
+	uint64_t total = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t W = *(const uint32_t*)((const char*)w + i * stride), H = *(const uint32_t*)((const char*)h + i * stride);
+		if (W == 0 || H == 0) return fail(RTX_ERR_ARG, "rtx_render_views: view " + std::to_string(i) + " has a zero width or height");
+		if (W > rtxviews::kMaxSide || H > rtxviews::kMaxSide) return fail(RTX_ERR_ARG, "rtx_render_views: view " + std::to_string(i) + " is larger than RTX_VIEWS_MAX_SIDE");
+		total += rtxviews::tilesOf(W, H);
+	}
+	if (total > rtxviews::kMaxItems) return fail(RTX_ERR_ARG, "rtx_render_views: more than RTX_VIEWS_MAX_TILES tiles in all");
+	*items = total;
+	return RTX_OK;
+}
+
+} // namespace
+
+int rtx_views_plan_probe(uint32_t n_views, const uint32_t* sizes2, uint32_t* items3_out, size_t cap_items, size_t* n_items)
+{
+	if (!n_items || (n_views && !sizes2)) return fail(RTX_ERR_ARG, "rtx_views_plan_probe: NULL argument");
+	uint64_t items = 0;
+	if (int rc = checkViewSizes(n_views, sizes2, sizes2 + 1, 8, &items)) return rc;
+	*n_items = (size_t)items;
+	if (!items3_out || cap_items < items) return RTX_OK;
+	// the table as rtx_render_views lays it out, read as the kernels read it
+	std::vector<uint32_t> first(n_views + 1, 0u);
+	for (uint32_t v = 0; v < n_views; v++) first[v + 1] = first[v] + (uint32_t)rtxviews::tilesOf(sizes2[2 * v], sizes2[2 * v + 1]);
+	for (uint32_t item = 0; item < (uint32_t)items; item++) {
+		const uint32_t v = rtxviews::viewOfItem([&](uint32_t i) { return first[i]; }, n_views, item);
+		const rtxviews::Tile t = rtxviews::tileOfItem(item, first[v], rtxviews::tilesAcross(sizes2[2 * v]));
+		items3_out[3 * (size_t)item] = v; items3_out[3 * (size_t)item + 1] = t.tx; items3_out[3 * (size_t)item + 2] = t.ty;
+	}
+	return RTX_OK;
+}
+
+int rtx_render_views(rtx_scene* s, uint32_t n_views, const rtx_view_target* views, int with_ssaa, void* stream)
+{
+	RoctxRange range("Render views (rtx_render_views)");
+	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
+	if (n_views == 0) return RTX_OK;
+	if (!views) return fail(RTX_ERR_ARG, "rtx_render_views: views is NULL");
+	uint64_t items64 = 0;
+	if (int rc = checkViewSizes(n_views, &views[0].width, &views[0].height, sizeof(rtx_view_target), &items64)) return rc;
+	for (uint32_t i = 0; i < n_views; i++) {
+		if (!views[i].fb_dev) return fail(RTX_ERR_ARG, "rtx_render_views: view " + std::to_string(i) + " has no framebuffer (fb_dev is NULL)");
+		if (with_ssaa && !views[i].mask_dev) return fail(RTX_ERR_ARG, "rtx_render_views: view " + std::to_string(i) + " has no mask (mask_dev is NULL) and SSAA is asked for");
+	}
+	if (s->params.bandH && s->params.nParts > 1) return fail(RTX_ERR_ARG, "rtx_render_views: the rows are shared among devices (rtx_set_row_ownership); deal out views, not rows");
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_views collects no statistics (rtx_counters_enable)");
+	if (showNormals(s)) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_views does not render the normals view (RTX_FLAG_SHOW_NORMALS)");
+	const uint32_t nItems = (uint32_t)items64;
+	// (sizes the recursion frames for the current view's depth; the tile lists, tile costs and events are neither used nor touched from here on)
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	hipStream_t st = (hipStream_t)stream;
+	if ((rc = renderOn(s, st))) return rc;
+	// the batch's scratch: only a larger batch than any before allocates (which waits for the device)
+	const size_t recBytes = (size_t)n_views * sizeof(ViewRec), tableBytes = recBytes + ((size_t)n_views + 1) * sizeof(uint32_t);
+	HIPCHK(s->viewsTable.reserve(tableBytes));
+	HIPCHK(s->viewsWork.reserve(64));
+	if (with_ssaa) { HIPCHK(s->viewsItemView.reserve(nItems)); HIPCHK(s->viewsList.reserve((size_t)nItems * 64)); }
+	// the staging buffer is free again once the previous call's copy out of it has been made
+	if (s->viewsStagePending) { HIPCHK(hipEventSynchronize(s->viewsStaged)); s->viewsStagePending = false; }
+	HIPCHK(s->viewsStage.reserve(tableBytes));
+	ViewRec* recs = (ViewRec*)s->viewsStage.host();
+	uint32_t* first = (uint32_t*)(s->viewsStage.host() + recBytes);
+	uint32_t at = 0;
+	for (uint32_t i = 0; i < n_views; i++) {
+		const rtx_view_target& t = views[i];
+		ViewRec& r = recs[i];
+		r.width = t.width; r.height = t.height; r.scale = t.scale; r.aspect = t.aspect;
+		memcpy(r.camPos, t.cam_pos, 12); memcpy(r.camM, t.cam_matrix, 64);
+		r.firstItem = first[i] = at;
+		r.fb = t.fb_dev; r.mask = t.mask_dev;
+		r.tilesX = rtxviews::tilesAcross(t.width); r.pad[0] = r.pad[1] = r.pad[2] = 0;
+		at += (uint32_t)rtxviews::tilesOf(t.width, t.height);
+	}
+	first[n_views] = at;
+	HIPCHK(hipMemcpyAsync(s->viewsTable.get(), s->viewsStage.host(), tableBytes, hipMemcpyHostToDevice, st));
+	HIPCHK(s->viewsStaged.create(hipEventDisableTiming));
+	HIPCHK(hipEventRecord(s->viewsStaged, st));
+	s->viewsStagePending = true;
+	HIPCHK(hipMemsetAsync(s->viewsWork.get(), 0, 64 * sizeof(uint32_t), st));
+	ViewsKernArgs k;
+	k.P = s->params;
+	k.A.views = (const ViewRec*)s->viewsTable.get(); k.A.first = (const uint32_t*)(s->viewsTable.get() + recBytes);
+	k.A.nViews = n_views; k.A.nItems = nItems;
+	k.A.itemView = s->viewsItemView; k.A.list = s->viewsList; k.A.heads = s->viewsWork;
+	const Variant v = variantOf(s);
+	// (the recursion frames of the pass-1 area hold blocksPass1 blocks)
+	const uint32_t itemBlocks = (nItems + 3) / 4;
+	hipLaunchKernelGGL(viewsPass1Kernel(v), dim3(std::min<uint32_t>((uint32_t)s->blocksPass1, itemBlocks)), dim3(256), 0, st, k);
+	HIPCHK(hipGetLastError());
+	if (!with_ssaa) return RTX_OK;
+	hipLaunchKernelGGL(rtxViewsMaskKernel, dim3(itemBlocks), dim3(256), 0, st, k.A);
+	HIPCHK(hipGetLastError());
+	// (the list's length is the device's to know: at most four SSAA items per tile, and a wave that finds the queue empty ends at once)
+	k.P.frames = s->frames + s->framesArea;
+	hipLaunchKernelGGL(viewsSsaaKernel(v), dim3(std::min<uint32_t>((uint32_t)s->blocksSsaa, nItems)), dim3(256), 0, st, k);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

@@ -1690,23 +1690,26 @@ __device__ __forceinline__ void consume(const Params& P, Lane& s, const Hit& h)
 	}
 }
 
-__device__ __forceinline__ void primaryRay(const Params& P, float x, float y, V3& o, V3& d)
+// (VIEW: rtxd::View, or the record of one view of a batch -- rtxviews::ViewRec, rtx_views.hip -- which names its camera fields alike)
+template <typename VIEW>
+__device__ __forceinline__ void viewRay(const VIEW& view, float x, float y, V3& o, V3& d)
 {
 	// scene.cpp:453-457 (getPixels adds another 0.5) and Camera::getRay, scene.cpp:52-53
-	const float w = (float)P.view.width, hgt = (float)P.view.height;
-	const float xp = (2 * (x + 0.5f) / w - 1) * P.view.scale * P.view.aspect;
-	const float yp = -(2 * (y + 0.5f) / hgt - 1) * P.view.scale;
+	const float w = (float)view.width, hgt = (float)view.height;
+	const float xp = (2 * (x + 0.5f) / w - 1) * view.scale * view.aspect;
+	const float yp = -(2 * (y + 0.5f) / hgt - 1) * view.scale;
 	const V3 s = normalized(mk(xp, yp, -1));
-	const float* M = P.view.camM;
+	const float* M = view.camM;
 	V3 r;
 	r.x = s.x * M[0] + s.y * M[4] + s.z * M[8] + M[12];
 	r.y = s.x * M[1] + s.y * M[5] + s.z * M[9] + M[13];
 	r.z = s.x * M[2] + s.y * M[6] + s.z * M[10] + M[14];
 	const float ww = s.x * M[3] + s.y * M[7] + s.z * M[11] + M[15];
 	if (ww != 0.0f && ww != 1.0f) { const float wi = 1.0f / ww; r.x *= wi; r.y *= wi; r.z *= wi; }   // geometry.h:300-305
-	o = mk(P.view.camPos[0], P.view.camPos[1], P.view.camPos[2]);
+	o = mk(view.camPos[0], view.camPos[1], view.camPos[2]);
 	d = r;
 }
+__device__ __forceinline__ void primaryRay(const Params& P, float x, float y, V3& o, V3& d) { viewRay(P.view, x, y, o, d); }
 
 // The shading state of a lane that nothing reads while its ray is traced (the hit being shaded, the light, the sums):
 // parked in LDS around every trace so that the walk has the registers.  Left to the compiler it goes to scratch, i.e.

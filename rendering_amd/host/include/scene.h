@@ -142,6 +142,8 @@ private:
 // Host-side flattening used by Scene::gpu(); exposed for tests and for maintainers wiring the reference's own
 // Scene to the C ABI.
 struct FlatScene;
+// rtx_view::scale / aspect of a camera's fov (degrees) and a frame size, as the flattened view gets them (also rah_view_target, capi.cpp)
+void viewScaleAspect(float fov, size_t width, size_t height, float& scale, float& aspect);
 FlatScene* flattenScene(Scene& scene);
 const rtx_scene_desc* flatDesc(const FlatScene*);
 void freeFlatScene(FlatScene*);

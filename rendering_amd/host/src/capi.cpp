@@ -4,6 +4,7 @@
 #include <unistd.h>
 
 #include "../../../include/rtx.h"
+#include "../../../include/rtx_views.h"
 #include "scene.h"
 #include "stats.h"
 #include "util.h"
@@ -202,6 +203,24 @@ void rah_camera(void* h, float* scale, float* aspect, float* m16, float* pos3)
 		freeFlatScene(f);
 		return 0;
 	});
+}
+
+// The camera fields and the size of one view of a batch (rtx_view_target, include/rtx_views.h): exactly what fillView gives the scene's own view
+// after rah_camera_set(pos3, rot3) + rah_scene_resize(w, ht) -- and, with fov >= 0, with that fov in the scene file -- through the same Camera
+// code and the same tanf.  fov < 0: the scene's.  The scene is not changed; the buffers of `out` are left as they are.  -1: a bad size.
+int rah_view_target(void* h, const float* pos3, const float* rot3, float fov, int w, int ht, rtx_view_target* out)
+{
+	Scene* s = (Scene*)h;
+	if (w <= 0 || ht <= 0) { gLastError = "rah_view_target: width and height must be > 0"; return -1; }
+	Camera cam;
+	cam.pos = Vec3f(pos3[0], pos3[1], pos3[2]); cam.rot = Vec3f(rot3[0], rot3[1], rot3[2]);
+	cam.fov = fov >= 0 ? fov : s->camera.fov;
+	cam.ensureMatrix();
+	out->width = (uint32_t)w; out->height = (uint32_t)ht;
+	out->cam_pos[0] = cam.pos.x; out->cam_pos[1] = cam.pos.y; out->cam_pos[2] = cam.pos.z;
+	for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) out->cam_matrix[i * 4 + j] = cam.rMatrix[i][j];
+	viewScaleAspect(cam.fov, (size_t)w, (size_t)ht, out->scale, out->aspect);
+	return 0;
 }
 
 // rtx_view::flags this scene uploads (RTX_FLAG_*), -1 on error

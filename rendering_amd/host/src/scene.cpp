@@ -340,6 +340,12 @@ struct FlatScene {
 	std::vector<std::vector<float>> lightPoints;
 };
 
+void viewScaleAspect(float fov, size_t width, size_t height, float& scale, float& aspect)
+{
+	scale = tanf(fov * 0.5f / 180.0f * (float)(3.14159265358979323846));   // scene.cpp:447
+	aspect = (width) / (float)height;                                      // scene.cpp:448
+}
+
 namespace {
 
 void put3(float* d, const Vec3f& v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }
@@ -368,8 +374,7 @@ void fillView(Scene& sc, rtx_view& v)
 	v.flags = (sc.cullingOn() ? RTX_FLAG_BACKFACE_CULL : 0u) | (sc.skyboxOn() ? RTX_FLAG_SKYBOX : 0u) | (sc.normalsOn() ? RTX_FLAG_SHOW_NORMALS : 0u);
 	put3(v.cam_pos, sc.camera.pos);
 	for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) v.cam_matrix[i * 4 + j] = sc.camera.rMatrix[i][j];
-	v.scale = tanf(sc.camera.fov * 0.5f / 180.0f * (float)(3.14159265358979323846));   // scene.cpp:447
-	v.aspect = (sc.options.width) / (float)sc.options.height;                          // scene.cpp:448
+	viewScaleAspect(sc.camera.fov, sc.options.width, sc.options.height, v.scale, v.aspect);
 }
 
 // the lights' records in the description (an area light's sample points: AreaLight::setPoints, kept alive in `points`)
