@@ -64,6 +64,10 @@ RTX_SURFACE_SYMBOLS = ["rtx_surface_rays"]
 # the extension of include/rtx_light.h: direct light at the hits of caller-supplied rays (not part of the drop-in boundary)
 RTX_LIGHT_SYMBOLS = ["rtx_light_rays"]
 
+# the extension of include/rtx_scatter.h: reflection and refraction rays at the hits of caller-supplied rays, and the sky colour of rays
+# (not part of the drop-in boundary)
+RTX_SCATTER_SYMBOLS = ["rtx_scatter_rays", "rtx_sky_rays"]
+
 # the extension of include/rtx_deform.h: deforming a mesh of a live scene from vertices on the device (not part of the drop-in boundary)
 RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
 
@@ -97,6 +101,11 @@ class LightBuffers(C.Structure):
     """rtx_light_buffers (include/rtx_light.h): the scene's number of lights and six device pointers, any of them NULL."""
     _fields_ = [("n_lights", C.c_uint32)] + [(n, C.c_void_p) for n in ("hits_dev", "diffuse_dev", "specular_dev", "light_diffuse_dev",
                                                                        "light_specular_dev", "light_open_dev")]
+
+
+class ScatterBuffers(C.Structure):
+    """rtx_scatter_buffers (include/rtx_scatter.h): six device pointers, any of them NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("hits_dev", "local_dev", "reflect_dev", "refract_dev", "weight_dev", "kinds_dev")]
 
 
 class ViewTarget(C.Structure):
@@ -193,6 +202,9 @@ def load():
     rtx.rtx_surface_rays.argtypes = [vp, u32, vp, C.POINTER(SurfaceBuffers), vp]
     if hasattr(rtx, "rtx_light_rays"):      # (a library without it is reported by exported_symbols)
         rtx.rtx_light_rays.argtypes = [vp, u32, vp, C.POINTER(LightBuffers), vp]
+    if hasattr(rtx, "rtx_scatter_rays"):      # (a library without them is reported by exported_symbols)
+        rtx.rtx_scatter_rays.argtypes = [vp, u32, vp, C.POINTER(ScatterBuffers), vp]
+        rtx.rtx_sky_rays.argtypes = [vp, u32, vp, vp, vp]
     if hasattr(rtx, "rtx_render_views"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_render_views.argtypes = [vp, u32, C.POINTER(ViewTarget), i32, vp]
         rtx.rtx_views_plan_probe.argtypes = [u32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -245,6 +257,8 @@ def load():
     host.rah_camera.argtypes = [vp, vp, vp, vp, vp]
     host.rah_scene_digest.argtypes = [vp, vp, i32]
     host.rah_view_flags.argtypes = [vp]
+    if hasattr(host, "rah_max_ray_depth"):
+        host.rah_max_ray_depth.argtypes = [vp]
     host.rah_load_bmp.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, i32]
     host.rah_object_move.argtypes = [vp, i32] + [vp] * 5
     host.rah_object_type.argtypes = [vp, i32]
@@ -288,7 +302,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -1072,6 +1086,112 @@ class Scene:
             bufs = LightBuffers(nl, *ptrs)
             _check(self.rtx.rtx_light_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_light_rays")
         return out
+
+    SCATTER_CHANNELS = ("hits", "local", "reflect", "refract", "weight", "kinds")
+
+    def scatter_rays(self, rays, local=True, reflect=True, refract=True, weight=True, kinds=True, hits=False, stream=None):
+        """rtx_scatter_rays: what castRay does at the first hits of the rays of a device tensor short of recursing, on the device, bit for
+        bit (include/rtx_scatter.h).  rays: as for trace_rays.  Returns a dict of the channels asked for, new tensors on the rays' device:
+        "local" (n, 3), the part of the hit's colour that needs no further ray (all of it at a Diffuse or Phong hit and at a miss, the
+        specular highlight at a Reflective or Transparent one); "reflect" and "refract" (n, 6), the {orig, dir} of the secondary rays the
+        recursion casts; "weight" (n, 2), the factors their colours enter with; "kinds" (n,), torch.uint8, bit 0: there is a reflection
+        ray, bit 1: a refraction ray; "hits" (n, 8), trace_rays' record.  Rays and weights that do not exist are 0.  With C(r) the
+        colour of a child, the ray's colour is C(reflect) * 0.8 + local at a mirror, ((0 + C(refract) * weight[1]) + C(reflect) *
+        weight[0]) + local at glass (the refraction term only where bit 1 is set) and local itself where kinds is 0: cast_tree.
+        Asynchronous on `stream`, which is handled as in trace_rays."""
+        import torch
+        asked = [(name, shape, dtype) for name, on, shape, dtype in (
+            ("hits", hits, (8,), torch.float32), ("local", local, (3,), torch.float32), ("reflect", reflect, (6,), torch.float32),
+            ("refract", refract, (6,), torch.float32), ("weight", weight, (2,), torch.float32), ("kinds", kinds, (), torch.uint8)) if on]
+        if not asked:
+            raise ValueError("scatter_rays: nothing to compute (every channel is off)")
+        n = _check_rays("scatter_rays", rays, self.device)
+        alloc_on, st = _query_stream(stream, rays.device, (rays,))
+        with torch.cuda.stream(alloc_on):
+            out = {name: torch.empty((n,) + shape, dtype=dtype, device=rays.device) for name, shape, dtype in asked}
+        if n:
+            bufs = ScatterBuffers(*[out[name].data_ptr() if name in out else None for name in self.SCATTER_CHANNELS])
+            _check(self.rtx.rtx_scatter_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_scatter_rays")
+        return out
+
+    def sky(self, rays, stream=None):
+        """rtx_sky_rays: Scene::getSkybox of the directions of the rays of a device tensor -- the sky texel with useSkybox, the background
+        colour without, whatever the ray would hit: castRay's answer for a ray beyond max_ray_depth.  rays: as for trace_rays.  Returns a
+        new float32 tensor (n, 3) on the rays' device.  Asynchronous on `stream`, which is handled as in trace_rays."""
+        import torch
+        n = _check_rays("sky", rays, self.device)
+        alloc_on, st = _query_stream(stream, rays.device, (rays,))
+        with torch.cuda.stream(alloc_on):
+            c = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        if n:
+            _check(self.rtx.rtx_sky_rays(self.gpu(), n, _ptr(rays), _ptr(c), st), "rtx_sky_rays")
+        return c
+
+    @property
+    def max_ray_depth(self):
+        """the scene file's max_ray_depth: the deepest level of castRay's recursion that is still traced"""
+        return int(self.host.rah_max_ray_depth(self.h))
+
+    def cast_tree(self, rays, depth=None, stream=None):
+        """castRay level by level, in torch on top of scatter_rays and sky: level 0 is `rays`, level k + 1 the children of level k in the
+        order of their parents, a parent's refraction ray before its reflection ray.  A level up to `depth` (None: the scene's
+        max_ray_depth) is one scatter_rays call; the rays of the level beyond it are not traced, their colour is sky(); a negative depth
+        makes level 0 sky.  The children are compacted with a boolean mask, which costs one host synchronisation per level.  The colours
+        are then composed from the deepest level up with the identities of include/rtx_scatter.h as written there, so with depth=None
+        they are the bits of trace_rays(rays)[1].
+        Returns (colours (n, 3), levels): levels[k] is a dict of "rays" (m, 6), "parent" (m,) int64 index into level k - 1 (None at
+        level 0), "kind" (m,) uint8 (0 for a ray that is not traced), "weight" (m, 2), "local" (m, 3) and "colour" (m, 3).
+        Everything is queued on `stream`: None, torch's current stream, or a torch.cuda.Stream, which is made the current one for the
+        torch operations in between (a raw handle is refused)."""
+        import torch
+        _check_rays("cast_tree", rays, self.device)
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise ValueError("cast_tree: stream must be a torch.cuda.Stream or None, got %s" % type(stream).__name__)
+        depth = self.max_ray_depth if depth is None else int(depth)
+        levels, cur, parent = [], rays, None
+        if stream is not None:
+            rays.record_stream(stream)
+        with torch.cuda.stream(stream):
+            for k in range(max(depth, -1) + 2):
+                m = cur.shape[0]
+                if k > depth or m == 0:
+                    sky = self.sky(cur)
+                    levels.append(dict(rays=cur, parent=parent, kind=torch.zeros(m, dtype=torch.uint8, device=cur.device),
+                                       weight=torch.zeros((m, 2), dtype=torch.float32, device=cur.device), local=sky, colour=sky))
+                    break
+                s = self.scatter_rays(cur)
+                levels.append(dict(rays=cur, parent=parent, kind=s["kinds"], weight=s["weight"], local=s["local"], colour=None))
+                # the children: per parent {refract, reflect}, those that exist (the mask's count comes to the host: one synchronisation)
+                both = torch.stack([s["refract"], s["reflect"]], 1).reshape(2 * m, 6)
+                exists = torch.stack([(s["kinds"] & 2) != 0, (s["kinds"] & 1) != 0], 1).reshape(2 * m)
+                at = torch.nonzero(exists).reshape(-1)
+                if at.numel() == 0:
+                    break
+                cur, parent = both[at].contiguous(), at // 2
+                levels[-1]["child_slot"] = at
+            for k in range(len(levels) - 1, -1, -1):
+                lv = levels[k]
+                if lv["colour"] is not None:
+                    continue
+                m = lv["rays"].shape[0]
+                at = lv.pop("child_slot", None)
+                col = lv["local"].clone()
+                if at is not None:
+                    # colours of the children in the parents' slots: [:, 0] of the refraction ray, [:, 1] of the reflection ray
+                    cc = torch.zeros((2 * m, 3), dtype=torch.float32, device=col.device)
+                    cc[at] = levels[k + 1]["colour"]
+                    cc = cc.reshape(m, 2, 3)
+                    kind, w = lv["kind"], lv["weight"]
+                    # a mirror and glass in total internal reflection both have kind 1; glass composes from +0 as castRay does, which differs
+                    # from the mirror's form only in the sign of a zero, so the form is chosen by the weight the contract gives a mirror
+                    mirror = (kind == 1) & (w[:, 0] == torch.tensor(0.8, dtype=torch.float32, device=col.device))
+                    acc = torch.zeros((m, 3), dtype=torch.float32, device=col.device)
+                    acc = torch.where(((kind & 2) != 0)[:, None], acc + cc[:, 0] * w[:, 1:2], acc)
+                    glass = (acc + cc[:, 1] * w[:, 0:1]) + lv["local"]
+                    col = torch.where(((kind & 1) != 0)[:, None], glass, col)
+                    col = torch.where(mirror[:, None], cc[:, 1] * w[:, 0:1] + lv["local"], col)
+                lv["colour"] = col
+        return levels[0]["colour"], levels
 
     def occluded(self, rays, tmax=None, stream=None):
         """rtx_occluded_rays: is anything between a ray's origin and its range?  Render::trace of a shadow ray whose info.tNear starts at

@@ -23,6 +23,7 @@
 #include "../../include/rtx_ao.h"
 #include "../../include/rtx_surface.h"
 #include "../../include/rtx_light.h"
+#include "../../include/rtx_scatter.h"
 #include "../../include/rtx_views.h"
 #include "rtx_device.h"
 #include "rtx_frame_plan.h"
@@ -40,6 +41,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_ao.hip"
 #include "rtx_surface.hip"
 #include "rtx_light.hip"
+#include "rtx_scatter.hip"
 #undef RTX_QUERY_INSTANCES
 #undef RTX_MESH_INSTANCES
 
@@ -224,6 +226,7 @@ struct rtx_scene {
 	int rayHitBlocks[2] = { 0, 0 };
 	int raySurfaceBlocks[2] = { 0, 0 };                        // rtx_surface_rays' kernel
 	int rayLightBlocks[2] = { 0, 0 };                          // rtx_light_rays' kernel
+	int rayScatterBlocks[2] = { 0, 0 };                        // rtx_scatter_rays' kernel
 	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
 	// rtx_render_views (rtx_views.hip): the view table of a batch (records, then the first item of every view) on the device and in the pinned
 	// buffer it is copied from -- viewsStaged: that copy, which the next call waits for before it fills the buffer again --, the heads, and
@@ -393,6 +396,12 @@ RayLightKernel rayLightKernel(const Variant& v)
 {
 	if (v.analytic) return rtxRayLightKernel<false, true, -1>;
 	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayLightKernel { return rtxRayLightKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+typedef void (*RayScatterKernel)(const Params, const uint32_t*, const rtx_scatter_buffers);
+RayScatterKernel rayScatterKernel(const Variant& v)
+{
+	if (v.analytic) return rtxRayScatterKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayScatterKernel { return rtxRayScatterKernel<true, decltype(b)::value, decltype(c)::value>; });
 }
 RayKernel rayColourKernel(const Variant& v)
 {
@@ -1800,6 +1809,7 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 		s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;      // (the hit kernel's occupancy is the variant's)
 		s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
 		s->rayLightBlocks[0] = s->rayLightBlocks[1] = 0;
+		s->rayScatterBlocks[0] = s->rayScatterBlocks[1] = 0;
 		for (auto& b : s->rayOccludedBlocks) b[0] = b[1] = 0;
 	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
@@ -2358,6 +2368,8 @@ constexpr uint32_t kOccludedReorderMin = kTraceReorderMin;
 constexpr uint32_t kSurfaceReorderMin = kTraceReorderMin;
 // ... and rtx_light_rays': its first half is rtx_surface_rays' 
 constexpr uint32_t kLightReorderMin = kTraceReorderMin;
+// ... and rtx_scatter_rays': the same first half, and the same light loop for the hits that read the lights
+constexpr uint32_t kScatterReorderMin = kTraceReorderMin;
 
 // The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
 // for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
@@ -2511,6 +2523,45 @@ int rtx_light_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_li
 	if (!light) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
 	else rc = launchRays(s, rayLightKernel(v), s->rayLightBlocks[v.cull ? 1 : 0], c, *out);
 	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_scatter_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_scatter_buffers* out, void* stream)
+{
+	RoctxRange range("Scatter rays (rtx_scatter_rays)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	const bool scatter = out->local_dev || out->reflect_dev || out->refract_dev || out->weight_dev || out->kinds_dev;
+	if (!out->hits_dev && !scatter) return fail(RTX_ERR_ARG, "rtx_scatter_rays: no output (all six buffers are NULL)");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, rays_dev, kScatterReorderMin, stream, c, rc)) return rc;
+	const Variant v = variantOf(s);
+	c.p.workCounter = s->rayWork;
+	// the hit records alone: rtx_trace_rays' launch
+	if (!scatter) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
+	else rc = launchRays(s, rayScatterKernel(v), s->rayScatterBlocks[v.cull ? 1 : 0], c, *out);
+	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_sky_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* colours_dev, void* stream)
+{
+	RoctxRange range("Sky rays (rtx_sky_rays)");
+	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
+	if (n == 0) return RTX_OK;
+	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
+	if (!colours_dev) return fail(RTX_ERR_ARG, "rtx_sky_rays: no output (colours is NULL)");
+	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
+	// a plain grid over the rays: no walk, no queue, none of the scene's ray scratch
+	const hipStream_t st = (hipStream_t)stream;
+	int rc = ensureWork(s);
+	if (rc) return rc;
+	if ((rc = renderOn(s, st))) return rc;
+	Params p = s->params;
+	p.probeRays = rays_dev; p.nProbe = n;
+	hipLaunchKernelGGL(rtxRaySkyKernel, dim3((uint32_t)(((size_t)n + 255) / 256)), dim3(256), 0, st, p, colours_dev);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

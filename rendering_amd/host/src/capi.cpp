@@ -234,6 +234,9 @@ int rah_view_flags(void* h)
 	});
 }
 
+// rtx_view::max_ray_depth this scene uploads: the scene file's max_ray_depth (Scene.cast_tree's default depth)
+int rah_max_ray_depth(void* h) { return ((Scene*)h)->options.maxRayDepth; }
+
 // loadBMP (util.h) into a caller buffer of `cap` bytes; returns the number of bytes the image needs (3*w*h).
 // (-1: unreadable / unsupported file, rah_last_error; -2: the image needs more than INT_MAX bytes)
 int rah_load_bmp(const char* path, int* w, int* h, unsigned char* out, int cap)
