@@ -78,8 +78,6 @@ struct RoctxRange {
 	~RoctxRange() { if (on) roctx().pop(); }
 };
 
-int scanExclusive(uint32_t* data, uint32_t n, uint32_t* tmp, hipStream_t st, uint32_t& launches);   // rtx_bvh.hip
-
 int fail(int code, const std::string& msg) { gErr = msg; return code; }
 
 #define HIPCHK(expr)                                                                                         \
@@ -96,20 +94,6 @@ template <typename F> auto dispatchVariant(bool boxes, bool cull, bool third, F&
 	auto withThird = [&](auto b, auto c) { return third ? f(b, c, std::true_type()) : f(b, c, std::false_type()); };
 	auto withCull = [&](auto b) { return cull ? withThird(b, std::integral_constant<int, 1>()) : withThird(b, std::integral_constant<int, 0>()); };
 	return boxes ? withCull(std::true_type()) : withCull(std::false_type());
-}
-
-} // namespace
-
-namespace {
-
-// (v0, e1, e2, tri) of leaf reference r (objects.cpp:70-71: v0v1 = v1 - v0, v0v2 = v2 - v0)
-void makeRef(const rtx_mesh& m, uint32_t ref, RefA& a, RefB& b, RefC& c)
-{
-	const uint32_t t = m.refs[ref];
-	const float* p = m.tri_pos + (size_t)t * 9;
-	a.v0x = p[0]; a.v0y = p[1]; a.v0z = p[2]; a.tri = t;
-	b.e1x = p[3] - p[0]; b.e1y = p[4] - p[1]; b.e1z = p[5] - p[2];
-	b.e2x = p[6] - p[0]; c.e2y = p[7] - p[1]; c.e2z = p[8] - p[2];
 }
 
 } // namespace
@@ -677,303 +661,13 @@ int stamp(rtx_scene* s, int which, hipStream_t st)
 
 } // namespace
 
+// device-side acceleration-structure build (uses fail / HIPCHK above)
+#include "rtx_bvh.hip"
+
+// the flatten of a mesh on the host and on the device (uses the scene's internals above and the tree of rtx_bvh.hip)
+#include "rtx_flatten.hip"
+
 namespace {
-
-// The host side of a mesh's upload, free of any device call (so that it can be checked without a GPU: rtx_mesh_flatten_probe):
-// 32-byte node records, the tree with every other level skipped (when every box lies inside its parent's), and the prune
-// blocks of its slots (DESIGN_HISTORY.md 3.1c).
-struct FlatMesh {
-	std::vector<Node> nodes;
-	std::vector<WideNode> wide;
-	std::vector<PruneBlock> prune;
-	std::vector<uint32_t> slotRange;      // per wide-node slot: [begin, end) of leaf references covering the slot's subtree (rtx_source.hip)
-	PruneRec rootRec;
-	float vmaxMesh = 0;
-	bool boxesRegular = true;
-};
-
-int flattenMesh(const rtx_mesh& m, bool pruneWanted, FlatMesh& out)
-{
-	if (!m.node_bounds || !m.node_skip || !m.leaf_begin || !m.leaf_count || (m.n_refs && !m.refs) || (m.n_tris && !m.tri_pos)) return fail(RTX_ERR_ARG, "mesh arrays missing");
-	for (uint32_t r = 0; r < m.n_refs; r++)
-		if (m.refs[r] >= m.n_tris) return fail(RTX_ERR_ARG, "leaf reference out of range");
-	std::vector<Node> nodes(m.n_nodes);
-	bool boxesRegular = true;
-	for (uint32_t i = 0; i < m.n_nodes; i++) {
-		Node& nd = nodes[i];
-		for (int c = 0; c < 3; c++) {
-			nd.b[2 * c] = m.node_bounds[(size_t)i * 6 + c]; nd.b[2 * c + 1] = m.node_bounds[(size_t)i * 6 + 3 + c];
-			if (!(std::fabs(nd.b[2 * c]) < 1e30f && std::fabs(nd.b[2 * c + 1]) < 1e30f && nd.b[2 * c] <= nd.b[2 * c + 1])) boxesRegular = false;
-		}
-		if (m.leaf_count[i] < 0) {
-			if (m.node_skip[i] <= (int32_t)i + 1 || m.node_skip[i] > (int32_t)m.n_nodes) return (fail(RTX_ERR_ARG, "bad skip index"));
-			nd.link = m.node_skip[i]; nd.first = 0;
-			continue;
-		}
-		const uint32_t begin = (uint32_t)m.leaf_begin[i], count = (uint32_t)m.leaf_count[i];
-		if (begin + count > m.n_refs) return (fail(RTX_ERR_ARG, "leaf range out of bounds"));
-		nd.link = ~m.leaf_count[i]; nd.first = (int32_t)begin;
-	}
-	// every inner node has both children inside the array and inside its own subtree [i + 1, skip): the bottom-up passes below index
-	// the right child of EVERY node, reachable from the root or not (rtx_mesh_flatten_probe feeds raw arrays in here)
-	for (uint32_t i = 0; i < m.n_nodes; i++) {
-		if (m.leaf_count[i] >= 0) continue;
-		if (i + 1 >= m.n_nodes) return fail(RTX_ERR_ARG, "inner node without children");
-		const uint32_t right = m.leaf_count[i + 1] >= 0 ? i + 2 : (uint32_t)m.node_skip[i + 1];
-		if (right <= i + 1 || right >= (uint32_t)m.node_skip[i] || right >= m.n_nodes) return fail(RTX_ERR_ARG, "inner node whose right child lies outside its subtree");
-	}
-	// the tree with every other level skipped (rtxd::WideNode), when every box lies inside its parent's
-	std::vector<WideNode> wide;
-	
-	std::vector<PruneBlock> prune;
-	float vmaxMesh = 0;
-	PruneRec rootRec;
-	memset(&rootRec, 0, sizeof(rootRec));
-	rootRec.h[0] = rootRec.h[1] = rootRec.h[2] = INFINITY; rootRec.P = INFINITY;
-	std::vector<std::array<uint32_t, kWideSlots>> slotNode;      // binary node behind every wide-node slot
-	constexpr uint32_t kNoNode = 0xffffffffu;
-	std::array<uint32_t, kWideSlots> noSlots; noSlots.fill(kNoNode);
-	if (boxesRegular && m.n_nodes > 0) {
-		bool nested = true;
-		uint32_t depthMax = 0;
-		auto isLeaf = [&](uint32_t i) { return m.leaf_count[i] >= 0; };
-		auto rightOf = [&](uint32_t i) { return isLeaf(i + 1) ? i + 2 : (uint32_t)m.node_skip[i + 1]; };     // children of inner node i: i + 1 and this
-		auto inside = [&](uint32_t c, uint32_t p) {
-			for (int k = 0; k < 3; k++)
-				if (!(nodes[c].b[2 * k] >= nodes[p].b[2 * k] && nodes[c].b[2 * k + 1] <= nodes[p].b[2 * k + 1])) return false;
-			return true;
-		};
-		// iterative pre-order construction: (binary node, index of its wide node, depth)
-		struct Item { uint32_t node, wideIndex, depth; };
-		std::vector<Item> todo;
-		wide.emplace_back(); memset(&wide[0], 0, sizeof(WideNode));
-		slotNode.push_back(noSlots);
-		if (isLeaf(0)) { wide[0].slot[0] = nodes[0]; slotNode[0][0] = 0; }
-		else todo.push_back({ 0u, 0u, 1u });
-		while (!todo.empty() && nested) {
-			const Item it = todo.back(); todo.pop_back();
-			depthMax = std::max(depthMax, it.depth);
-			// the slots: the descendants kWideLevels levels below the node, left to right (a leaf on the way takes a slot itself)
-			uint32_t slots[kWideSlots]; int ns = 0;
-			std::function<void(uint32_t, int)> gather = [&](uint32_t node, int levels) {
-				if (!nested) return;
-				const uint32_t kids[2] = { node + 1, rightOf(node) };
-				for (uint32_t c : kids) {
-					if (c >= m.n_nodes || !inside(c, node)) { nested = false; return; }
-					if (isLeaf(c) || levels == 1) slots[ns++] = c;
-					else gather(c, levels - 1);
-					if (!nested) return;
-				}
-			};
-			gather(it.node, kWideLevels);
-			if (!nested) break;
-			// children wide nodes are created in REVERSE so that the vector stays in pre-order when popped; indices are fixed here
-			uint32_t childWide[kWideSlots] = { 0 };
-			for (int k = 0; k < ns; k++)
-				if (!isLeaf(slots[k])) { childWide[k] = (uint32_t)wide.size(); wide.emplace_back(); memset(&wide.back(), 0, sizeof(WideNode)); slotNode.push_back(noSlots); }
-			for (int k = ns - 1; k >= 0; k--) {
-				slotNode[it.wideIndex][k] = slots[k];
-				Node sl = nodes[slots[k]];
-				if (!isLeaf(slots[k])) { sl.link = (int32_t)childWide[k] + 1; sl.first = 0; todo.push_back({ slots[k], childWide[k], it.depth + 1 }); }
-				wide[it.wideIndex].slot[k] = sl;
-			}
-		}
-		// The walk's stack: while a node of wide level L is visited, every level above it has at most kWideSlots - 1 of its slots waiting and the node
-		// pushes at most kWideSlots -- (kWideSlots - 1) (L - 1) + kWideSlots entries.  A tree deeper than the stack allows is walked in the binary form
-		// (eight slots, 72 entries: ten wide levels = thirty binary ones need 71; the 250 000-triangle mesh has 27).
-		if (!nested || (kWideSlots - 1) * depthMax + 1 > kWideStackEntries) wide.clear();      // (wideStack holds kWideStackEntries per wave)
-		if (!wide.empty() && pruneWanted) {
-			// Prune records (rtxd::PruneRec): per binary node the true box of the triangles its subtree references and the
-			// largest |e1|_1 |e2|_1 among them (bottom-up over the pre-order array), then one record per wide-node slot.
-			// The triangle as the exact test sees it: v0, v0 + e1, v0 + e2 with the fp32 differences of makeRef (objects.cpp:70-71).
-			struct Agg { double lo[3], hi[3], ps, qlo[3], qhi[3], wlo, whi; bool planes; uint32_t rb, re; };
-			std::vector<Agg> agg(m.n_nodes);
-			for (uint32_t i = m.n_nodes; i-- > 0;) {
-				Agg& a = agg[i];
-				for (int k = 0; k < 3; k++) { a.lo[k] = a.qlo[k] = INFINITY; a.hi[k] = a.qhi[k] = -INFINITY; }
-				a.ps = 0; a.wlo = INFINITY; a.whi = -INFINITY; a.planes = true; a.rb = 0xffffffffu; a.re = 0;
-				auto merge = [&](const Agg& b) {
-					a.rb = std::min(a.rb, b.rb); a.re = std::max(a.re, b.re);
-					for (int k = 0; k < 3; k++) {
-						a.lo[k] = std::min(a.lo[k], b.lo[k]); a.hi[k] = std::max(a.hi[k], b.hi[k]);
-						a.qlo[k] = std::min(a.qlo[k], b.qlo[k]); a.qhi[k] = std::max(a.qhi[k], b.qhi[k]);
-					}
-					a.ps = std::max(a.ps, b.ps); a.wlo = std::min(a.wlo, b.wlo); a.whi = std::max(a.whi, b.whi);
-					a.planes = a.planes && b.planes;
-				};
-				if (!isLeaf(i)) { merge(agg[i + 1]); merge(agg[rightOf(i)]); continue; }
-				const uint32_t begin = (uint32_t)m.leaf_begin[i], count = (uint32_t)m.leaf_count[i];
-				if (count) { a.rb = begin; a.re = begin + count; }
-				for (uint32_t r = begin; r < begin + count; r++) {
-					RefA ra; RefB rb; RefC rc;
-					makeRef(m, r, ra, rb, rc);
-					const double v0[3] = { ra.v0x, ra.v0y, ra.v0z }, e1[3] = { rb.e1x, rb.e1y, rb.e1z }, e2[3] = { rb.e2x, rc.e2y, rc.e2z };
-					double s1 = 0, s2 = 0;
-					for (int k = 0; k < 3; k++) {
-						const double x1 = v0[k] + e1[k], x2 = v0[k] + e2[k];
-						a.lo[k] = std::min(a.lo[k], std::min(v0[k], std::min(x1, x2)));
-						a.hi[k] = std::max(a.hi[k], std::max(v0[k], std::max(x1, x2)));
-						s1 += std::fabs(e1[k]); s2 += std::fabs(e2[k]);
-					}
-					a.ps = std::max(a.ps, s1 * s2);
-					// scaled plane normal q = (e2 x e1) / (s1 s2) and offset v0 . q.  A triangle with a zero edge can never be
-					// accepted (det_c = 0 exactly) and bounds nothing; one whose scale underflows spoils the slot's plane bound.
-					if (s1 == 0 || s2 == 0) continue;
-					const double sc = s1 * s2;
-					if (!(sc > 1e-30) || !std::isfinite(sc)) { a.planes = false; continue; }
-					const double mq[3] = { (e2[1] * e1[2] - e2[2] * e1[1]) / sc, (e2[2] * e1[0] - e2[0] * e1[2]) / sc, (e2[0] * e1[1] - e2[1] * e1[0]) / sc };
-					double w = 0;
-					for (int k = 0; k < 3; k++) { a.qlo[k] = std::min(a.qlo[k], mq[k]); a.qhi[k] = std::max(a.qhi[k], mq[k]); w += v0[k] * mq[k]; }
-					a.wlo = std::min(a.wlo, w); a.whi = std::max(a.whi, w);
-				}
-			}
-			auto makeRec = [&](const Agg& a, PruneRec& pr) {
-				memset(&pr, 0, sizeof(pr));
-				pr.h[0] = pr.h[1] = pr.h[2] = -1e30f;      // empty: nothing can meet it
-				if (!(a.lo[0] <= a.hi[0])) return;         // no triangles
-				bool finite = std::isfinite(a.ps);
-				for (int c = 0; c < 3; c++) finite = finite && std::isfinite(a.lo[c]) && std::isfinite(a.hi[c]);
-				if (!finite) { pr.h[0] = pr.h[1] = pr.h[2] = INFINITY; pr.P = pr.Pgen = INFINITY; return; }      // never pruned
-				for (int c = 0; c < 3; c++) {
-					const double mid = 0.5 * (a.lo[c] + a.hi[c]), big = std::max(std::fabs(a.lo[c]), std::fabs(a.hi[c]));
-					pr.c[c] = (float)mid;
-					// [c - h, c + h] really contains [lo, hi] (c is rounded, h rounded up)
-					pr.h[c] = (float)((0.5 * (a.hi[c] - a.lo[c]) + std::fabs((double)pr.c[c] - mid)) * (1.0 + 0x1p-20) + 0x1p-24 * big + 1e-37);
-				}
-				pr.P = pr.Pgen = (float)(a.ps * (1.0 + 0x1p-20) + 1e-37);
-			};
-			makeRec(agg[0], rootRec);
-			prune.resize(wide.size());
-			out.slotRange.assign(wide.size() * kWideSlots * 2, 0u);
-			for (int c = 0; c < 3; c++) vmaxMesh = std::max(vmaxMesh, (float)std::max(std::fabs(agg[0].lo[c]), std::fabs(agg[0].hi[c])));
-			for (size_t wi = 0; wi < wide.size(); wi++)
-				for (int k = 0; k < kWideSlots; k++) {
-					PruneRec& pr = prune[wi].box[k];
-					PlaneRec& pl = prune[wi].plane[k];
-					memset(&pr, 0, sizeof(pr)); memset(&pl, 0, sizeof(pl));
-					pr.h[0] = pr.h[1] = pr.h[2] = -1e30f;      // empty: nothing can meet it
-					// no plane bound: a record that can never be "dead" whatever the bundle -- q = 0 +- 0 (max dir . q + 2 kd >= 0), offsets in [-inf, +inf]
-					// (planeAlive's three rejections are all false for it; pruneEval8 has no separate "usable" test)
-					pl.wlo = -INFINITY; pl.whi = INFINITY;
-					const uint32_t nd = slotNode[wi][k];
-					if (nd == kNoNode) continue;
-					const Agg& a = agg[nd];
-					if (a.rb < a.re) { out.slotRange[(wi * kWideSlots + k) * 2] = a.rb; out.slotRange[(wi * kWideSlots + k) * 2 + 1] = a.re; }
-					makeRec(a, pr);
-					if (!(a.lo[0] <= a.hi[0]) || !std::isfinite(pr.P)) continue;
-					if (a.planes && a.wlo <= a.whi && std::isfinite(a.wlo) && std::isfinite(a.whi)) {
-						for (int c = 0; c < 3; c++) {
-							const double mid = 0.5 * (a.qlo[c] + a.qhi[c]);
-							pl.qc[c] = (float)mid;
-							pl.qr[c] = (float)((0.5 * (a.qhi[c] - a.qlo[c]) + std::fabs((double)pl.qc[c] - mid)) * (1.0 + 0x1p-20) + 0x1p-24);
-						}
-						pl.wlo = (float)(a.wlo - (std::fabs(a.wlo) * 0x1p-22 + 1e-37)); pl.whi = (float)(a.whi + (std::fabs(a.whi) * 0x1p-22 + 1e-37));
-					}
-				}
-		}
-	}
-	out.nodes.swap(nodes); out.wide.swap(wide); out.prune.swap(prune);
-	out.rootRec = rootRec; out.vmaxMesh = vmaxMesh; out.boxesRegular = boxesRegular;
-	return RTX_OK;
-}
-
-// The geometry of mesh `mi` as rtx_scene_create uploads it: the flattened tree (flattenMesh), the leaf boxes of the cost estimate, the wide nodes,
-// the prune blocks and their source copies, the leaf references, the bundle-splitting terms.  Fills those fields of dm, the mesh's source
-// record, its leaves and its root box; every allocation goes to `owned` (counted as scene data, but for the sources' scratch).
-// rtx_scene_update_mesh (rtx_edit.hip) does the same on the device for new triangles (deviceMeshGeometry, rtx_flatten.hip).
-int uploadMeshGeometry(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, DevBag& owned, Mesh& dm, rtx_scene::SrcMesh& sm,
-                       rtx_scene::MeshLeaves& leaves, float bounds[6])
-{
-	FlatMesh flat;
-	{
-		const int frc = flattenMesh(m, s->knobs.prune, flat);
-		if (frc) return frc;
-	}
-	std::vector<Node>& nodes = flat.nodes;
-	std::vector<WideNode>& wide = flat.wide;
-	std::vector<PruneBlock>& prune = flat.prune;
-	const PruneRec rootRec = flat.rootRec;
-	const float vmaxMesh = flat.vmaxMesh;
-	const bool boxesRegular = flat.boxesRegular;
-	// leaf references in the reference's order, three parallel arrays padded by one wave
-	std::vector<RefA> refA((size_t)m.n_refs + 64);
-	std::vector<RefB> refB((size_t)m.n_refs + 64);
-	std::vector<RefC> refC((size_t)m.n_refs + 64);
-	memset(refA.data(), 0, refA.size() * sizeof(RefA)); memset(refB.data(), 0, refB.size() * sizeof(RefB)); memset(refC.data(), 0, refC.size() * sizeof(RefC));
-	for (uint32_t r = 0; r < m.n_refs; r++) {
-		if (m.refs[r] >= m.n_tris) return (fail(RTX_ERR_ARG, "leaf reference out of range"));
-		makeRef(m, r, refA[r], refB[r], refC[r]);
-	}
-	for (int c = 0; c < 6; c++) bounds[c] = m.n_nodes ? m.node_bounds[c] : 0.0f;
-	HIPCHK(owned.upload(nodes.data(), nodes.size(), &dm.nodes));
-	{
-		// for the first-frame cost estimate: the TRUE box of every non-empty leaf's triangles and its reference count
-		std::vector<float> lb;
-		for (uint32_t i = 0; i < m.n_nodes; i++) {
-			if (m.leaf_count[i] <= 0) continue;
-			float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-			for (uint32_t r = (uint32_t)m.leaf_begin[i]; r < (uint32_t)(m.leaf_begin[i] + m.leaf_count[i]); r++) {
-				const float* p = m.tri_pos + (size_t)m.refs[r] * 9;
-				for (int v = 0; v < 9; v++) { lo[v % 3] = std::min(lo[v % 3], p[v]); hi[v % 3] = std::max(hi[v % 3], p[v]); }
-			}
-			if (!(std::isfinite(lo[0] + lo[1] + lo[2] + hi[0] + hi[1] + hi[2]))) continue;
-			lb.insert(lb.end(), { lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], (float)m.leaf_count[i], 0.0f });
-		}
-		const float* dev = nullptr;
-		HIPCHK(owned.upload(lb.data(), lb.size(), &dev));
-		leaves = { dev, (uint32_t)(lb.size() / 8) };
-	}
-	HIPCHK(owned.upload(wide.data(), wide.size(), &dm.wide));
-	dm.nWide = (uint32_t)wide.size();
-	// prune blocks: copy 0 (any ray) followed by the source copies (rtxd::PruneRec: the camera's, the point lights'), all
-	// equal to copy 0 until buildSources patches their P
-	sm = rtx_scene::SrcMesh();
-	const uint32_t nCopies = (s->knobs.sources && !prune.empty()) ? 2u + std::min<uint32_t>(nLights, kMaxSrcLights) : 1u;
-	if (!prune.empty()) {
-		PruneBlock* pb = nullptr;
-		if (owned.alloc(&pb, (size_t)nCopies * prune.size() * sizeof(PruneBlock)) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (prune blocks)"));
-		for (uint32_t c = 0; c < nCopies; c++)
-			if (hipMemcpy(pb + (size_t)c * prune.size(), prune.data(), prune.size() * sizeof(PruneBlock), hipMemcpyHostToDevice) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMemcpy (prune blocks)"));
-		dm.prune = pb;
-		sm.pruneAlloc = pb; sm.pruneWide = (uint32_t)prune.size();
-		if (nCopies > 1) { sm.base = pb; sm.nWide = (uint32_t)prune.size(); }
-	}
-	dm.vmax = vmaxMesh;
-	dm.rootRec = rootRec;
-	if (!(vmaxMesh < 0x1p40f)) { dm.prune = nullptr; dm.rootRec.h[0] = dm.rootRec.h[1] = dm.rootRec.h[2] = INFINITY; }      // (huge or non-finite coordinates: nothing is pruned)
-	HIPCHK(owned.upload(refA.data(), refA.size(), &dm.refA));
-	HIPCHK(owned.upload(refB.data(), refB.size(), &dm.refB));
-	HIPCHK(owned.upload(refC.data(), refC.size(), &dm.refC));
-	if (sm.base && vmaxMesh < 0x1p40f && m.n_refs) {
-		sm.nRefs = m.n_refs; sm.refA = dm.refA; sm.refB = dm.refB; sm.refC = dm.refC; sm.vmax = vmaxMesh; sm.meshIndex = mi;
-		HIPCHK(owned.upload(flat.slotRange.data(), flat.slotRange.size(), &sm.slotRange));
-		if (owned.alloc(&sm.refP, ((size_t)m.n_refs + m.n_refs / 64 + 2) * sizeof(float), false) != hipSuccess) return (fail(RTX_ERR_DEVICE, "hipMalloc (source scratch)"));
-		sm.blockP = sm.refP + m.n_refs;
-	}
-	else sm.base = nullptr;
-	dm.nNodes = m.n_nodes; dm.nRefs = m.n_refs; dm.nTris = m.n_tris; dm.boxesRegular = boxesRegular ? 1u : 0u;
-	{
-		// mean edge length of the referenced triangles -> width above which a ray bundle is split (performance only)
-		double sum = 0; size_t cnt = 0;
-		const size_t stride = m.n_refs > 65536 ? m.n_refs / 65536 : 1;
-		for (size_t r = 0; r < m.n_refs; r += stride) {
-			const RefB& b = refB[r]; const RefC& c = refC[r];
-			const double l1 = std::sqrt((double)b.e1x * b.e1x + (double)b.e1y * b.e1y + (double)b.e1z * b.e1z);
-			const double l2 = std::sqrt((double)b.e2x * b.e2x + (double)c.e2y * c.e2y + (double)c.e2z * c.e2z);
-			if (std::isfinite(l1 + l2)) { sum += l1 + l2; cnt += 2; }
-		}
-		const float factor = s->knobs.fatFactor;
-		dm.fatRadius = cnt && factor > 0 ? (float)(sum / (double)cnt) * factor : INFINITY;
-		double rad = 0;
-		for (int c = 0; c < 3; c++) {
-			const double lo = m.n_nodes ? m.node_bounds[c] : 0.0, hi = m.n_nodes ? m.node_bounds[3 + c] : 0.0;
-			dm.centre[c] = (float)(0.5 * (lo + hi)); rad += 0.25 * (hi - lo) * (hi - lo);
-		}
-		dm.radius = (float)std::sqrt(rad);
-		if (!std::isfinite(dm.radius)) { dm.radius = 0; dm.fatRadius = INFINITY; }
-	}
-	return RTX_OK;
-}
 
 // The fields of a mesh object's record that derive from its mesh (bx: the mesh's root box, its six floats of meshBounds).
 void meshObjectRecord(const float* bx, Object& d, const Mesh& dm, const rtx_scene::SrcMesh& sm)
@@ -2751,9 +2445,6 @@ int rtx_vec_probe(int device, int op, uint32_t n, const float* a, const float* b
 }
 
 } // extern "C"
-
-// device-side acceleration-structure build (uses fail / HIPCHK above)
-#include "rtx_bvh.hip"
 
 // multi-GPU: RCCL communicator + frame gather (uses fail / HIPCHK above)
 #include "rtx_comm.hip"

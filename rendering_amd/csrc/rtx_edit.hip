@@ -1,14 +1,12 @@
 // Editing a live scene (include/rtx_scene_edit.h): an object's record (rtx_scene_set_object), a mesh's triangles
 // (rtx_scene_update_mesh), the lights (rtx_scene_set_lights) and the object and mesh lists (rtx_scene_set_objects).  A scene edited here holds what rtx_scene_create would have uploaded for the edited description: the mesh's
-// structure is built again on the device with the reference's builder (rtx_bvh.hip) and flattened with the very code the load runs
-// (flattenMesh / uploadMeshGeometry in rtx_api.hip); everything derived from the geometry that preparing a view reads is rebuilt.
-// Part of rtx_api.hip's translation unit (no kernel of its own).
+// structure is built again on the device with the reference's builder (rtx_bvh.hip) and flattened there with the record formulas the load runs on
+// the host (rtx_flatten.hip: deviceMeshGeometry beside uploadMeshGeometry, both over rtx_flat_records.h); everything derived from the geometry that
+// preparing a view reads is rebuilt.  Part of rtx_api.hip's translation unit (no kernel of its own).
 
 #include <chrono>
 
 int rtxBvhBuildDevice(const float* tri_pos_dev, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out);
-
-#include "rtx_flatten.hip"
 
 namespace {
 

@@ -44,6 +44,7 @@
 #include <math.h>
 
 #include "rtx_device.h"
+#include "rtx_flat_records.h"
 
 namespace rtxsrc {
 
@@ -55,7 +56,7 @@ __host__ __device__ inline float sourceP(const float v0[3], const float e1[3], c
 	const double u = 0x1p-24;
 	const double s1 = fabs((double)e1[0]) + fabs((double)e1[1]) + fabs((double)e1[2]), s2 = fabs((double)e2[0]) + fabs((double)e2[1]) + fabs((double)e2[2]);
 	const double pgen = s1 * s2;
-	const float pgenF = (float)(pgen * (1.0 + 0x1p-20) + 1e-37);      // (as flattenMesh rounds a slot's Pgen)
+	const float pgenF = rtxflat::roundPgen(pgen);                     // (as the flatten rounds a slot's Pgen)
 	if (!(pgen > 0.0) || !(pgen <= 0.0159)) return pgenF;             // (zero edge: never accepted -- any P will do; NaN / large: no certificate)
 	const double m[3] = { (double)e2[1] * e1[2] - (double)e2[2] * e1[1], (double)e2[2] * e1[0] - (double)e2[0] * e1[2], (double)e2[0] * e1[1] - (double)e2[1] * e1[0] };
 	const double mm = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);

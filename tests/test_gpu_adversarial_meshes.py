@@ -190,3 +190,44 @@ def test_raw_triangles_through_update_mesh(ra, tmp_path, name):
         else:
             assert copies.shape[0] == 0 and copies.shape[1] == 0, "%s: prune blocks without a wide tree" % what
     g.close()
+
+
+@pytest.mark.parametrize("name", ["two", "stack_129", "tiny"])
+def test_updated_mesh_has_a_created_scenes_estimate_and_prune_copies(ra, tmp_path, name):
+    """The two outputs of the flatten that (d) does not read -- the leaf boxes of the cost estimate and the slots' reference ranges, which
+    the source copies of the prune blocks are built from: a scene created from the family's raw triangles written as an OBJ (the host
+    flatten) against a stand-in scene whose mesh rtx_scene_update_mesh replaces with the created scene's placed triangles and root box (the
+    device flatten), under one new view: cost_grid() and every copy of the prune blocks."""
+    obj = tmp_path / "raw.obj"
+    obj.write_text(A.obj_text(A.raw_form(name)[0]))
+    base = A.base_scene("two")
+    f = ra.Scene(write_scene(tmp_path, add_object(base, "mesh", None, **A.mesh_keys("two", obj)), "created"), W, H)
+    tree = f.bvh(1)
+    t = np.ascontiguousarray(tree["tris"][:, 0:9], np.float32)
+    n = len(t)
+    lo = np.ascontiguousarray(tree["bounds"][0, 0:3], np.float32); hi = np.ascontiguousarray(tree["bounds"][0, 3:6], np.float32)
+    stand_in = np.array(A.pins() + [A.corner((0.125 + 0.75 * (i % 32) / 32, 0.125 + 0.75 * (i // 32) / 36, 0.5), 0.015625) for i in range(n - 2)])
+    obj = tmp_path / "stand_in.obj"
+    obj.write_text(A.obj_text(stand_in))
+    g = ra.Scene(write_scene(tmp_path, add_object(base, "mesh", None, **A.mesh_keys("two", obj)), "stand_in"), W, H)
+    assert g.bvh(1)["n_tris"] == n
+    sc = g.gpu()
+    pos = torch.from_numpy(t).cuda()
+    nrm = torch.from_numpy(np.tile(np.float32([0, 0, 1]), (n, 3))).contiguous().cuda()
+    tb = torch.from_numpy(np.ascontiguousarray(g.bvh(1)["tris"][:, 24:30])).cuda()
+    torch.cuda.synchronize()
+    rc = g.rtx.rtx_scene_update_mesh(sc, 0, C.c_void_p(pos.data_ptr()), C.c_void_p(nrm.data_ptr()), C.c_void_p(tb.data_ptr()), lo.ctypes.data, hi.ctypes.data, 1, None)
+    assert rc == 0, g.rtx.rtx_last_error()
+    assert same_tree(g.device_mesh(0), tree) is None
+    cam, rot = g.camera_pose()
+    there = (cam + np.float32([0.125, 0.0625, 0]), rot + np.float32([0, 5, 0]))
+    for s in (g, f):
+        s.set_camera(*there)
+    got, want = g.device_prune_copies(0), f.device_prune_copies(0)
+    assert got.shape == want.shape and got.shape[0] >= 2, "%s: %r copies of the prune blocks, the created scene's %r" % (name, got.shape, want.shape)
+    for c in range(got.shape[0]):
+        assert np.array_equal(bits(got[c]), bits(want[c])), "%s: copy %d of the prune blocks differs from the created scene's" % (name, c)
+    for a, b, part in zip(g.cost_grid(), f.cost_grid(), ("references", "leaves")):
+        assert a.shape == b.shape and np.array_equal(a, b), "%s: the cost estimate's %s differ from the created scene's" % (name, part)
+    assert g.cost_grid()[1].sum() > 0
+    g.close(); f.close()
