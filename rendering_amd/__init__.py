@@ -68,6 +68,10 @@ RTX_LIGHT_SYMBOLS = ["rtx_light_rays"]
 # (not part of the drop-in boundary)
 RTX_SCATTER_SYMBOLS = ["rtx_scatter_rays", "rtx_sky_rays"]
 
+# the extension of include/rtx_points.h: direct light and ambient occlusion at caller-supplied surface points (not part of the drop-in
+# boundary)
+RTX_POINTS_SYMBOLS = ["rtx_light_points", "rtx_ao_points"]
+
 # the extension of include/rtx_deform.h: deforming a mesh of a live scene from vertices on the device (not part of the drop-in boundary)
 RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
 
@@ -205,6 +209,9 @@ def load():
     if hasattr(rtx, "rtx_scatter_rays"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_scatter_rays.argtypes = [vp, u32, vp, C.POINTER(ScatterBuffers), vp]
         rtx.rtx_sky_rays.argtypes = [vp, u32, vp, vp, vp]
+    if hasattr(rtx, "rtx_light_points"):      # (a library without them is reported by exported_symbols)
+        rtx.rtx_light_points.argtypes = [vp, u32, vp, vp, C.POINTER(LightBuffers), vp]
+        rtx.rtx_ao_points.argtypes = [vp, u32, vp, C.POINTER(AoParams), vp, vp, vp]
     if hasattr(rtx, "rtx_render_views"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_render_views.argtypes = [vp, u32, C.POINTER(ViewTarget), i32, vp]
         rtx.rtx_views_plan_probe.argtypes = [u32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -302,7 +309,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -1085,6 +1092,75 @@ class Scene:
         if n and any(p is not None for p in ptrs):
             bufs = LightBuffers(nl, *ptrs)
             _check(self.rtx.rtx_light_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_light_rays")
+        return out
+
+    @staticmethod
+    def _check_points(who, points, device):
+        """The points of the wrapper `who`: a contiguous float32 tensor (n, 6) = {P xyz, N xyz} on cuda:`device`.  Returns n."""
+        import torch
+        _check_tensor(who, "points", points, torch.float32, ("n", 6), device)
+        if points.shape[0] > 0xFFFFFFC0:
+            raise ValueError("%s: at most %d points per call, got %d" % (who, 0xFFFFFFC0, points.shape[0]))
+        return points.shape[0]
+
+    def light_points(self, points, view=None, diffuse=True, specular=None, per_light=False, stream=None):
+        """rtx_light_points: the direct light at surface points the caller already has, on the device -- castRay's sums over the lights with
+        their shadow rays at a hit at P with the shading normal N, bit for bit (include/rtx_points.h).  points: contiguous float32 torch
+        tensor (n, 6) = {P xyz, N xyz} on this scene's device; N is used as stored.  view: None, or a float32 tensor (n, 4) = {V xyz, ns}
+        on that device -- V the direction of the ray that arrived at P, ns the specular exponent.  specular: None means "iff view is
+        given"; True without a view is refused.  Returns a dict of new tensors on the points' device, as light_rays does: "diffuse" (n, 3)
+        and "specular" (n, 3), float32; with per_light also "light_diffuse" (n, L, 3), "light_specular" (n, L, 3) when specular is on, and
+        "light_open" (n, L), int32, how many of the light's shadow rays arrive.  The sums are 0 on a scene without lights (L = 0).
+        Asynchronous on `stream`, which is handled as in trace_rays (the view is recorded on it like the points)."""
+        import torch
+        if specular is None:
+            specular = view is not None
+        if specular and view is None:
+            raise ValueError("light_points: specular needs a view")
+        if not (diffuse or specular or per_light):
+            raise ValueError("light_points: nothing to compute (every channel is off)")
+        n = self._check_points("light_points", points, self.device)
+        if view is not None:
+            _check_tensor("light_points", "view", view, torch.float32, (n, 4), self.device)
+        nl = self.n_lights if per_light else 0
+        asked = [(name, shape, dtype) for name, on, shape, dtype in (
+            ("diffuse", diffuse, (3,), torch.float32), ("specular", specular, (3,), torch.float32),
+            ("light_diffuse", per_light, (nl, 3), torch.float32), ("light_specular", per_light and specular, (nl, 3), torch.float32),
+            ("light_open", per_light, (nl,), torch.int32)) if on]
+        alloc_on, st = _query_stream(stream, points.device, (points, view))
+        with torch.cuda.stream(alloc_on):
+            out = {name: torch.empty((n,) + shape, dtype=dtype, device=points.device) for name, shape, dtype in asked}
+        # (a scene without lights: the per-light tensors are empty, and the library takes no pointer for them)
+        ptrs = [out[name].data_ptr() if name in out and out[name].numel() else None
+                for name in ("diffuse", "specular", "light_diffuse", "light_specular", "light_open")]
+        if n and any(p is not None for p in ptrs):
+            bufs = LightBuffers(nl, None, *ptrs)
+            _check(self.rtx.rtx_light_points(self.gpu(), n, _ptr(points), _ptr(view), C.byref(bufs), st), "rtx_light_points")
+        return out
+
+    def ao_points(self, points, dirs, radius=float("inf"), ao=True, counts=False, stream=None):
+        """rtx_ao_points: ambient occlusion at surface points the caller already has, on the device (include/rtx_points.h).  points: as
+        for light_points.  For every point, each direction of `dirs` (float32 (K, 3), K in 1 .. 256, world space, used as stored) with
+        N . d > 0 is traced from P + N * bias with the rule of occluded() and the range `radius` (> 0; inf: the whole ray; the library
+        refuses anything else, and K outside 1 .. 256).  Returns a dict of the channels asked for, new tensors (n,) on the points' device:
+        "ao", float32, open / traced, 1.0 where nothing was traced; "counts", int32, open | traced << 16.  Asynchronous on `stream`,
+        which is handled as in trace_rays (dirs is recorded on it like the points)."""
+        import torch
+        if not (ao or counts):
+            raise ValueError("ao_points: nothing to compute (ao and counts are both off)")
+        n = self._check_points("ao_points", points, self.device)
+        _check_tensor("ao_points", "dirs", dirs, torch.float32, ("K", 3), self.device)
+        alloc_on, st = _query_stream(stream, points.device, (points, dirs))
+        with torch.cuda.stream(alloc_on):
+            out = {}
+            if ao:
+                out["ao"] = torch.empty((n,), dtype=torch.float32, device=points.device)
+            if counts:
+                out["counts"] = torch.empty((n,), dtype=torch.int32, device=points.device)
+        if n:
+            par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
+            _check(self.rtx.rtx_ao_points(self.gpu(), n, _ptr(points), C.byref(par), _ptr(out.get("ao")), _ptr(out.get("counts")), st),
+                   "rtx_ao_points")
         return out
 
     SCATTER_CHANNELS = ("hits", "local", "reflect", "refract", "weight", "kinds")

@@ -24,6 +24,7 @@
 #include "../../include/rtx_surface.h"
 #include "../../include/rtx_light.h"
 #include "../../include/rtx_scatter.h"
+#include "../../include/rtx_points.h"
 #include "../../include/rtx_views.h"
 #include "rtx_device.h"
 #include "rtx_frame_plan.h"
@@ -42,6 +43,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_surface.hip"
 #include "rtx_light.hip"
 #include "rtx_scatter.hip"
+#include "rtx_points.hip"
 #undef RTX_QUERY_INSTANCES
 #undef RTX_MESH_INSTANCES
 
@@ -211,6 +213,8 @@ struct rtx_scene {
 	int raySurfaceBlocks[2] = { 0, 0 };                        // rtx_surface_rays' kernel
 	int rayLightBlocks[2] = { 0, 0 };                          // rtx_light_rays' kernel
 	int rayScatterBlocks[2] = { 0, 0 };                        // rtx_scatter_rays' kernel
+	int pointLightBlocks[2] = { 0, 0 };                        // rtx_light_points' kernel
+	int pointAoBlocks[2] = { 0, 0 };                           // rtx_ao_points' kernel
 	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
 	// rtx_render_views (rtx_views.hip): the view table of a batch (records, then the first item of every view) on the device and in the pinned
 	// buffer it is copied from -- viewsStaged: that copy, which the next call waits for before it fills the buffer again --, the heads, and
@@ -386,6 +390,19 @@ RayScatterKernel rayScatterKernel(const Variant& v)
 {
 	if (v.analytic) return rtxRayScatterKernel<false, true, -1>;
 	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayScatterKernel { return rtxRayScatterKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+// (the kernels of include/rtx_points.h: rtx_points.hip)
+typedef void (*PointLightKernel)(const Params, const uint32_t*, const float*, const rtx_light_buffers);
+PointLightKernel pointLightKernel(const Variant& v)
+{
+	if (v.analytic) return rtxPointLightKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> PointLightKernel { return rtxPointLightKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+typedef void (*PointAoKernel)(const Params, const uint32_t*, const AoArgs);
+PointAoKernel pointAoKernel(const Variant& v)
+{
+	if (v.analytic) return rtxPointAoKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> PointAoKernel { return rtxPointAoKernel<true, decltype(b)::value, decltype(c)::value>; });
 }
 RayKernel rayColourKernel(const Variant& v)
 {
@@ -1504,6 +1521,8 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 		s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
 		s->rayLightBlocks[0] = s->rayLightBlocks[1] = 0;
 		s->rayScatterBlocks[0] = s->rayScatterBlocks[1] = 0;
+		s->pointLightBlocks[0] = s->pointLightBlocks[1] = 0;
+		s->pointAoBlocks[0] = s->pointAoBlocks[1] = 0;
 		for (auto& b : s->rayOccludedBlocks) b[0] = b[1] = 0;
 	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
@@ -2064,6 +2083,8 @@ constexpr uint32_t kSurfaceReorderMin = kTraceReorderMin;
 constexpr uint32_t kLightReorderMin = kTraceReorderMin;
 // ... and rtx_scatter_rays': the same first half, and the same light loop for the hits that read the lights
 constexpr uint32_t kScatterReorderMin = kTraceReorderMin;
+// ... and rtx_light_points' and rtx_ao_points': the same grouping with {P, N} in the place of origin and direction
+constexpr uint32_t kPointsReorderMin = kTraceReorderMin;
 
 // The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
 // for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
@@ -2236,6 +2257,49 @@ int rtx_scatter_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_
 	if (!scatter) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
 	else rc = launchRays(s, rayScatterKernel(v), s->rayScatterBlocks[v.cull ? 1 : 0], c, *out);
 	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+// include/rtx_points.h: the batch is {P, N} in the layout of a ray buffer, so startRays' checks and grouping are the rays'
+int rtx_light_points(rtx_scene* s, uint32_t n, const float* points_dev, const float* view_dev, const rtx_light_buffers* out, void* stream)
+{
+	RoctxRange range("Light points (rtx_light_points)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	if (out->hits_dev) return fail(RTX_ERR_ARG, "rtx_light_points: hits_dev must be NULL (a point has no hit record)");
+	const bool perLight = out->light_diffuse_dev || out->light_specular_dev || out->light_open_dev;
+	if (!out->diffuse_dev && !out->specular_dev && !perLight) return fail(RTX_ERR_ARG, "rtx_light_points: no output (all five buffers are NULL)");
+	if (!view_dev && (out->specular_dev || out->light_specular_dev)) return fail(RTX_ERR_ARG, "rtx_light_points: a specular buffer without view_dev");
+	// (a per-light buffer sized before rtx_scene_set_lights would be written past its end, or with another stride)
+	if (perLight && out->n_lights != s->params.nLights) return fail(RTX_ERR_ARG, "rtx_light_points: n_lights is not the scene's number of lights");
+	if (perLight && s->params.nLights == 0) return fail(RTX_ERR_ARG, "rtx_light_points: per-light buffers on a scene without lights");
+	if (n != 0 && !points_dev) return fail(RTX_ERR_ARG, "rtx_light_points: points is NULL");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, points_dev, kPointsReorderMin, stream, c, rc)) return rc;
+	const Variant v = variantOf(s);
+	c.p.workCounter = s->rayWork;
+	if ((rc = launchRays(s, pointLightKernel(v), s->pointLightBlocks[v.cull ? 1 : 0], c, view_dev, *out))) return rc;
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_ao_points(rtx_scene* s, uint32_t n, const float* points_dev, const rtx_ao_params* par, float* ao, uint32_t* counts, void* stream)
+{
+	RoctxRange range("Ambient occlusion at points (rtx_ao_points)");
+	if (!s || !par) return fail(RTX_ERR_ARG, "scene/params is NULL");
+	if (!ao && !counts) return fail(RTX_ERR_ARG, "rtx_ao_points: no output (both buffers are NULL)");
+	if (!par->dirs_dev) return fail(RTX_ERR_ARG, "rtx_ao_points: dirs_dev is NULL");
+	if (par->n_dirs < 1 || par->n_dirs > 256) return fail(RTX_ERR_ARG, "rtx_ao_points: n_dirs must be 1 .. 256");
+	if (!(par->radius > 0)) return fail(RTX_ERR_ARG, "rtx_ao_points: radius must be > 0 (+inf: the whole ray)");
+	if (n != 0 && !points_dev) return fail(RTX_ERR_ARG, "rtx_ao_points: points is NULL");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, points_dev, kPointsReorderMin, stream, c, rc)) return rc;
+	const Variant v = variantOf(s);
+	c.p.workCounter = s->rayWork;
+	const AoArgs args = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
+	if ((rc = launchRays(s, pointAoKernel(v), s->pointAoBlocks[v.cull ? 1 : 0], c, args))) return rc;
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

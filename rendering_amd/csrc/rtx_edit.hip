@@ -255,6 +255,8 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 	s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;
 	s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
 	s->rayLightBlocks[0] = s->rayLightBlocks[1] = 0;
+	s->pointLightBlocks[0] = s->pointLightBlocks[1] = 0;
+	s->pointAoBlocks[0] = s->pointAoBlocks[1] = 0;
 	memset(s->rayOccludedBlocks, 0, sizeof(s->rayOccludedBlocks));
 
 	// 5. the view's preparation again: every source copy is built again, every tile list and frame-mode measurement forgotten
