@@ -72,6 +72,9 @@ RTX_SCATTER_SYMBOLS = ["rtx_scatter_rays", "rtx_sky_rays"]
 # boundary)
 RTX_POINTS_SYMBOLS = ["rtx_light_points", "rtx_ao_points"]
 
+# the extension of include/rtx_render_light.h: direct light of a frame (not part of the drop-in boundary)
+RTX_RENDER_LIGHT_SYMBOLS = ["rtx_render_light"]
+
 # the extension of include/rtx_deform.h: deforming a mesh of a live scene from vertices on the device (not part of the drop-in boundary)
 RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
 
@@ -104,6 +107,12 @@ class SurfaceBuffers(C.Structure):
 class LightBuffers(C.Structure):
     """rtx_light_buffers (include/rtx_light.h): the scene's number of lights and six device pointers, any of them NULL."""
     _fields_ = [("n_lights", C.c_uint32)] + [(n, C.c_void_p) for n in ("hits_dev", "diffuse_dev", "specular_dev", "light_diffuse_dev",
+                                                                       "light_specular_dev", "light_open_dev")]
+
+
+class FrameLightBuffers(C.Structure):
+    """rtx_frame_light_buffers (include/rtx_render_light.h): the scene's number of lights and five device pointers, any of them NULL."""
+    _fields_ = [("n_lights", C.c_uint32)] + [(n, C.c_void_p) for n in ("diffuse_dev", "specular_dev", "light_diffuse_dev",
                                                                        "light_specular_dev", "light_open_dev")]
 
 
@@ -212,6 +221,8 @@ def load():
     if hasattr(rtx, "rtx_light_points"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_light_points.argtypes = [vp, u32, vp, vp, C.POINTER(LightBuffers), vp]
         rtx.rtx_ao_points.argtypes = [vp, u32, vp, C.POINTER(AoParams), vp, vp, vp]
+    if hasattr(rtx, "rtx_render_light"):      # (a library without it is reported by exported_symbols)
+        rtx.rtx_render_light.argtypes = [vp, u32, u32, C.POINTER(FrameLightBuffers), vp]
     if hasattr(rtx, "rtx_render_views"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_render_views.argtypes = [vp, u32, C.POINTER(ViewTarget), i32, vp]
         rtx.rtx_views_plan_probe.argtypes = [u32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -309,7 +320,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -1400,6 +1411,32 @@ class Scene:
         _, st = _query_stream(stream, self.device, (dirs, ao, counts))
         par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
         _check(self.rtx.rtx_render_ao(self.gpu(), r0, r1, C.byref(par), _ptr(ao), _ptr(counts), st), "rtx_render_ao")
+
+    def render_light(self, diffuse=None, specular=None, light_diffuse=None, light_specular=None, light_open=None, rows=None, stream=None):
+        """rtx_render_light: the direct light of the frame in one launch -- for every pixel of pass 1 castRay's sums over the lights with
+        their shadow rays at the first hit of its primary ray, the bits of light_rays for that ray (include/rtx_render_light.h) -- written
+        into the device tensors that are given (any subset, at least one): diffuse and specular float32 (H, W, 3), the sums a Diffuse
+        hit's colour (albedo * diffuse) and a Phong hit's ((albedo * ambient + diffuse * kd) + specular * ks) are made of; light_diffuse
+        and light_specular float32 (L, H, W, 3), what each of the scene's L lights adds to them, one image per light; light_open int32
+        (L, H, W), how many of the light's shadow rays arrive (0 / 1; up to its number of samples for an area light).  Contiguous, on
+        this scene's device.  Written: the pixels x < W-1, y < H-1 of rows [r0, r1) that this part owns; nothing else of a tensor is
+        touched.  A miss: zeros.  Asynchronous on `stream` (None: torch's current stream of the scene's device); with a
+        torch.cuda.Stream the tensors are recorded on it."""
+        import torch
+        hw, nl = (self.height, self.width), self.n_lights
+        given = (("diffuse", diffuse, torch.float32, hw + (3,)), ("specular", specular, torch.float32, hw + (3,)),
+                 ("light_diffuse", light_diffuse, torch.float32, (nl,) + hw + (3,)), ("light_specular", light_specular, torch.float32, (nl,) + hw + (3,)),
+                 ("light_open", light_open, torch.int32, (nl,) + hw))
+        if all(t is None for _, t, _, _ in given):
+            raise ValueError("render_light: nothing to compute (at least one buffer is needed)")
+        for name, t, dtype, shape in given:
+            if t is not None:
+                _check_tensor("render_light", name, t, dtype, shape, self.device)
+        r0, r1 = rows if rows is not None else (0, self.height)
+        _, st = _query_stream(stream, self.device, [t for _, t, _, _ in given])
+        # (a scene without lights: the per-light tensors are empty, and the library takes no pointer for them)
+        bufs = FrameLightBuffers(nl, *[t.data_ptr() if t is not None and t.numel() else None for _, t, _, _ in given])
+        _check(self.rtx.rtx_render_light(self.gpu(), r0, r1, C.byref(bufs), st), "rtx_render_light")
 
     def device_mesh(self, mesh):
         """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,

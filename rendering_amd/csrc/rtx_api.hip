@@ -25,6 +25,7 @@
 #include "../../include/rtx_light.h"
 #include "../../include/rtx_scatter.h"
 #include "../../include/rtx_points.h"
+#include "../../include/rtx_render_light.h"
 #include "../../include/rtx_views.h"
 #include "rtx_device.h"
 #include "rtx_frame_plan.h"
@@ -44,6 +45,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_light.hip"
 #include "rtx_scatter.hip"
 #include "rtx_points.hip"
+#include "rtx_render_light.hip"
 #undef RTX_QUERY_INSTANCES
 #undef RTX_MESH_INSTANCES
 
@@ -433,6 +435,12 @@ AoKernel aoKernel(const Variant& v)
 {
 	if (v.analytic) return rtxAoKernel<false, true, -1>;
 	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> AoKernel { return rtxAoKernel<true, decltype(b)::value, decltype(c)::value>; });
+}
+typedef void (*LightFrameKernel)(const Params, const rtx_frame_light_buffers);
+LightFrameKernel lightFrameKernel(const Variant& v)
+{
+	if (v.analytic) return rtxLightFrameKernel<false, true, -1>;
+	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> LightFrameKernel { return rtxLightFrameKernel<true, decltype(b)::value, decltype(c)::value>; });
 }
 // (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
 typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
@@ -2363,6 +2371,28 @@ int rtx_render_ao(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_ao
 	if (int ro = renderOn(s, st)) return ro;
 	const AoArgs a = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
 	hipLaunchKernelGGL(aoKernel(variantOf(s)), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, a);
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
+}
+
+int rtx_render_light(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_frame_light_buffers* out, void* stream)
+{
+	RoctxRange range("Direct light (rtx_render_light)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	const bool perLight = out->light_diffuse_dev || out->light_specular_dev || out->light_open_dev;
+	if (!out->diffuse_dev && !out->specular_dev && !perLight) return fail(RTX_ERR_ARG, "rtx_render_light: no output (all five buffers are NULL)");
+	// (a per-light buffer sized before rtx_scene_set_lights would be written past its end)
+	if (perLight && out->n_lights != s->params.nLights) return fail(RTX_ERR_ARG, "rtx_render_light: n_lights is not the scene's number of lights");
+	if (perLight && s->params.nLights == 0) return fail(RTX_ERR_ARG, "rtx_render_light: per-light buffers on a scene without lights");
+	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_light collects no statistics (rtx_counters_enable)");
+	// (the plain grid of rtx_render_aov; no event is recorded)
+	Params p = s->params;
+	int rc;
+	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
+	HIPCHK(hipSetDevice(s->device));
+	hipStream_t st = (hipStream_t)stream;
+	if (int ro = renderOn(s, st)) return ro;
+	hipLaunchKernelGGL(lightFrameKernel(variantOf(s)), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, *out);
 	HIPCHK(hipGetLastError());
 	return RTX_OK;
 }

@@ -8,9 +8,15 @@
 //   wantOpen        wave-uniform: every (ray, light) pair is walked
 //   h               a Hit the shadow walks may overwrite
 //   RTX_LIGHT_LOOP_PER_LIGHT   statements that run once per light after its samples, with li, nLights, D, S and nOpen in scope
+//   RTX_LIGHT_LOOP_PARK / RTX_LIGHT_LOOP_UNPARK   optional: statements right before and after the mesh walk of a shadow bundle, for a kernel
+//                   that keeps values the walk does not read somewhere else meanwhile (rtx_render_light.hip); absent, they are nothing
 // -- and it leaves the sums in diff and spec, which it declares.
 // It is text and not a __forceinline__ function because rtxRayLightKernel has to stay the machine code it was: as a function taking a
 // callback, all five instances of that kernel came out with another register allocation.
+#ifndef RTX_LIGHT_LOOP_PARK
+#define RTX_LIGHT_LOOP_PARK
+#define RTX_LIGHT_LOOP_UNPARK
+#endif
 		const V3 O = p + n * P.view.bias;                    // castRay's shadow-ray origin (scene.cpp:787)
 		V3 diff = mk(0, 0, 0), spec = mk(0, 0, 0);
 		const uint32_t nLights = uni(P.nLights);
@@ -70,7 +76,9 @@
 							// (a light's source copy was derived for shadow-ray origins within srcNmax |bias| of the surface: a longer shading normal,
 							// or NaN, falls back to copy 0 -- advance() in rtx_kernels.hip)
 							const uint32_t src = (lt == 2 && li < P.nSrcLights && len2(n) <= P.srcNmax2) ? 2u + li : 0u;
+							RTX_LIGHT_LOOP_PARK
 							traceWave<false, true, false, BOXES, CULLK, 2>(P, open, true, O, nL, tmWalk, h, cnt, src);
+							RTX_LIGHT_LOOP_UNPARK
 							open = open && h.obj < 0;
 						}
 					}
@@ -98,3 +106,5 @@
 			RTX_LIGHT_LOOP_PER_LIGHT
 		}
 #undef RTX_LIGHT_LOOP_PER_LIGHT
+#undef RTX_LIGHT_LOOP_PARK
+#undef RTX_LIGHT_LOOP_UNPARK
