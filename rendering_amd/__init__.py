@@ -374,12 +374,13 @@ def _check_tensor(who, name, t, dtype, shape, device=None):
         raise ValueError("%s: %s must be on cuda:%d, the scene's device, got %s" % (who, name, device, t.device))
 
 
-def _check_rays(who, rays, device):
-    """The rays of the wrapper `who`: a contiguous float32 tensor (n, 6) on cuda:`device` of at most 0xFFFFFFC0 rays.  Returns n."""
+def _check_rays(who, rays, device, noun="rays"):
+    """The rays of the wrapper `who`: a contiguous float32 tensor (n, 6) on cuda:`device` of at most 0xFFFFFFC0 rays.  Returns n.
+    noun "points": the batch is {P xyz, N xyz} in the same layout (light_points, ao_points)."""
     import torch
-    _check_tensor(who, "rays", rays, torch.float32, ("n", 6), device)
+    _check_tensor(who, noun, rays, torch.float32, ("n", 6), device)
     if rays.shape[0] > 0xFFFFFFC0:
-        raise ValueError("%s: at most %d rays per call, got %d" % (who, 0xFFFFFFC0, rays.shape[0]))
+        raise ValueError("%s: at most %d %s per call, got %d" % (who, 0xFFFFFFC0, noun, rays.shape[0]))
     return rays.shape[0]
 
 
@@ -395,6 +396,33 @@ def _query_stream(stream, device, inputs):
             if t is not None:
                 t.record_stream(alloc_on)
     return alloc_on, C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if stream is None else Scene._stream_ptr(stream)
+
+
+def _query_outputs(channels, n, device, alloc_on):
+    """The outputs of a query over n rays or points from its channel table, rows (name, on, tail shape, dtype): a dict of the channels
+    that are on, new tensors (n,) + tail on `device` allocated on the query stream (_query_stream's alloc_on), and the pointers of all
+    channels in the table's order -- None for a channel that is off or empty (a per-light channel of a scene without lights has no
+    pointer for the library)."""
+    import torch
+    with torch.cuda.stream(alloc_on):
+        out = {name: torch.empty((n,) + tail, dtype=dtype, device=device) for name, on, tail, dtype in channels if on}
+    return out, [out[name].data_ptr() if name in out and out[name].numel() else None for name, _, _, _ in channels]
+
+
+def _frame_tensors(who, outputs, device, stream, inputs=()):
+    """The tensors of the frame call `who`, rows (name, tensor, dtype, shape): `outputs`, of which the caller gives any subset but at
+    least one, and `inputs`, which are all required.  Each is checked (_check_tensor, the inputs first) and, with a torch.cuda.Stream,
+    recorded on it.  Returns (the stream's pointer, the outputs' pointers in order: None for one that is not given or is empty -- a
+    per-light tensor of a scene without lights has no pointer for the library)."""
+    if all(t is None for _, t, _, _ in outputs):
+        raise ValueError("%s: nothing to compute (at least one buffer is needed)" % who)
+    for name, t, dtype, shape in inputs:
+        _check_tensor(who, name, t, dtype, shape, device)
+    for name, t, dtype, shape in outputs:
+        if t is not None:
+            _check_tensor(who, name, t, dtype, shape, device)
+    _, st = _query_stream(stream, device, [t for _, t, _, _ in tuple(inputs) + tuple(outputs)])
+    return st, [t.data_ptr() if t is not None and t.numel() else None for _, t, _, _ in outputs]
 
 
 def set_ac_build(mode, device=0):
@@ -1063,17 +1091,16 @@ class Scene:
         position, normal and specular are 0 at a miss.  The object's other constants are in device_objects(), indexed by hits[:, 1].
         Asynchronous on `stream`, which is handled as in trace_rays."""
         import torch
-        asked = [(name, shape) for name, on, shape in (("hits", hits, (8,)), ("position", position, (3,)), ("normal", normal, (3,)),
-                                                       ("albedo", albedo, (3,)), ("specular", specular, ())) if on]
-        if not asked:
+        f32 = torch.float32
+        channels = (("hits", hits, (8,), f32), ("position", position, (3,), f32), ("normal", normal, (3,), f32),
+                    ("albedo", albedo, (3,), f32), ("specular", specular, (), f32))
+        if not any(on for _, on, _, _ in channels):
             raise ValueError("surface_rays: nothing to compute (every channel is off)")
         n = _check_rays("surface_rays", rays, self.device)
         alloc_on, st = _query_stream(stream, rays.device, (rays,))
-        with torch.cuda.stream(alloc_on):
-            out = {name: torch.empty((n,) + shape, dtype=torch.float32, device=rays.device) for name, shape in asked}
+        out, ptrs = _query_outputs(channels, n, rays.device, alloc_on)
         if n:
-            bufs = SurfaceBuffers(*[out[name].data_ptr() if name in out else None for name in ("hits", "position", "normal", "albedo", "specular")])
-            _check(self.rtx.rtx_surface_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_surface_rays")
+            _check(self.rtx.rtx_surface_rays(self.gpu(), n, _ptr(rays), C.byref(SurfaceBuffers(*ptrs)), st), "rtx_surface_rays")
         return out
 
     def light_rays(self, rays, diffuse=True, specular=True, hits=False, per_light=False, stream=None):
@@ -1090,29 +1117,14 @@ class Scene:
             raise ValueError("light_rays: nothing to compute (every channel is off)")
         n = _check_rays("light_rays", rays, self.device)
         nl = self.n_lights if per_light else 0
-        asked = [(name, shape, dtype) for name, on, shape, dtype in (
-            ("hits", hits, (8,), torch.float32), ("diffuse", diffuse, (3,), torch.float32), ("specular", specular, (3,), torch.float32),
-            ("light_diffuse", per_light, (nl, 3), torch.float32), ("light_specular", per_light, (nl, 3), torch.float32),
-            ("light_open", per_light, (nl,), torch.int32)) if on]
+        channels = (("hits", hits, (8,), torch.float32), ("diffuse", diffuse, (3,), torch.float32), ("specular", specular, (3,), torch.float32),
+                    ("light_diffuse", per_light, (nl, 3), torch.float32), ("light_specular", per_light, (nl, 3), torch.float32),
+                    ("light_open", per_light, (nl,), torch.int32))
         alloc_on, st = _query_stream(stream, rays.device, (rays,))
-        with torch.cuda.stream(alloc_on):
-            out = {name: torch.empty((n,) + shape, dtype=dtype, device=rays.device) for name, shape, dtype in asked}
-        # (a scene without lights: the per-light tensors are empty, and the library takes no pointer for them)
-        ptrs = [out[name].data_ptr() if name in out and out[name].numel() else None
-                for name in ("hits", "diffuse", "specular", "light_diffuse", "light_specular", "light_open")]
+        out, ptrs = _query_outputs(channels, n, rays.device, alloc_on)
         if n and any(p is not None for p in ptrs):
-            bufs = LightBuffers(nl, *ptrs)
-            _check(self.rtx.rtx_light_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_light_rays")
+            _check(self.rtx.rtx_light_rays(self.gpu(), n, _ptr(rays), C.byref(LightBuffers(nl, *ptrs)), st), "rtx_light_rays")
         return out
-
-    @staticmethod
-    def _check_points(who, points, device):
-        """The points of the wrapper `who`: a contiguous float32 tensor (n, 6) = {P xyz, N xyz} on cuda:`device`.  Returns n."""
-        import torch
-        _check_tensor(who, "points", points, torch.float32, ("n", 6), device)
-        if points.shape[0] > 0xFFFFFFC0:
-            raise ValueError("%s: at most %d points per call, got %d" % (who, 0xFFFFFFC0, points.shape[0]))
-        return points.shape[0]
 
     def light_points(self, points, view=None, diffuse=True, specular=None, per_light=False, stream=None):
         """rtx_light_points: the direct light at surface points the caller already has, on the device -- castRay's sums over the lights with
@@ -1130,23 +1142,17 @@ class Scene:
             raise ValueError("light_points: specular needs a view")
         if not (diffuse or specular or per_light):
             raise ValueError("light_points: nothing to compute (every channel is off)")
-        n = self._check_points("light_points", points, self.device)
+        n = _check_rays("light_points", points, self.device, "points")
         if view is not None:
             _check_tensor("light_points", "view", view, torch.float32, (n, 4), self.device)
         nl = self.n_lights if per_light else 0
-        asked = [(name, shape, dtype) for name, on, shape, dtype in (
-            ("diffuse", diffuse, (3,), torch.float32), ("specular", specular, (3,), torch.float32),
-            ("light_diffuse", per_light, (nl, 3), torch.float32), ("light_specular", per_light and specular, (nl, 3), torch.float32),
-            ("light_open", per_light, (nl,), torch.int32)) if on]
+        channels = (("diffuse", diffuse, (3,), torch.float32), ("specular", specular, (3,), torch.float32),
+                    ("light_diffuse", per_light, (nl, 3), torch.float32), ("light_specular", per_light and specular, (nl, 3), torch.float32),
+                    ("light_open", per_light, (nl,), torch.int32))
         alloc_on, st = _query_stream(stream, points.device, (points, view))
-        with torch.cuda.stream(alloc_on):
-            out = {name: torch.empty((n,) + shape, dtype=dtype, device=points.device) for name, shape, dtype in asked}
-        # (a scene without lights: the per-light tensors are empty, and the library takes no pointer for them)
-        ptrs = [out[name].data_ptr() if name in out and out[name].numel() else None
-                for name in ("diffuse", "specular", "light_diffuse", "light_specular", "light_open")]
+        out, ptrs = _query_outputs(channels, n, points.device, alloc_on)
         if n and any(p is not None for p in ptrs):
-            bufs = LightBuffers(nl, None, *ptrs)
-            _check(self.rtx.rtx_light_points(self.gpu(), n, _ptr(points), _ptr(view), C.byref(bufs), st), "rtx_light_points")
+            _check(self.rtx.rtx_light_points(self.gpu(), n, _ptr(points), _ptr(view), C.byref(LightBuffers(nl, None, *ptrs)), st), "rtx_light_points")
         return out
 
     def ao_points(self, points, dirs, radius=float("inf"), ao=True, counts=False, stream=None):
@@ -1159,19 +1165,13 @@ class Scene:
         import torch
         if not (ao or counts):
             raise ValueError("ao_points: nothing to compute (ao and counts are both off)")
-        n = self._check_points("ao_points", points, self.device)
+        n = _check_rays("ao_points", points, self.device, "points")
         _check_tensor("ao_points", "dirs", dirs, torch.float32, ("K", 3), self.device)
         alloc_on, st = _query_stream(stream, points.device, (points, dirs))
-        with torch.cuda.stream(alloc_on):
-            out = {}
-            if ao:
-                out["ao"] = torch.empty((n,), dtype=torch.float32, device=points.device)
-            if counts:
-                out["counts"] = torch.empty((n,), dtype=torch.int32, device=points.device)
+        out, ptrs = _query_outputs((("ao", ao, (), torch.float32), ("counts", counts, (), torch.int32)), n, points.device, alloc_on)
         if n:
             par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
-            _check(self.rtx.rtx_ao_points(self.gpu(), n, _ptr(points), C.byref(par), _ptr(out.get("ao")), _ptr(out.get("counts")), st),
-                   "rtx_ao_points")
+            _check(self.rtx.rtx_ao_points(self.gpu(), n, _ptr(points), C.byref(par), ptrs[0], ptrs[1], st), "rtx_ao_points")
         return out
 
     SCATTER_CHANNELS = ("hits", "local", "reflect", "refract", "weight", "kinds")
@@ -1187,18 +1187,15 @@ class Scene:
         weight[0]) + local at glass (the refraction term only where bit 1 is set) and local itself where kinds is 0: cast_tree.
         Asynchronous on `stream`, which is handled as in trace_rays."""
         import torch
-        asked = [(name, shape, dtype) for name, on, shape, dtype in (
-            ("hits", hits, (8,), torch.float32), ("local", local, (3,), torch.float32), ("reflect", reflect, (6,), torch.float32),
-            ("refract", refract, (6,), torch.float32), ("weight", weight, (2,), torch.float32), ("kinds", kinds, (), torch.uint8)) if on]
-        if not asked:
+        channels = (("hits", hits, (8,), torch.float32), ("local", local, (3,), torch.float32), ("reflect", reflect, (6,), torch.float32),
+                    ("refract", refract, (6,), torch.float32), ("weight", weight, (2,), torch.float32), ("kinds", kinds, (), torch.uint8))
+        if not any(on for _, on, _, _ in channels):
             raise ValueError("scatter_rays: nothing to compute (every channel is off)")
         n = _check_rays("scatter_rays", rays, self.device)
         alloc_on, st = _query_stream(stream, rays.device, (rays,))
-        with torch.cuda.stream(alloc_on):
-            out = {name: torch.empty((n,) + shape, dtype=dtype, device=rays.device) for name, shape, dtype in asked}
+        out, ptrs = _query_outputs(channels, n, rays.device, alloc_on)      # (in the order of SCATTER_CHANNELS, the struct's)
         if n:
-            bufs = ScatterBuffers(*[out[name].data_ptr() if name in out else None for name in self.SCATTER_CHANNELS])
-            _check(self.rtx.rtx_scatter_rays(self.gpu(), n, _ptr(rays), C.byref(bufs), st), "rtx_scatter_rays")
+            _check(self.rtx.rtx_scatter_rays(self.gpu(), n, _ptr(rays), C.byref(ScatterBuffers(*ptrs)), st), "rtx_scatter_rays")
         return out
 
     def sky(self, rays, stream=None):
@@ -1313,17 +1310,12 @@ class Scene:
         Asynchronous on `stream` (None: torch's current stream of the scene's device); with a torch.cuda.Stream the tensors are
         recorded on it."""
         import torch
-        given = (("depth", depth, torch.float32, ()), ("object_id", object_id, torch.int32, ()), ("triangle_id", triangle_id, torch.int32, ()),
-                 ("uv", uv, torch.float32, (2,)), ("normal", normal, torch.float32, (3,)), ("albedo", albedo, torch.float32, (3,)))
-        if all(t is None for _, t, _, _ in given):
-            raise ValueError("render_aov: nothing to compute (at least one buffer is needed)")
-        for name, t, dtype, tail in given:
-            if t is not None:
-                _check_tensor("render_aov", name, t, dtype, (self.height, self.width) + tail, self.device)
+        hw = (self.height, self.width)
+        given = (("depth", depth, torch.float32, hw), ("object_id", object_id, torch.int32, hw), ("triangle_id", triangle_id, torch.int32, hw),
+                 ("uv", uv, torch.float32, hw + (2,)), ("normal", normal, torch.float32, hw + (3,)), ("albedo", albedo, torch.float32, hw + (3,)))
+        st, ptrs = _frame_tensors("render_aov", given, self.device, stream)
         r0, r1 = rows if rows is not None else (0, self.height)
-        _, st = _query_stream(stream, self.device, [t for _, t, _, _ in given])
-        bufs = AovBuffers(*[t.data_ptr() if t is not None else None for _, t, _, _ in given])
-        _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(bufs), st), "rtx_render_aov")
+        _check(self.rtx.rtx_render_aov(self.gpu(), r0, r1, C.byref(AovBuffers(*ptrs)), st), "rtx_render_aov")
 
     def view_target(self, pos, rot, fov=None, width=None, height=None):
         """The camera fields and size of one view of a batch (ViewTarget with NULL buffers; rah_view_target): what this scene's own view
@@ -1401,16 +1393,12 @@ class Scene:
         Asynchronous on `stream` (None: torch's current stream of the scene's device); with a torch.cuda.Stream the tensors are
         recorded on it."""
         import torch
-        if ao is None and counts is None:
-            raise ValueError("render_ao: nothing to compute (at least one buffer is needed)")
-        _check_tensor("render_ao", "dirs", dirs, torch.float32, ("K", 3), self.device)
-        for name, t, dtype in (("ao", ao, torch.float32), ("counts", counts, torch.int32)):
-            if t is not None:
-                _check_tensor("render_ao", name, t, dtype, (self.height, self.width), self.device)
+        hw = (self.height, self.width)
+        st, ptrs = _frame_tensors("render_ao", (("ao", ao, torch.float32, hw), ("counts", counts, torch.int32, hw)), self.device, stream,
+                                  inputs=(("dirs", dirs, torch.float32, ("K", 3)),))
         r0, r1 = rows if rows is not None else (0, self.height)
-        _, st = _query_stream(stream, self.device, (dirs, ao, counts))
         par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
-        _check(self.rtx.rtx_render_ao(self.gpu(), r0, r1, C.byref(par), _ptr(ao), _ptr(counts), st), "rtx_render_ao")
+        _check(self.rtx.rtx_render_ao(self.gpu(), r0, r1, C.byref(par), ptrs[0], ptrs[1], st), "rtx_render_ao")
 
     def render_light(self, diffuse=None, specular=None, light_diffuse=None, light_specular=None, light_open=None, rows=None, stream=None):
         """rtx_render_light: the direct light of the frame in one launch -- for every pixel of pass 1 castRay's sums over the lights with
@@ -1427,16 +1415,9 @@ class Scene:
         given = (("diffuse", diffuse, torch.float32, hw + (3,)), ("specular", specular, torch.float32, hw + (3,)),
                  ("light_diffuse", light_diffuse, torch.float32, (nl,) + hw + (3,)), ("light_specular", light_specular, torch.float32, (nl,) + hw + (3,)),
                  ("light_open", light_open, torch.int32, (nl,) + hw))
-        if all(t is None for _, t, _, _ in given):
-            raise ValueError("render_light: nothing to compute (at least one buffer is needed)")
-        for name, t, dtype, shape in given:
-            if t is not None:
-                _check_tensor("render_light", name, t, dtype, shape, self.device)
+        st, ptrs = _frame_tensors("render_light", given, self.device, stream)
         r0, r1 = rows if rows is not None else (0, self.height)
-        _, st = _query_stream(stream, self.device, [t for _, t, _, _ in given])
-        # (a scene without lights: the per-light tensors are empty, and the library takes no pointer for them)
-        bufs = FrameLightBuffers(nl, *[t.data_ptr() if t is not None and t.numel() else None for _, t, _, _ in given])
-        _check(self.rtx.rtx_render_light(self.gpu(), r0, r1, C.byref(bufs), st), "rtx_render_light")
+        _check(self.rtx.rtx_render_light(self.gpu(), r0, r1, C.byref(FrameLightBuffers(nl, *ptrs)), st), "rtx_render_light")
 
     def device_mesh(self, mesh):
         """The device's current tree of mesh `mesh` (index among the meshes) in the layout of bvh(): bounds, skip, leaf_begin, leaf_count,

@@ -11,14 +11,7 @@
 template <bool MESH, bool BOXES, int CULLK, bool SURFACE>
 __global__ void __launch_bounds__(256) rtxAovKernel(const Params P, const rtx_aov_buffers out)
 {
-	const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
-	if (wave >= P.nTiles) return;
-	const uint32_t W = P.view.width, H = P.view.height;
-	const uint32_t tx = wave % P.tilesX, ty = P.tileRow0 + wave / P.tilesX;
-	const uint32_t x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-	// pass 1's pixels of the rows this part owns (no halo rows: nothing here looks at a neighbour)
-	const bool valid = x < W - 1 && y < H - 1 && y >= P.rowBegin && y < P.rowEnd && rowOwned(P.bandH, P.nParts, P.part, y);
-	if (ballot(valid) == 0) return;
+	RTX_TILE_PIXEL()      // (x, y, valid, W)
 	V3 o, d;
 	primaryRay(P, (float)x + 0.5f, (float)y + 0.5f, o, d);
 	Hit h;

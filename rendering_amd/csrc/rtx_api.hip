@@ -48,6 +48,10 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_render_light.hip"
 #undef RTX_QUERY_INSTANCES
 #undef RTX_MESH_INSTANCES
+#undef RTX_WALK_RANGE
+#undef RTX_ANY_HIT
+#undef RTX_AO_DIRECTIONS
+#undef RTX_TILE_PIXEL
 
 // rtx_sort.hip
 hipError_t rtxSortRayKeys(void* temp, size_t* tempBytes, const uint32_t* keysIn, uint32_t* keysOut, uint32_t* order, uint32_t n, int endBit,
@@ -206,18 +210,12 @@ struct rtx_scene {
 	uint32_t framesRecovered = 0;
 	// rtx_render_ac: per-pixel counts when the caller passes none, and the frame's maximum
 	DevArray<uint32_t> acCounts, acMax;
-	// rtx_trace_rays: sort keys (in, out) and the order of up to rayCap rays, the sort's scratch, queue heads + key box (rtxRayInitKernel);
-	// blocks per CU of the hit kernel launched for culling off / on (0: not asked yet)
+	// rtx_trace_rays: sort keys (in, out) and the order of up to rayCap rays, the sort's scratch, queue heads + key box (rtxRayInitKernel)
 	DevArray<uint32_t> rayKeys, rayOrder; size_t rayCap = 0;      // (rayKeys: 2 rayCap keys, rayOrder: rayCap)
 	DevArray<char> raySortTemp;
 	DevArray<uint32_t> rayWork;
-	int rayHitBlocks[2] = { 0, 0 };
-	int raySurfaceBlocks[2] = { 0, 0 };                        // rtx_surface_rays' kernel
-	int rayLightBlocks[2] = { 0, 0 };                          // rtx_light_rays' kernel
-	int rayScatterBlocks[2] = { 0, 0 };                        // rtx_scatter_rays' kernel
-	int pointLightBlocks[2] = { 0, 0 };                        // rtx_light_points' kernel
-	int pointAoBlocks[2] = { 0, 0 };                           // rtx_ao_points' kernel
-	int rayOccludedBlocks[2][2] = { { 0, 0 }, { 0, 0 } };      // rtx_occluded_rays' kernel: [culling][scene order]
+	// blocks per CU of every ray or point kernel launched so far (blocksPerCU, rtx_query.hip): a handful of entries, keyed by the kernel itself
+	std::vector<std::pair<const void*, int>> kernelBlocksPerCU;
 	// rtx_render_views (rtx_views.hip): the view table of a batch (records, then the first item of every view) on the device and in the pinned
 	// buffer it is copied from -- viewsStaged: that copy, which the next call waits for before it fills the buffer again --, the heads, and
 	// with SSAA the view of every item and the list of flagged pixels.  They only grow.
@@ -349,8 +347,8 @@ Variant variantOf(const rtx_scene* s)
 	return { s->analytic, s->stats, s->boxPrune, (s->params.view.flags & RTX_FLAG_BACKFACE_CULL) != 0, s->plain };
 }
 
-// The kernel of each family for a variant.  (The families order their template parameters differently; the third flag of
-// dispatchVariant is PLAIN, the occlusion kernel's ORDER, or nothing at all for the hit kernel.)
+// The kernel of each frame family for a variant; the third flag of dispatchVariant is PLAIN.  (The query families, whose template
+// parameters come in another order, have their selectors in rtx_query.hip.)
 typedef void (*FrameKernel)(const Params);
 FrameKernel pass1Kernel(const Variant& v)
 {
@@ -369,113 +367,19 @@ FrameKernel frameKernel(const Variant& v)      // (rtx_render_frame has no instr
 	if (v.analytic) return rtxFrameKernel<false>;
 	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> FrameKernel { return rtxFrameKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
 }
-typedef void (*RayKernel)(const Params, const uint32_t*, float*);
-RayKernel rayHitKernel(const Variant& v)
-{
-	if (v.analytic) return rtxRayHitKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayKernel { return rtxRayHitKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-typedef void (*RaySurfaceKernel)(const Params, const uint32_t*, const rtx_surface_buffers);
-RaySurfaceKernel raySurfaceKernel(const Variant& v)
-{
-	if (v.analytic) return rtxRaySurfaceKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RaySurfaceKernel { return rtxRaySurfaceKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-typedef void (*RayLightKernel)(const Params, const uint32_t*, const rtx_light_buffers);
-RayLightKernel rayLightKernel(const Variant& v)
-{
-	if (v.analytic) return rtxRayLightKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayLightKernel { return rtxRayLightKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-typedef void (*RayScatterKernel)(const Params, const uint32_t*, const rtx_scatter_buffers);
-RayScatterKernel rayScatterKernel(const Variant& v)
-{
-	if (v.analytic) return rtxRayScatterKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> RayScatterKernel { return rtxRayScatterKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-// (the kernels of include/rtx_points.h: rtx_points.hip)
-typedef void (*PointLightKernel)(const Params, const uint32_t*, const float*, const rtx_light_buffers);
-PointLightKernel pointLightKernel(const Variant& v)
-{
-	if (v.analytic) return rtxPointLightKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> PointLightKernel { return rtxPointLightKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-typedef void (*PointAoKernel)(const Params, const uint32_t*, const AoArgs);
-PointAoKernel pointAoKernel(const Variant& v)
-{
-	if (v.analytic) return rtxPointAoKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> PointAoKernel { return rtxPointAoKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-RayKernel rayColourKernel(const Variant& v)
-{
-	if (v.analytic) return rtxRayColourKernel<false, true, -1, false>;
-	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> RayKernel { return rtxRayColourKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
-}
-// rtx_render_views' pass-1 and SSAA kernels: the instances of rtxRayColourKernel
-typedef void (*ViewsKernel)(const ViewsKernArgs);
-ViewsKernel viewsPass1Kernel(const Variant& v)
-{
-	if (v.analytic) return rtxViewsPass1Kernel<false, true, -1, false>;
-	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> ViewsKernel { return rtxViewsPass1Kernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
-}
-ViewsKernel viewsSsaaKernel(const Variant& v)
-{
-	if (v.analytic) return rtxViewsSsaaKernel<false, true, -1, false>;
-	return dispatchVariant(v.boxes, v.cull, v.plain, [](auto b, auto c, auto pl) -> ViewsKernel { return rtxViewsSsaaKernel<true, decltype(b)::value, decltype(c)::value, decltype(pl)::value>; });
-}
-// (surface: the normal or the albedo is asked for -- only then is shadePrimary part of the kernel)
-typedef void (*AovKernel)(const Params, const rtx_aov_buffers);
-AovKernel aovKernel(const Variant& v, bool surface)
-{
-	if (v.analytic) return surface ? rtxAovKernel<false, true, -1, true> : rtxAovKernel<false, true, -1, false>;
-	return dispatchVariant(v.boxes, v.cull, surface, [](auto b, auto c, auto sf) -> AovKernel { return rtxAovKernel<true, decltype(b)::value, decltype(c)::value, decltype(sf)::value>; });
-}
-typedef void (*AoKernel)(const Params, const AoArgs);
-AoKernel aoKernel(const Variant& v)
-{
-	if (v.analytic) return rtxAoKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> AoKernel { return rtxAoKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-typedef void (*LightFrameKernel)(const Params, const rtx_frame_light_buffers);
-LightFrameKernel lightFrameKernel(const Variant& v)
-{
-	if (v.analytic) return rtxLightFrameKernel<false, true, -1>;
-	return dispatchVariant(v.boxes, v.cull, false, [](auto b, auto c, auto) -> LightFrameKernel { return rtxLightFrameKernel<true, decltype(b)::value, decltype(c)::value>; });
-}
-// (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one kernel)
-typedef void (*OccludedKernel)(const Params, const uint32_t*, const float*, uint8_t*);
-OccludedKernel rayOccludedKernel(const Variant& v, bool sceneOrder)
-{
-	if (v.analytic) return rtxRayOccludedKernel<false, true, -1, true>;
-	return dispatchVariant(v.boxes, v.cull, sceneOrder, [](auto b, auto c, auto ord) -> OccludedKernel { return rtxRayOccludedKernel<true, decltype(b)::value, decltype(c)::value, decltype(ord)::value>; });
-}
 
-// Blocks of `kernel` (256 threads) a CU holds at once, asked once: perCU = 0 means not asked yet.
+// Blocks of `kernel` (256 threads) a CU holds at once, as the runtime answers.
 int askBlocksPerCU(int& perCU, const void* kernel)
 {
-	if (perCU == 0) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, 0)); perCU = std::max(perCU, 1); }
-	return RTX_OK;
-}
-
-// A batch of caller-supplied rays on its way to the kernels of rtx_rays.hip (startRays): the argument block of the launches, the rays' order,
-// the stream and the number of 64-ray groups.
-struct RayCall { Params p; const uint32_t* order; hipStream_t st; uint32_t waves; };
-
-// A launch of persistent waves for such a batch: as many blocks as the device holds of `kernel` at once (perCU: askBlocksPerCU's
-// answer for it, kept by the scene), at most one wave per group.
-template <typename... KArgs, typename... Args>
-int launchRays(rtx_scene* s, void (*kernel)(KArgs...), int& perCU, const RayCall& c, Args... args)
-{
-	if (int rc = askBlocksPerCU(perCU, (const void*)kernel)) return rc;
-	const uint32_t blocks = std::min<uint32_t>((uint32_t)(perCU * s->numCUs), (c.waves + 3) / 4);
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, c.st, c.p, c.order, args...);
+	HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, 0));
+	perCU = std::max(perCU, 1);
 	return RTX_OK;
 }
 
 // ... and of the whole device, at most `knobPerCU` per CU when that knob is set
 int residentBlocks(const rtx_scene* s, FrameKernel kernel, int knobPerCU, int* blocks)
 {
-	int b = 0;
+	int b;
 	const int rc = askBlocksPerCU(b, (const void*)kernel);
 	if (rc) return rc;
 	if (knobPerCU >= 1 && knobPerCU < b) b = knobPerCU;
@@ -1525,13 +1429,6 @@ int rtx_set_knob(rtx_scene* s, const char* name, double value)
 		// (taken by the next launch; launches already queued keep the variant they were launched with)
 		k.pruneBoxes = value < 0 ? -1 : (value != 0 ? 1 : 0);
 		chooseBoxPrune(s);
-		s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;      // (the hit kernel's occupancy is the variant's)
-		s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
-		s->rayLightBlocks[0] = s->rayLightBlocks[1] = 0;
-		s->rayScatterBlocks[0] = s->rayScatterBlocks[1] = 0;
-		s->pointLightBlocks[0] = s->pointLightBlocks[1] = 0;
-		s->pointAoBlocks[0] = s->pointAoBlocks[1] = 0;
-		for (auto& b : s->rayOccludedBlocks) b[0] = b[1] = 0;
 	}
 	else return fail(RTX_ERR_ARG, "unknown knob: " + n);
 	return RTX_OK;
@@ -2077,325 +1974,12 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 	return RTX_OK;
 }
 
-namespace {
+} // extern "C"
 
-// rtx_trace_rays groups the rays by key from this many on, unless they already come in coherent groups (rtxRayKeyKernel; measured on one
-// MI355X: profiles/trace_rays_time.json)
-constexpr uint32_t kTraceReorderMin = 1u << 20;
-// rtx_occluded_rays' own threshold for the same rule (profiles/occluded_rays_time.json)
-constexpr uint32_t kOccludedReorderMin = kTraceReorderMin;
-// ... and rtx_surface_rays': its times follow rtx_trace_rays' hits-only times within 0.1 ms at every setting of the knob, so it keeps that
-// call's threshold (profiles/surface_time.json)
-constexpr uint32_t kSurfaceReorderMin = kTraceReorderMin;
-// ... and rtx_light_rays': its first half is rtx_surface_rays' 
-constexpr uint32_t kLightReorderMin = kTraceReorderMin;
-// ... and rtx_scatter_rays': the same first half, and the same light loop for the hits that read the lights
-constexpr uint32_t kScatterReorderMin = kTraceReorderMin;
-// ... and rtx_light_points' and rtx_ao_points': the same grouping with {P, N} in the place of origin and direction
-constexpr uint32_t kPointsReorderMin = kTraceReorderMin;
+// the ray, point and first-hit queries of a loaded scene: their kernel selectors, shared host steps and entry points (uses the scene's internals above)
+#include "rtx_query.hip"
 
-// The scratch of rtx_trace_rays for n rays: only a larger n than ever before allocates (the old buffers are freed first -- hipFree waits
-// for the device, so no launch of an earlier call still reads them).  (The sort's scratch is asked for every call -- a host computation --
-// in case a smaller n ever needed more.)
-int ensureRayScratch(rtx_scene* s, uint32_t n, bool reorder, hipStream_t st)
-{
-	HIPCHK(s->rayWork.reserve(64));
-	if (!reorder) return RTX_OK;
-	if (n > s->rayCap) {
-		s->rayCap = 0;      // (until both are in place)
-		HIPCHK(s->rayKeys.reserve(2 * (size_t)n));
-		HIPCHK(s->rayOrder.reserve(n));
-		s->rayCap = n;
-	}
-	size_t bytes = 0;
-	HIPCHK(rtxSortRayKeys(nullptr, &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
-	HIPCHK(s->raySortTemp.reserve(bytes));
-	return RTX_OK;
-}
-
-// The order of n rays grouped by key (rtx_rays.hip: box, key with the coherence check, stable sort), queued on st after rtxRayInitKernel:
-// *order = the scene's rayOrder (ensureRayScratch has sized it).
-int groupRays(rtx_scene* s, const Params& p, const float* rays_dev, uint32_t n, hipStream_t st, const uint32_t** order)
-{
-	// the camera's position and axes: the frame of the key's coordinates (rtx_rays.hip, rayCoords)
-	const float* M = p.view.camM;
-	const RayAxes ax = { { M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10] }, { p.view.camPos[0], p.view.camPos[1], p.view.camPos[2] } };
-	const uint32_t groups = (uint32_t)(((size_t)n + 255) / 256);
-	double* spread = (double*)(s->rayWork + 44);
-	hipLaunchKernelGGL(rtxRayBoxKernel, dim3(std::min<uint32_t>(groups, (uint32_t)s->numCUs * 8u)), dim3(256), 0, st, rays_dev, n, ax, s->rayWork + 32, spread);
-	// (by default the caller's order is kept where it is already as coherent: rtxRayKeyKernel; trace_reorder = 1 always sorts)
-	hipLaunchKernelGGL(rtxRayKeyKernel, dim3(groups), dim3(256), 0, st, rays_dev, n, ax, (const uint32_t*)(s->rayWork + 32), (const double*)spread,
-	                   s->knobs.traceOriginFirst, s->knobs.traceReorder < 0 ? 1 : 0, s->rayKeys);
-	size_t bytes = s->raySortTemp.capacity();
-	HIPCHK(rtxSortRayKeys(s->raySortTemp.get(), &bytes, s->rayKeys, s->rayKeys + s->rayCap, s->rayOrder, n, kRayKeyBits, st));
-	*order = s->rayOrder;
-	return RTX_OK;
-}
-
-// What rtx_trace_rays and rtx_occluded_rays do before their own launches: the scene's work buffers, the order against the preparation, the
-// decision to group the rays (from reorderMin rays on, unless the knob trace_reorder says always / never) and, if so, their order.
-// p: the argument block of the launches to come.
-int beginRays(rtx_scene* s, uint32_t n, const float* rays_dev, uint32_t reorderMin, hipStream_t st, Params& p, const uint32_t** order)
-{
-	int rc = ensureWork(s);
-	if (rc) return rc;
-	if ((rc = renderOn(s, st))) return rc;
-	const bool reorder = s->knobs.traceReorder < 0 ? n >= reorderMin : s->knobs.traceReorder != 0;
-	if ((rc = ensureRayScratch(s, n, reorder, st))) return rc;
-	p = s->params;
-	p.probeRays = rays_dev; p.nProbe = n;
-	hipLaunchKernelGGL(rtxRayInitKernel, dim3(1), dim3(64), 0, st, s->rayWork.get());
-	*order = nullptr;
-	if (reorder && (rc = groupRays(s, p, rays_dev, n, st, order))) return rc;
-	return RTX_OK;
-}
-
-// The common start of rtx_trace_rays, rtx_occluded_rays and rtx_surface_rays, after their own checks: the checks of n and rays, then
-// beginRays, which fill c (RayCall).
-// false: the call ends here with rc -- no ray (RTX_OK), or an error.
-bool startRays(rtx_scene* s, uint32_t n, const float* rays_dev, uint32_t reorderMin, void* stream, RayCall& c, int& rc)
-{
-	rc = RTX_OK;
-	if (n == 0) return false;
-	if (!rays_dev) { rc = fail(RTX_ERR_ARG, "rays is NULL"); return false; }
-	if (n > 0xffffffc0u) { rc = fail(RTX_ERR_ARG, "too many rays"); return false; }
-	c.st = (hipStream_t)stream;
-	c.order = nullptr;
-	c.waves = (n + 63) / 64;
-	return (rc = beginRays(s, n, rays_dev, reorderMin, c.st, c.p, &c.order)) == RTX_OK;
-}
-
-} // namespace
-
-int rtx_trace_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* hits_dev, float* colours_dev, void* stream)
-{
-	RoctxRange range("Trace rays (rtx_trace_rays)");
-	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
-	if (!hits_dev && !colours_dev) return fail(RTX_ERR_ARG, "rtx_trace_rays: no output (hits and colours are both NULL)");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, rays_dev, kTraceReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	// (the recursion frames of the pass-1 area hold blocksPass1 blocks: the grid of the kernels that shade)
-	const uint32_t blocksShade = std::min<uint32_t>((uint32_t)s->blocksPass1, (c.waves + 3) / 4);
-	c.p.workCounter = s->rayWork;
-	if (showNormals(s)) hipLaunchKernelGGL(rtxRayNormalsKernel, dim3(blocksShade), dim3(256), 0, c.st, c.p, c.order, hits_dev, colours_dev);
-	else {
-		if (hits_dev && (rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, hits_dev))) return rc;
-		if (colours_dev) {
-			c.p.workCounter = s->rayWork + 16;
-			hipLaunchKernelGGL(rayColourKernel(v), dim3(blocksShade), dim3(256), 0, c.st, c.p, c.order, colours_dev);
-		}
-	}
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_occluded_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const float* tmax_dev, uint8_t* occluded_dev, void* stream)
-{
-	RoctxRange range("Occluded rays (rtx_occluded_rays)");
-	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
-	// (this call has always looked at n and rays first: an empty batch needs no output, and "rays is NULL" comes before this message)
-	if (n != 0 && rays_dev && !occluded_dev) return fail(RTX_ERR_ARG, "rtx_occluded_rays: no output (occluded is NULL)");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, rays_dev, kOccludedReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	const bool sceneOrder = s->knobs.occludedSceneOrder != 0;
-	c.p.workCounter = s->rayWork;
-	if ((rc = launchRays(s, rayOccludedKernel(v, sceneOrder), s->rayOccludedBlocks[v.cull ? 1 : 0][sceneOrder ? 1 : 0], c, tmax_dev, occluded_dev))) return rc;
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_surface_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_surface_buffers* out, void* stream)
-{
-	RoctxRange range("Surface rays (rtx_surface_rays)");
-	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	const bool surface = out->position_dev || out->normal_dev || out->albedo_dev || out->specular_dev;
-	if (!out->hits_dev && !surface) return fail(RTX_ERR_ARG, "rtx_surface_rays: no output (all five buffers are NULL)");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, rays_dev, kSurfaceReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	c.p.workCounter = s->rayWork;
-	// the hit records alone: rtx_trace_rays' launch (no surface fetch is compiled into that kernel)
-	if (!surface) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
-	else rc = launchRays(s, raySurfaceKernel(v), s->raySurfaceBlocks[v.cull ? 1 : 0], c, *out);
-	if (rc) return rc;
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_light_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_light_buffers* out, void* stream)
-{
-	RoctxRange range("Light rays (rtx_light_rays)");
-	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	const bool perLight = out->light_diffuse_dev || out->light_specular_dev || out->light_open_dev;
-	const bool light = out->diffuse_dev || out->specular_dev || perLight;
-	if (!out->hits_dev && !light) return fail(RTX_ERR_ARG, "rtx_light_rays: no output (all six buffers are NULL)");
-	// (a per-light buffer sized before rtx_scene_set_lights would be written past its end, or with another stride)
-	if (perLight && out->n_lights != s->params.nLights) return fail(RTX_ERR_ARG, "rtx_light_rays: n_lights is not the scene's number of lights");
-	if (perLight && s->params.nLights == 0) return fail(RTX_ERR_ARG, "rtx_light_rays: per-light buffers on a scene without lights");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, rays_dev, kLightReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	c.p.workCounter = s->rayWork;
-	// the hit records alone: rtx_trace_rays' launch
-	if (!light) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
-	else rc = launchRays(s, rayLightKernel(v), s->rayLightBlocks[v.cull ? 1 : 0], c, *out);
-	if (rc) return rc;
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_scatter_rays(rtx_scene* s, uint32_t n, const float* rays_dev, const rtx_scatter_buffers* out, void* stream)
-{
-	RoctxRange range("Scatter rays (rtx_scatter_rays)");
-	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	const bool scatter = out->local_dev || out->reflect_dev || out->refract_dev || out->weight_dev || out->kinds_dev;
-	if (!out->hits_dev && !scatter) return fail(RTX_ERR_ARG, "rtx_scatter_rays: no output (all six buffers are NULL)");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, rays_dev, kScatterReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	c.p.workCounter = s->rayWork;
-	// the hit records alone: rtx_trace_rays' launch
-	if (!scatter) rc = launchRays(s, rayHitKernel(v), s->rayHitBlocks[v.cull ? 1 : 0], c, out->hits_dev);
-	else rc = launchRays(s, rayScatterKernel(v), s->rayScatterBlocks[v.cull ? 1 : 0], c, *out);
-	if (rc) return rc;
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-// include/rtx_points.h: the batch is {P, N} in the layout of a ray buffer, so startRays' checks and grouping are the rays'
-int rtx_light_points(rtx_scene* s, uint32_t n, const float* points_dev, const float* view_dev, const rtx_light_buffers* out, void* stream)
-{
-	RoctxRange range("Light points (rtx_light_points)");
-	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	if (out->hits_dev) return fail(RTX_ERR_ARG, "rtx_light_points: hits_dev must be NULL (a point has no hit record)");
-	const bool perLight = out->light_diffuse_dev || out->light_specular_dev || out->light_open_dev;
-	if (!out->diffuse_dev && !out->specular_dev && !perLight) return fail(RTX_ERR_ARG, "rtx_light_points: no output (all five buffers are NULL)");
-	if (!view_dev && (out->specular_dev || out->light_specular_dev)) return fail(RTX_ERR_ARG, "rtx_light_points: a specular buffer without view_dev");
-	// (a per-light buffer sized before rtx_scene_set_lights would be written past its end, or with another stride)
-	if (perLight && out->n_lights != s->params.nLights) return fail(RTX_ERR_ARG, "rtx_light_points: n_lights is not the scene's number of lights");
-	if (perLight && s->params.nLights == 0) return fail(RTX_ERR_ARG, "rtx_light_points: per-light buffers on a scene without lights");
-	if (n != 0 && !points_dev) return fail(RTX_ERR_ARG, "rtx_light_points: points is NULL");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, points_dev, kPointsReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	c.p.workCounter = s->rayWork;
-	if ((rc = launchRays(s, pointLightKernel(v), s->pointLightBlocks[v.cull ? 1 : 0], c, view_dev, *out))) return rc;
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_ao_points(rtx_scene* s, uint32_t n, const float* points_dev, const rtx_ao_params* par, float* ao, uint32_t* counts, void* stream)
-{
-	RoctxRange range("Ambient occlusion at points (rtx_ao_points)");
-	if (!s || !par) return fail(RTX_ERR_ARG, "scene/params is NULL");
-	if (!ao && !counts) return fail(RTX_ERR_ARG, "rtx_ao_points: no output (both buffers are NULL)");
-	if (!par->dirs_dev) return fail(RTX_ERR_ARG, "rtx_ao_points: dirs_dev is NULL");
-	if (par->n_dirs < 1 || par->n_dirs > 256) return fail(RTX_ERR_ARG, "rtx_ao_points: n_dirs must be 1 .. 256");
-	if (!(par->radius > 0)) return fail(RTX_ERR_ARG, "rtx_ao_points: radius must be > 0 (+inf: the whole ray)");
-	if (n != 0 && !points_dev) return fail(RTX_ERR_ARG, "rtx_ao_points: points is NULL");
-	RayCall c;
-	int rc;
-	if (!startRays(s, n, points_dev, kPointsReorderMin, stream, c, rc)) return rc;
-	const Variant v = variantOf(s);
-	c.p.workCounter = s->rayWork;
-	const AoArgs args = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
-	if ((rc = launchRays(s, pointAoKernel(v), s->pointAoBlocks[v.cull ? 1 : 0], c, args))) return rc;
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_sky_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* colours_dev, void* stream)
-{
-	RoctxRange range("Sky rays (rtx_sky_rays)");
-	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
-	if (n == 0) return RTX_OK;
-	if (!rays_dev) return fail(RTX_ERR_ARG, "rays is NULL");
-	if (!colours_dev) return fail(RTX_ERR_ARG, "rtx_sky_rays: no output (colours is NULL)");
-	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "too many rays");
-	// a plain grid over the rays: no walk, no queue, none of the scene's ray scratch
-	const hipStream_t st = (hipStream_t)stream;
-	int rc = ensureWork(s);
-	if (rc) return rc;
-	if ((rc = renderOn(s, st))) return rc;
-	Params p = s->params;
-	p.probeRays = rays_dev; p.nProbe = n;
-	hipLaunchKernelGGL(rtxRaySkyKernel, dim3((uint32_t)(((size_t)n + 255) / 256)), dim3(256), 0, st, p, colours_dev);
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_render_aov(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_aov_buffers* out, void* stream)
-{
-	RoctxRange range("First-hit buffers (rtx_render_aov)");
-	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	if (!out->depth_dev && !out->object_dev && !out->triangle_dev && !out->uv_dev && !out->normal_dev && !out->albedo_dev)
-		return fail(RTX_ERR_ARG, "rtx_render_aov: no output (all six buffers are NULL)");
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_aov collects no statistics (rtx_counters_enable)");
-	// A plain grid over the tiles, as the normals view; no event is recorded (rtx_last_kernel_ms and the frame-mode measurements keep
-	// what the ordinary frames left).
-	Params p = s->params;
-	int rc;
-	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
-	HIPCHK(hipSetDevice(s->device));
-	hipStream_t st = (hipStream_t)stream;
-	if (int ro = renderOn(s, st)) return ro;
-	const bool surface = out->normal_dev || out->albedo_dev;
-	hipLaunchKernelGGL(aovKernel(variantOf(s), surface), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, *out);
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_render_ao(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_ao_params* par, float* ao, uint32_t* counts, void* stream)
-{
-	RoctxRange range("Ambient occlusion (rtx_render_ao)");
-	if (!s || !par) return fail(RTX_ERR_ARG, "scene/params is NULL");
-	if (!ao && !counts) return fail(RTX_ERR_ARG, "rtx_render_ao: no output (both buffers are NULL)");
-	if (!par->dirs_dev) return fail(RTX_ERR_ARG, "rtx_render_ao: dirs_dev is NULL");
-	if (par->n_dirs < 1 || par->n_dirs > 256) return fail(RTX_ERR_ARG, "rtx_render_ao: n_dirs must be 1 .. 256");
-	if (!(par->radius > 0)) return fail(RTX_ERR_ARG, "rtx_render_ao: radius must be > 0 (+inf: the whole ray)");
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_ao collects no statistics (rtx_counters_enable)");
-	// (the plain grid of rtx_render_aov; no event is recorded)
-	Params p = s->params;
-	int rc;
-	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
-	HIPCHK(hipSetDevice(s->device));
-	hipStream_t st = (hipStream_t)stream;
-	if (int ro = renderOn(s, st)) return ro;
-	const AoArgs a = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
-	hipLaunchKernelGGL(aoKernel(variantOf(s)), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, a);
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_render_light(rtx_scene* s, uint32_t rowBegin, uint32_t rowEnd, const rtx_frame_light_buffers* out, void* stream)
-{
-	RoctxRange range("Direct light (rtx_render_light)");
-	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
-	const bool perLight = out->light_diffuse_dev || out->light_specular_dev || out->light_open_dev;
-	if (!out->diffuse_dev && !out->specular_dev && !perLight) return fail(RTX_ERR_ARG, "rtx_render_light: no output (all five buffers are NULL)");
-	// (a per-light buffer sized before rtx_scene_set_lights would be written past its end)
-	if (perLight && out->n_lights != s->params.nLights) return fail(RTX_ERR_ARG, "rtx_render_light: n_lights is not the scene's number of lights");
-	if (perLight && s->params.nLights == 0) return fail(RTX_ERR_ARG, "rtx_render_light: per-light buffers on a scene without lights");
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_light collects no statistics (rtx_counters_enable)");
-	// (the plain grid of rtx_render_aov; no event is recorded)
-	Params p = s->params;
-	int rc;
-	if (!plainTileGrid(s, rowBegin, rowEnd, p, rc)) return rc;
-	HIPCHK(hipSetDevice(s->device));
-	hipStream_t st = (hipStream_t)stream;
-	if (int ro = renderOn(s, st)) return ro;
-	hipLaunchKernelGGL(lightFrameKernel(variantOf(s)), dim3((p.nTiles + 3) / 4), dim3(256), 0, st, p, *out);
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
+extern "C" {
 
 namespace {
 

@@ -245,19 +245,13 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 	if (!sb.empty()) s->meshLeaves.push_back({ devSpheres, (uint32_t)(sb.size() / 8) });
 	s->params.meshes = devMeshes; s->params.objects = devObjs; s->params.nObjects = nObjects;
 
-	// 4. the kernel variant again; with another family pass 1's grid, and the ray kernels' occupancy is asked again
+	// 4. the kernel variant again; with another family pass 1's grid (the ray kernels' occupancy is kept per kernel: blocksPerCU)
 	const bool wasAnalytic = s->analytic, wasPlain = s->plain;
 	chooseAnalytic(s);
 	chooseBoxPrune(s);
 	choosePlain(s);
 	if (s->analytic != wasAnalytic || s->plain != wasPlain)
 		if ((rc = askResidentBlocks(s))) return rc;
-	s->rayHitBlocks[0] = s->rayHitBlocks[1] = 0;
-	s->raySurfaceBlocks[0] = s->raySurfaceBlocks[1] = 0;
-	s->rayLightBlocks[0] = s->rayLightBlocks[1] = 0;
-	s->pointLightBlocks[0] = s->pointLightBlocks[1] = 0;
-	s->pointAoBlocks[0] = s->pointAoBlocks[1] = 0;
-	memset(s->rayOccludedBlocks, 0, sizeof(s->rayOccludedBlocks));
 
 	// 5. the view's preparation again: every source copy is built again, every tile list and frame-mode measurement forgotten
 	return refreshView(s);

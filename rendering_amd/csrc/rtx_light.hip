@@ -6,8 +6,8 @@
 // surfaceAtHit), of which P, N and the ray's direction stay alive.  Second half: a wave-uniform loop over the lights, as castRayPlainWave's:
 // light i's record comes through the scalar unit and is the same for all 64 lanes, so is the sample point of an area light in the inner
 // loop; every bundle the walk is handed is 64 shadow rays towards one source.  The any-hit trace has rtxAoKernel's shape -- spheres and
-// planes first, the mesh walk only for the lanes still open -- and is written out there (one site for every kind of light): shared with the
-// other kernels it cost them 1-5 %.  The loop's text is rtx_light_loop.h, which rtx_scatter.hip includes as well.  The shadow rays of point light i < P.nSrcLights walk with source class 2 + i, the rule
+// planes first, the mesh walk only for the lanes still open -- and is that kernel's text, RTX_ANY_HIT of rtx_rays.hip (one site for every
+// kind of light): as a function shared with the other kernels it cost them 1-5 %.  The loop's text is rtx_light_loop.h, which rtx_scatter.hip includes as well.  The shadow rays of point light i < P.nSrcLights walk with source class 2 + i, the rule
 // of advance() in rtx_kernels.hip.  No state machine, no park area, no recursion frames.
 #pragma clang fp contract(off)
 

@@ -59,29 +59,14 @@
 					moot = (!wantD || plusZero(I * a)) && (!wantS || plusZero(I * b));
 				}
 				const bool lit = hit && (wantOpen || !moot);
-				// rtx_occluded_rays' question for {O, -L} with the range dist: a NaN range occludes nothing (such a lane asks no object); a mesh
-				// records only t < FLT_MAX, so a range above FLT_MAX is FLT_MAX for its walk, whose bundle limit has to stay finite
+				// rtx_occluded_rays' question for {O, -L} with the range dist (RTX_ANY_HIT, rtx_rays.hip): a NaN range occludes nothing (such a
+				// lane asks no object).
+				// (Source class: a light's source copy was derived for shadow-ray origins within srcNmax |bias| of the surface: a longer shading
+				// normal, or NaN, falls back to copy 0 -- advance() in rtx_kernels.hip)
 				const bool asked = lit && !(dist != dist);
 				bool open = asked;
 				if (ballot(asked) != 0) {
-					const float tmWalk = dist > kFltMax ? kFltMax : dist;
-					if (!MESH) {
-						traceWave<false, false, false, BOXES, CULLK>(P, open, true, O, nL, dist, h, cnt);
-						open = open && h.obj < 0;
-					}
-					else {
-						traceWave<false, false, false, BOXES, CULLK, 1>(P, open, true, O, nL, dist, h, cnt);
-						open = open && h.obj < 0;
-						if (ballot(open) != 0) {
-							// (a light's source copy was derived for shadow-ray origins within srcNmax |bias| of the surface: a longer shading normal,
-							// or NaN, falls back to copy 0 -- advance() in rtx_kernels.hip)
-							const uint32_t src = (lt == 2 && li < P.nSrcLights && len2(n) <= P.srcNmax2) ? 2u + li : 0u;
-							RTX_LIGHT_LOOP_PARK
-							traceWave<false, true, false, BOXES, CULLK, 2>(P, open, true, O, nL, tmWalk, h, cnt, src);
-							RTX_LIGHT_LOOP_UNPARK
-							open = open && h.obj < 0;
-						}
-					}
+					RTX_ANY_HIT(open, O, nL, dist, RTX_WALK_RANGE(dist), (lt == 2 && li < P.nSrcLights && len2(n) <= P.srcNmax2) ? 2u + li : 0u, RTX_LIGHT_LOOP_PARK, RTX_LIGHT_LOOP_UNPARK)
 				}
 				open = lit && (open || !asked);
 				nOpen += open ? 1u : 0u;

@@ -8,8 +8,8 @@
 // dir = V and ns from the caller's view record, one 16-byte load per point.  The shadow rays of point light i < P.nSrcLights walk with
 // source class 2 + i under the two rules that make that copy valid for an origin anywhere in space: the length rule is in the loop's text
 // (len2(n) <= P.srcNmax2), the origin-magnitude rule is applied per record by the walk itself (pruneEval8: ainf <= kSrcAinfMax).
-// rtxPointAoKernel: rtxAoKernel's loop over the directions, written out -- direction k through the scalar unit, spheres and planes asked
-// first, the mesh walk for the lanes still open, a range above FLT_MAX capped for the walk.
+// rtxPointAoKernel: rtxAoKernel's loop over the directions (RTX_AO_DIRECTIONS, rtx_rays.hip) -- direction k through the scalar unit, spheres
+// and planes asked first, the mesh walk for the lanes still open, a range above FLT_MAX capped for the walk.
 #pragma clang fp contract(off)
 
 namespace {
@@ -55,36 +55,12 @@ template <bool MESH, bool BOXES, int CULLK>
 __global__ void __launch_bounds__(256) rtxPointAoKernel(const Params P, const uint32_t* order, const AoArgs A)
 {
 	Counts cnt = {};
-	// A mesh records only t < FLT_MAX, so a range above FLT_MAX is FLT_MAX for its walk, whose bundle limit has to stay finite; a sphere or
-	// a plane is compared with the range itself (rtxRayOccludedKernel).
-	const float tm = A.radius;
-	const float tmWalk = tm > kFltMax ? kFltMax : tm;
+	const float tmWalk = RTX_WALK_RANGE(A.radius);
 	const uint32_t nDirs = uni(A.nDirs);
 	forEachRayWave(P, order, [&](bool valid, uint32_t i, const V3& p, const V3& N) {
 		const V3 O = p + N * P.view.bias;                      // castRay's shadow-ray origin (scene.cpp:787)
 		Hit h;
-		uint32_t acc = 0;               // open | traced << 16
-		for (uint32_t k = 0; k < nDirs; k = uni(k + 1)) {
-			const float* dk = uni(A.dirs + (size_t)k * 3);
-			const V3 d = mk(sloadf(dk), sloadf(dk + 1), sloadf(dk + 2));
-			const float c = dot(N, d);
-			const bool traced = valid && c > 0;     // (strict: a zero or NaN direction, or a zero or NaN normal, is never traced)
-			if (ballot(traced) == 0) continue;
-			bool open = traced;
-			if (!MESH) {
-				traceWave<false, false, false, BOXES, CULLK>(P, open, true, O, d, tm, h, cnt);
-				open = open && h.obj < 0;
-			}
-			else {
-				traceWave<false, false, false, BOXES, CULLK, 1>(P, open, true, O, d, tm, h, cnt);
-				open = open && h.obj < 0;
-				if (ballot(open) != 0) {
-					traceWave<false, true, false, BOXES, CULLK, 2>(P, open, true, O, d, tmWalk, h, cnt);
-					open = open && h.obj < 0;
-				}
-			}
-			acc += (traced ? 0x10000u : 0u) + (open ? 1u : 0u);
-		}
+		RTX_AO_DIRECTIONS(valid, O, N, A)      // (declares acc; every point counts as a hit)
 		if (!valid) return;
 		const uint32_t nTraced = acc >> 16, nOpen = acc & 0xFFFFu;
 		if (A.counts) A.counts[i] = acc;

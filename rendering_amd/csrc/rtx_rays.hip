@@ -2,7 +2,7 @@
 // handed over in device memory, on the caller's stream.  DESIGN.md section 3.6.
 //
 // The walk (traceWave) is built for bundles of 64 coherent rays: one box of origins times one box of directions.  Rays in the order a
-// caller hands them over can be anything but coherent, so by default they are first grouped (the launch code in rtx_api.hip):
+// caller hands them over can be anything but coherent, so by default they are first grouped (the launch code in rtx_query.hip):
 //   1. rtxRayBoxKernel: the range of the rays' five key coordinates (direction and origin as seen from the camera: rayCoords), and how
 //      far they spread within the caller's own groups of 64;
 //   2. rtxRayKeyKernel: a 30-bit key per ray, the Morton interleave of the coordinates whose range is not empty, normalised to it
@@ -221,6 +221,68 @@ template __global__ void KERNEL<true, false, 0, ##__VA_ARGS__> ARGS;
 RTX_MESH_INSTANCES(KERNEL, ARGS, ##__VA_ARGS__)                        \
 template __global__ void KERNEL<false, true, -1, ##__VA_ARGS__> ARGS;
 
+// Texts that several kernels share, as function-like macros: they expand inside a kernel's body, where P (Params), h (a Hit the traces may
+// overwrite), cnt (Counts) and the template arguments MESH, BOXES and CULLK are in scope.  Macros and not __forceinline__ functions because
+// every kernel has to stay the machine code it was: as functions these steps came out with other register allocations, 1 - 5 % slower
+// (DESIGN.md 3.14, 3.19).
+
+// A mesh records only t < FLT_MAX (scene.cpp:735, 740), so a range above FLT_MAX is FLT_MAX for its walk, whose bundle limit has to stay
+// finite; a sphere or a plane is compared with the range itself.
+#define RTX_WALK_RANGE(TM) ((TM) > kFltMax ? kFltMax : (TM))
+
+// rtx_occluded_rays' question in its default order, for a wave: is the ray {O, D} of range TM (never NaN) open?  OPEN: in, the lanes that
+// ask; out, those of them that no opaque object blocks.  The spheres and planes are asked first (a few instructions per object), the
+// meshes are walked only for the lanes still open, with the source class SRC (evaluated only if some lane is) and the range TMWALK --
+// RTX_WALK_RANGE(TM), as that expression or as a value the kernel computed once.
+// PARK, UNPARK: statements right before and after the mesh walk, for a kernel that keeps values the walk does not read somewhere else
+// meanwhile (rtx_render_light.hip); may be empty.
+#define RTX_ANY_HIT(OPEN, O, D, TM, TMWALK, SRC, PARK, UNPARK)                                                    \
+	if (!MESH) {                                                                                                  \
+		traceWave<false, false, false, BOXES, CULLK>(P, OPEN, true, O, D, TM, h, cnt);                            \
+		OPEN = OPEN && h.obj < 0;                                                                                 \
+	}                                                                                                             \
+	else {                                                                                                        \
+		traceWave<false, false, false, BOXES, CULLK, 1>(P, OPEN, true, O, D, TM, h, cnt);                         \
+		OPEN = OPEN && h.obj < 0;                                                                                 \
+		if (ballot(OPEN) != 0) {                                                                                  \
+			const uint32_t anyHitSrc = (SRC);                                                                     \
+			PARK                                                                                                  \
+			traceWave<false, true, false, BOXES, CULLK, 2>(P, OPEN, true, O, D, TMWALK, h, cnt, anyHitSrc);         \
+			UNPARK                                                                                                \
+			OPEN = OPEN && h.obj < 0;                                                                             \
+		}                                                                                                         \
+	}
+
+// Ambient occlusion's loop over the directions (rtxAoKernel, rtxPointAoKernel): direction k comes through the scalar unit and is the same
+// for all 64 lanes; a lane traces it if LIVE and it leaves the surface on the side of the normal N, from O, with the any-hit question
+// above.  Declares acc = open | traced << 16.  A: the kernel's AoArgs.  Reads nDirs = uni(A.nDirs) and tmWalk = RTX_WALK_RANGE(A.radius),
+// which the kernel declares once: in front of forEachRayWave's loop in rtxPointAoKernel, whose machine code differs (other registers,
+// another schedule) with either inside it.
+#define RTX_AO_DIRECTIONS(LIVE, O, N, A)                                                                          \
+	uint32_t acc = 0;                                                                                             \
+	for (uint32_t k = 0; k < nDirs; k = uni(k + 1)) {                                                             \
+		const float* dk = uni(A.dirs + (size_t)k * 3);                                                            \
+		const V3 d = mk(sloadf(dk), sloadf(dk + 1), sloadf(dk + 2));                                              \
+		const float c = dot(N, d);                                                                                \
+		const bool traced = (LIVE) && c > 0;       /* strict: a zero or NaN direction or normal is never traced */ \
+		if (ballot(traced) == 0) continue;                                                                        \
+		bool open = traced;                                                                                       \
+		RTX_ANY_HIT(open, O, d, A.radius, tmWalk, 0u, , )                                                         \
+		acc += (traced ? 0x10000u : 0u) + (open ? 1u : 0u);                                                       \
+	}
+
+// The pixel of a lane in the frame queries' plain grid (rtxAovKernel, rtxAoKernel, rtxLightFrameKernel): one 8x8 tile per wave (the pattern
+// of rtxNormalsKernel's mode 0).  Declares wave, lane, W, H, tx, ty, x, y and valid -- pass 1's pixels of the rows this part owns (no halo
+// rows: nothing here looks at a neighbour) -- and ends the waves beyond the grid and those without a valid pixel.
+#define RTX_TILE_PIXEL()                                                                                          \
+	const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();                                \
+	if (wave >= P.nTiles) return;                                                                                 \
+	const uint32_t W = P.view.width, H = P.view.height;                                                           \
+	const uint32_t tx = wave % P.tilesX, ty = P.tileRow0 + wave / P.tilesX;                                       \
+	const uint32_t x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);                                             \
+	const bool valid = x < W - 1 && y < H - 1 && y >= P.rowBegin && y < P.rowEnd && rowOwned(P.bandH, P.nParts, P.part, y); \
+	if (ballot(valid) == 0) return;
+
 // Render::trace alone (hits only): no castRay state machine, no LDS park area, no recursion frames.  P.workCounter: this launch's queue
 // head; P.nProbe rays at P.probeRays.
 template <bool MESH, bool BOXES, int CULLK>
@@ -261,15 +323,8 @@ __global__ void __launch_bounds__(256) rtxRayOccludedKernel(const Params P, cons
 		const bool asked = valid && !(tm != tm);
 		bool open = asked;
 		Hit h;
-		// A mesh records only t < FLT_MAX (scene.cpp:735, 740), so a range above FLT_MAX is FLT_MAX for its walk, whose bundle limit has
-		// to stay finite; a sphere or a plane is compared with the range itself.
-		const float tmWalk = tm > kFltMax ? kFltMax : tm;
-		if (!MESH) {
-			traceWave<false, false, false, BOXES, CULLK>(P, open, true, o, d, tm, h, cnt);
-			open = open && h.obj < 0;
-		}
-		else if (ORDER) {
-			traceWave<false, true, false, BOXES, CULLK>(P, open, true, o, d, tmWalk, h, cnt);
+		if (MESH && ORDER) {
+			traceWave<false, true, false, BOXES, CULLK>(P, open, true, o, d, RTX_WALK_RANGE(tm), h, cnt);
 			open = open && h.obj < 0;
 			// (what only the unbounded range admits: a sphere or plane at exactly FLT_MAX)
 			if (ballot(open && tm > kFltMax) != 0) {
@@ -278,12 +333,7 @@ __global__ void __launch_bounds__(256) rtxRayOccludedKernel(const Params P, cons
 			}
 		}
 		else {
-			traceWave<false, false, false, BOXES, CULLK, 1>(P, open, true, o, d, tm, h, cnt);
-			open = open && h.obj < 0;
-			if (ballot(open) != 0) {
-				traceWave<false, true, false, BOXES, CULLK, 2>(P, open, true, o, d, tmWalk, h, cnt);
-				open = open && h.obj < 0;
-			}
+			RTX_ANY_HIT(open, o, d, tm, RTX_WALK_RANGE(tm), 0u, , )
 		}
 		if (valid) occluded[i] = (asked && !open) ? 1 : 0;
 	}

@@ -32,14 +32,7 @@ template <bool MESH, bool BOXES, int CULLK>
 __global__ void __launch_bounds__(256) rtxLightFrameKernel(const Params P, const rtx_frame_light_buffers out)
 {
 	fillPowTab();      // (powfRef's tables, in LDS; before any wave leaves: it holds the block's barrier)
-	const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
-	if (wave >= P.nTiles) return;
-	const uint32_t W = P.view.width, H = P.view.height;
-	const uint32_t tx = wave % P.tilesX, ty = P.tileRow0 + wave / P.tilesX;
-	const uint32_t x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-	// rtxAovKernel's pixels: pass 1's, of the rows this part owns
-	const bool valid = x < W - 1 && y < H - 1 && y >= P.rowBegin && y < P.rowEnd && rowOwned(P.bandH, P.nParts, P.part, y);
-	if (ballot(valid) == 0) return;
+	RTX_TILE_PIXEL()      // (x, y, valid, W, H)
 	// (wave-uniform: what the caller asked for)
 	const bool wantD = out.diffuse_dev || out.light_diffuse_dev, wantS = out.specular_dev || out.light_specular_dev;
 	const bool wantOpen = out.light_open_dev != nullptr;

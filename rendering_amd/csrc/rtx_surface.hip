@@ -4,7 +4,7 @@
 //
 // Built from the shared steps of rtx_rays.hip: forEachRayWave hands every persistent wave its rays through the order, traceWave runs in
 // its trace-only form with the general source class (these rays start anywhere), surfaceAtHit fetches the surface of the lanes that hit
-// and the sky colour of the others, storeHit and store3 write.  A request for the hit records alone never comes here (rtx_api.hip
+// and the sky colour of the others, storeHit and store3 write.  A request for the hit records alone never comes here (rtx_query.hip
 // launches rtxRayHitKernel for it), so the surface fetch is the only form of this kernel.
 #pragma clang fp contract(off)
 

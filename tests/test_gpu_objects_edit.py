@@ -300,6 +300,19 @@ def test_other_entry_points_after_an_object_edit(ra, tmp_path):
     frame(g, w, h)
     rays = torch.from_numpy(probe_rays(4096)).cuda()
     g.trace_rays(rays); g.occluded(rays)          # (the ray kernels of the first variant have been asked for)
+    dirs = torch.from_numpy(ra.sphere_directions(8)).cuda()
+
+    def queries(s, points=None):
+        """The surface, light and scatter queries at the probe rays, and the point queries at `points` (None: at this scene's own hits)."""
+        surf = s.surface_rays(rays, hits=True, position=True, normal=True, albedo=True, specular=True)
+        if points is None:
+            points = torch.cat([surf["position"], surf["normal"]], 1).contiguous()
+        out = dict(surface_rays=surf, light_rays=s.light_rays(rays, hits=True, per_light=True), scatter_rays=s.scatter_rays(rays, hits=True),
+                   light_points=s.light_points(points, per_light=True), ao_points=s.ao_points(points, dirs, counts=True))
+        torch.cuda.synchronize()
+        return {call: {ch: t.cpu().numpy() for ch, t in chans.items()} for call, chans in out.items()}, points
+
+    queries(g)                                    # (... and those of the surface, light, scatter and point queries)
     for step in [("remove", 1), ("add", "sphere", None, MIRROR), ("add", "mesh", 0, BUMPY), ("remove", 4)]:
         text = apply_step(g, text, step)
     f = ra.Scene(write_scene(tmp_path, text, "entry"), w, h)
@@ -315,6 +328,16 @@ def test_other_entry_points_after_an_object_edit(ra, tmp_path):
     for t in (None, tmax):
         assert np.array_equal(g.occluded(rays, t).cpu().numpy(), f.occluded(rays, t).cpu().numpy()), "occluded: differs from a fresh scene's"
     assert g.occluded(rays).cpu().numpy().any()
+    # the queries whose kernels were asked for before the edits: every channel, the point queries at the fresh scene's hits for both
+    qf, points = queries(f)
+    qg, _ = queries(g, points)
+    assert (qf["surface_rays"]["hits"][:, 1] >= 0).any() and qf["ao_points"]["counts"].any() and qf["light_points"]["light_open"].any()
+    for call in ("surface_rays", "light_rays", "scatter_rays", "light_points", "ao_points"):
+        assert list(qg[call]) == list(qf[call])
+        for ch in qf[call]:
+            a, b = qg[call][ch], qf[call][ch]
+            assert a.shape == b.shape and a.dtype == b.dtype and np.array_equal(bits(a) if a.dtype == np.float32 else a, bits(b) if b.dtype == np.float32 else b), (
+                "%s: the channel %s differs from a fresh scene's" % (call, ch))
     # the instrumented pass 1 and its counters
     p1 = []
     for s in (g, f):

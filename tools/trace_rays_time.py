@@ -119,7 +119,7 @@ def main():
                 med, mn = timed(lambda: s.trace_rays(rays, hits=hits, colours=colours), reps)
                 row["%s_%s_ms" % (mname, label)] = med
                 row["%s_%s_min_ms" % (mname, label)] = mn
-        # the defaults (trace_reorder -1: grouped from kTraceReorderMin rays on, unless the rays already come in coherent groups;
+        # the defaults (trace_reorder -1: grouped from kReorderMin rays on, unless the rays already come in coherent groups;
         # trace_key_origin_first 1), every output mode
         s.set_knob("trace_reorder", -1); s.set_knob("trace_key_origin_first", 1)
         for mname, (hits, colours) in MODES.items():
