@@ -75,6 +75,10 @@ RTX_POINTS_SYMBOLS = ["rtx_light_points", "rtx_ao_points"]
 # the extension of include/rtx_render_light.h: direct light of a frame (not part of the drop-in boundary)
 RTX_RENDER_LIGHT_SYMBOLS = ["rtx_render_light"]
 
+# the extension of include/rtx_radiance.h: radiance gathered over directions at caller-supplied surface points (not part of the drop-in
+# boundary)
+RTX_RADIANCE_SYMBOLS = ["rtx_radiance_points"]
+
 # the extension of include/rtx_deform.h: deforming a mesh of a live scene from vertices on the device (not part of the drop-in boundary)
 RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
 
@@ -151,6 +155,11 @@ class AoParams(C.Structure):
     _fields_ = [("n_dirs", C.c_uint32), ("dirs_dev", C.c_void_p), ("radius", C.c_float)]
 
 
+class RadianceParams(C.Structure):
+    """rtx_radiance_params (include/rtx_radiance.h)"""
+    _fields_ = [("n_dirs", C.c_uint32), ("dirs_dev", C.c_void_p), ("weights_dev", C.c_void_p), ("cosine", C.c_int32)]
+
+
 def sphere_directions(n):
     """n directions (n even) as float32 (n, 3): the first n / 2 are the upper half of a Fibonacci spiral over the sphere --
     z = 1 - 2 (i + 0.5) / n, phi = (i + 0.5) pi (3 - sqrt 5), (r cos phi, r sin phi, z) with r = sqrt(1 - z^2), in float64 rounded to
@@ -221,6 +230,8 @@ def load():
     if hasattr(rtx, "rtx_light_points"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_light_points.argtypes = [vp, u32, vp, vp, C.POINTER(LightBuffers), vp]
         rtx.rtx_ao_points.argtypes = [vp, u32, vp, C.POINTER(AoParams), vp, vp, vp]
+    if hasattr(rtx, "rtx_radiance_points"):      # (a library without it is reported by exported_symbols)
+        rtx.rtx_radiance_points.argtypes = [vp, u32, vp, C.POINTER(RadianceParams), vp, vp, vp]
     if hasattr(rtx, "rtx_render_light"):      # (a library without it is reported by exported_symbols)
         rtx.rtx_render_light.argtypes = [vp, u32, u32, C.POINTER(FrameLightBuffers), vp]
     if hasattr(rtx, "rtx_render_views"):      # (a library without them is reported by exported_symbols)
@@ -320,7 +331,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -1172,6 +1183,32 @@ class Scene:
         if n:
             par = AoParams(dirs.shape[0], dirs.data_ptr(), float(radius))
             _check(self.rtx.rtx_ao_points(self.gpu(), n, _ptr(points), C.byref(par), ptrs[0], ptrs[1], st), "rtx_ao_points")
+        return out
+
+    def radiance_points(self, points, dirs, weights=None, cosine=False, total=True, counts=False, stream=None):
+        """rtx_radiance_points: the radiance that arrives at surface points the caller already has, summed over a set of directions, on
+        the device (include/rtx_radiance.h).  points: as for light_points.  For every point, each direction of `dirs` (float32 (K, 3), K
+        in 1 .. 256, world space, used as stored) with c = N . d > 0 is cast from P + N * bias as trace_rays(colours=True) casts a ray --
+        the whole recursion, bit for bit -- and its colour enters the sum with the weight weights[k] (float32 (K,); None: 1) times c when
+        `cosine` is on, in the order of the directions.  Returns a dict of the channels asked for, new tensors on the points' device:
+        "sum" (n, 3), float32, +0 where nothing was traced (total=True); "counts" (n,), int32, the number of traced directions.
+        Refused while the "show_normals" flag is set.  Asynchronous on `stream`, which is handled as in trace_rays (dirs and weights are
+        recorded on it like the points)."""
+        import torch
+        if not (total or counts):
+            raise ValueError("radiance_points: nothing to compute (total and counts are both off)")
+        n = _check_rays("radiance_points", points, self.device, "points")
+        _check_tensor("radiance_points", "dirs", dirs, torch.float32, ("K", 3), self.device)
+        k = dirs.shape[0]
+        if k < 1 or k > 256:
+            raise ValueError("radiance_points: 1 .. 256 directions per call, got %d" % k)
+        if weights is not None:
+            _check_tensor("radiance_points", "weights", weights, torch.float32, (k,), self.device)
+        alloc_on, st = _query_stream(stream, points.device, (points, dirs, weights))
+        out, ptrs = _query_outputs((("sum", total, (3,), torch.float32), ("counts", counts, (), torch.int32)), n, points.device, alloc_on)
+        if n:
+            par = RadianceParams(k, dirs.data_ptr(), weights.data_ptr() if weights is not None else None, 1 if cosine else 0)
+            _check(self.rtx.rtx_radiance_points(self.gpu(), n, _ptr(points), C.byref(par), ptrs[0], ptrs[1], st), "rtx_radiance_points")
         return out
 
     SCATTER_CHANNELS = ("hits", "local", "reflect", "refract", "weight", "kinds")

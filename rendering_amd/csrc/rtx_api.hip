@@ -26,6 +26,7 @@
 #include "../../include/rtx_scatter.h"
 #include "../../include/rtx_points.h"
 #include "../../include/rtx_render_light.h"
+#include "../../include/rtx_radiance.h"
 #include "../../include/rtx_views.h"
 #include "rtx_device.h"
 #include "rtx_frame_plan.h"
@@ -46,6 +47,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_scatter.hip"
 #include "rtx_points.hip"
 #include "rtx_render_light.hip"
+#include "rtx_radiance.hip"
 #undef RTX_QUERY_INSTANCES
 #undef RTX_MESH_INSTANCES
 #undef RTX_WALK_RANGE

@@ -1,5 +1,5 @@
 // The queries of a loaded scene (include/rtx_query.h, rtx_surface.h, rtx_light.h, rtx_scatter.h, rtx_points.h, rtx_aov.h, rtx_ao.h,
-// rtx_render_light.h): which kernel a call launches, the host steps the calls share, and the entry points.  Included by rtx_api.hip after
+// rtx_render_light.h, rtx_radiance.h): which kernel a call launches, the host steps the calls share, and the entry points.  Included by rtx_api.hip after
 // the scene's internals (Variant, dispatchVariant, ensureWork, renderOn, plainTileGrid, fail / HIPCHK), as rtx_edit.hip is.
 
 namespace {
@@ -34,6 +34,7 @@ RTX_SELECTOR(aoKernel, (const Variant& v), false, (const Params, const AoArgs), 
 RTX_SELECTOR(lightFrameKernel, (const Variant& v), false, (const Params, const rtx_frame_light_buffers), rtxLightFrameKernel<M, B, C>)
 // (PLAIN exists for mesh scenes only: M && T)
 RTX_SELECTOR(rayColourKernel, (const Variant& v), v.plain, (const Params, const uint32_t*, float*), rtxRayColourKernel<M, B, C, M && T>)
+RTX_SELECTOR(pointRadianceKernel, (const Variant& v), v.plain, (const Params, const uint32_t*, const RadianceArgs), rtxPointRadianceKernel<M, B, C, M && T>)
 // rtx_render_views' pass-1 and SSAA kernels: the instances of rtxRayColourKernel
 RTX_SELECTOR(viewsPass1Kernel, (const Variant& v), v.plain, (const ViewsKernArgs), rtxViewsPass1Kernel<M, B, C, M && T>)
 RTX_SELECTOR(viewsSsaaKernel, (const Variant& v), v.plain, (const ViewsKernArgs), rtxViewsSsaaKernel<M, B, C, M && T>)
@@ -313,6 +314,29 @@ int rtx_ao_points(rtx_scene* s, uint32_t n, const float* points_dev, const rtx_a
 	if (!startRays(s, n, points_dev, stream, c, rc)) return rc;
 	const AoArgs args = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
 	return launchRays(s, pointAoKernel(variantOf(s)), c, args);
+}
+
+// include/rtx_radiance.h: the point queries' steps, and rtx_trace_rays' grid for the kernel that shades
+int rtx_radiance_points(rtx_scene* s, uint32_t n, const float* points_dev, const rtx_radiance_params* par, float* sum, uint32_t* counts, void* stream)
+{
+	RoctxRange range("Radiance at points (rtx_radiance_points)");
+	if (!s || !par) return fail(RTX_ERR_ARG, "scene/params is NULL");
+	if (!sum && !counts) return fail(RTX_ERR_ARG, "rtx_radiance_points: no output (both buffers are NULL)");
+	if (!par->dirs_dev) return fail(RTX_ERR_ARG, "rtx_radiance_points: dirs_dev is NULL");
+	if (par->n_dirs < 1 || par->n_dirs > 256) return fail(RTX_ERR_ARG, "rtx_radiance_points: n_dirs must be 1 .. 256");
+	if (par->cosine != 0 && par->cosine != 1) return fail(RTX_ERR_ARG, "rtx_radiance_points: cosine must be 0 or 1");
+	if (n != 0 && !points_dev) return fail(RTX_ERR_ARG, "rtx_radiance_points: points is NULL");
+	if (n > 0xffffffc0u) return fail(RTX_ERR_ARG, "rtx_radiance_points: too many points (n)");
+	if (showNormals(s)) return fail(RTX_ERR_UNSUPPORTED, "rtx_radiance_points: RTX_FLAG_SHOW_NORMALS is set (a debug view has no radiance)");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, points_dev, stream, c, rc)) return rc;
+	// (the recursion frames of the pass-1 area hold blocksPass1 blocks: rtx_trace_rays' blocksShade)
+	const uint32_t blocksShade = std::min<uint32_t>((uint32_t)s->blocksPass1, (c.waves + 3) / 4);
+	const RadianceArgs args = { par->dirs_dev, par->weights_dev, par->n_dirs, par->cosine, sum, counts };
+	hipLaunchKernelGGL(pointRadianceKernel(variantOf(s)), dim3(blocksShade), dim3(256), 0, c.st, c.p, c.order, args);
+	HIPCHK(hipGetLastError());
+	return RTX_OK;
 }
 
 int rtx_sky_rays(rtx_scene* s, uint32_t n, const float* rays_dev, float* colours_dev, void* stream)
