@@ -86,6 +86,9 @@ RTX_DEFORM_SYMBOLS = ["rtx_scene_set_mesh_topology", "rtx_scene_deform_mesh"]
 # declared in include/rtx_debug.h and listed with the probes above)
 RTX_VIEWS_SYMBOLS = ["rtx_render_views"]
 
+# the extension of include/rtx_views_aov.h: first-hit buffers and primary rays of many views in one call (not part of the drop-in boundary)
+RTX_VIEWS_AOV_SYMBOLS = ["rtx_render_views_aov"]
+
 
 class MeshTopology(C.Structure):
     """rtx_mesh_topology (include/rtx_deform.h): six counts, then five host pointers."""
@@ -129,6 +132,13 @@ class ViewTarget(C.Structure):
     """rtx_view_target (include/rtx_views.h): one view of a batch -- size, camera, device buffers."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("cam_pos", C.c_float * 3), ("cam_matrix", C.c_float * 16),
                 ("scale", C.c_float), ("aspect", C.c_float), ("fb_dev", C.c_void_p), ("mask_dev", C.c_void_p)]
+
+
+class ViewAovTarget(C.Structure):
+    """rtx_view_aov_target (include/rtx_views_aov.h): one view of a batch -- size and camera as ViewTarget's, then eight device pointers."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("cam_pos", C.c_float * 3), ("cam_matrix", C.c_float * 16),
+                ("scale", C.c_float), ("aspect", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("depth_dev", "object_dev", "triangle_dev", "uv_dev", "normal_dev", "albedo_dev", "position_dev", "rays_dev")]
 
 
 def cube_cameras(pos):
@@ -237,7 +247,10 @@ def load():
     if hasattr(rtx, "rtx_render_views"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_render_views.argtypes = [vp, u32, C.POINTER(ViewTarget), i32, vp]
         rtx.rtx_views_plan_probe.argtypes = [u32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-        host.rah_view_target.argtypes = [vp, vp, vp, C.c_float, i32, i32, C.POINTER(ViewTarget)]
+        # (the last: a ViewTarget or a ViewAovTarget, whose size and camera fields lie alike; the function leaves the buffers alone)
+        host.rah_view_target.argtypes = [vp, vp, vp, C.c_float, i32, i32, vp]
+    if hasattr(rtx, "rtx_render_views_aov"):      # (a library without it is reported by exported_symbols)
+        rtx.rtx_render_views_aov.argtypes = [vp, u32, C.POINTER(ViewAovTarget), vp]
     rtx.rtx_kernel_time_reset.argtypes = [vp]
     rtx.rtx_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     rtx.rtx_tile_cost_read.argtypes = [vp, vp, C.c_size_t]
@@ -331,7 +344,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -381,7 +394,14 @@ def _check_tensor(who, name, t, dtype, shape, device=None):
         raise ValueError("%s: %s must have shape %s, got %s" % (who, name, str(shape).replace("'", ""), tuple(t.shape)))
     if not t.is_contiguous():
         raise ValueError("%s: %s must be contiguous" % (who, name))
-    if device is not None and (t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != device):
+    if device is not None:
+        _check_device(who, name, t, device)
+
+
+def _check_device(who, name, t, device):
+    """... and is on cuda:`device` (_check_tensor's last check, for a wrapper that makes it after the shapes of all its tensors)."""
+    import torch
+    if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != device:
         raise ValueError("%s: %s must be on cuda:%d, the scene's device, got %s" % (who, name, device, t.device))
 
 
@@ -1420,6 +1440,75 @@ class Scene:
             t.mask_dev = mask_ptr
         _, st = _query_stream(stream, self.device, ([fbs, masks] if whole else fb_list + (mask_list or [])))
         _check(self.rtx.rtx_render_views(self.gpu(), n, targets, 1 if ssaa else 0, st), "rtx_render_views")
+
+    def render_views_aov(self, cameras, depth=None, object_id=None, triangle_id=None, uv=None, normal=None, albedo=None, position=None, rays=None,
+                         stream=None):
+        """rtx_render_views_aov: first-hit buffers and primary rays of many views of this scene in one call.  cameras: render_views'
+        sequence of (pos, rot) or (pos, rot, fov); cube_cameras(pos) gives the six of a cube map.  Every channel that is given (any subset,
+        at least one) is one tensor (N, H, W[, c]) or a list of N tensors (H_i, W_i[, c]) -- all channels in the same form --, contiguous
+        and on this scene's device: depth float32, object_id and triangle_id int32, uv float32 c = 2, normal, albedo and position float32
+        c = 3, rays float32 c = 6.  The sizes of the views are the tensors'; the channels of a view agree in size.
+        View i receives in its pixels x < W-1, y < H-1 the bits of set_camera + resize + render_aov with its camera and size, in `position`
+        the bits of surface_rays' position for the pixel's primary ray ((0, 0, 0) at a miss) and in `rays` that ray itself, {orig, dir}:
+        trace_rays(rays_i.reshape(-1, 6)) is render_pass1 of that view.  Nothing else of a tensor is touched.  The culling and skybox flags
+        and the background are this scene's current ones for every view.  The scene's own view, its tile costs and its timings are left
+        as they are.  Asynchronous on `stream` (None: torch's current stream of the scene's device); with a torch.cuda.Stream the tensors
+        are recorded on it."""
+        import torch
+        who = "render_views_aov"
+        cameras = list(cameras)
+        n = len(cameras)
+        f32, i32 = torch.float32, torch.int32
+        table = (("depth", depth, f32, ()), ("object_id", object_id, i32, ()), ("triangle_id", triangle_id, i32, ()), ("uv", uv, f32, (2,)),
+                 ("normal", normal, f32, (3,)), ("albedo", albedo, f32, (3,)), ("position", position, f32, (3,)), ("rays", rays, f32, (6,)))
+        given = [(k, name, t, dtype, tail) for k, (name, t, dtype, tail) in enumerate(table) if t is not None]
+        if not given:
+            raise ValueError("%s: nothing to compute (at least one channel is needed)" % who)
+        for _, name, t, _, _ in given:
+            if not isinstance(t, (torch.Tensor, list, tuple)):
+                raise ValueError("%s: %s must be a torch tensor or a list of torch tensors, got %s" % (who, name, type(t).__name__))
+        # one tensor per channel for the batch: checked once, the views' addresses follow from its shape (no per-view tensor is made)
+        whole = isinstance(given[0][2], torch.Tensor)
+        if any(isinstance(t, torch.Tensor) != whole for _, _, t, _, _ in given):
+            raise ValueError("%s: the channels must all be one tensor or all be lists" % who)
+        if whole:
+            nhw = None
+            for _, name, t, dtype, tail in given:
+                _check_tensor(who, name, t, dtype, (nhw or ("N", "H", "W")) + tail)
+                nhw = nhw or tuple(int(x) for x in t.shape[:3])
+            if nhw[0] != n:
+                raise ValueError("%s: %d cameras but %d views in %s" % (who, n, nhw[0], given[0][1]))
+            if nhw[1] < 1 or nhw[2] < 1:
+                raise ValueError("%s: %s is empty" % (who, given[0][1]))
+        else:
+            for _, name, t, _, _ in given:
+                if len(t) != n:
+                    raise ValueError("%s: %d cameras but %d tensors in %s" % (who, n, len(t), name))
+        targets = (ViewAovTarget * max(n, 1))()
+        for i, cam in enumerate(cameras):
+            if len(cam) not in (2, 3):
+                raise ValueError("%s: camera %d must be (pos, rot) or (pos, rot, fov)" % (who, i))
+            t = targets[i]
+            if whole:
+                h, w = nhw[1], nhw[2]
+                for k, _, ten, _, tail in given:
+                    setattr(t, ViewAovTarget._fields_[6 + k][0], ten.data_ptr() + i * h * w * 4 * (tail[0] if tail else 1))
+            else:
+                hw = None
+                for k, name, tens, dtype, tail in given:
+                    _check_tensor(who, "%s[%d]" % (name, i), tens[i], dtype, (hw or ("H", "W")) + tail)
+                    hw = hw or (int(tens[i].shape[0]), int(tens[i].shape[1]))
+                    setattr(t, ViewAovTarget._fields_[6 + k][0], tens[i].data_ptr())
+                h, w = hw
+                if h < 1 or w < 1:
+                    raise ValueError("%s: %s[%d] is empty" % (who, given[0][1], i))
+            self._fill_view_target(t, cam[0], cam[1], cam[2] if len(cam) == 3 else None, w, h)
+        # (the device last, so that what is wrong with the shapes and the cameras is said first)
+        for _, name, t, _, _ in given:
+            for j, x in enumerate((t,) if whole else t):
+                _check_device(who, name if whole else "%s[%d]" % (name, j), x, self.device)
+        _, st = _query_stream(stream, self.device, [g[2] for g in given] if whole else [x for g in given for x in g[2]])
+        _check(self.rtx.rtx_render_views_aov(self.gpu(), n, targets, st), "rtx_render_views_aov")
 
     def render_ao(self, dirs, radius=float("inf"), ao=None, counts=None, rows=None, stream=None):
         """rtx_render_ao: ambient occlusion of the frame in one launch.  For every pixel of pass 1 whose primary ray hits, each direction

@@ -40,6 +40,8 @@ RTX_SELECTOR(viewsPass1Kernel, (const Variant& v), v.plain, (const ViewsKernArgs
 RTX_SELECTOR(viewsSsaaKernel, (const Variant& v), v.plain, (const ViewsKernArgs), rtxViewsSsaaKernel<M, B, C, M && T>)
 // (surface: the normal or the albedo is asked for -- only then is shadePrimary part of the kernel)
 RTX_SELECTOR(aovKernel, (const Variant& v, bool surface), surface, (const Params, const rtx_aov_buffers), rtxAovKernel<M, B, C, T>)
+// (rtx_render_views_aov: surface -- the normal, the albedo or the hit point is asked for)
+RTX_SELECTOR(viewsAovKernel, (const Variant& v, bool surface), surface, (const ViewsAovKernArgs), rtxViewsAovKernel<M, B, C, T>)
 #undef RTX_SELECTOR
 // (sceneOrder: knob occluded_scene_order -- the objects in scene order instead of spheres and planes first; scenes without meshes have one
 // kernel, whose ORDER is true whatever the knob says)
