@@ -45,6 +45,12 @@ def lib():
         _lib.orc_refract.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         _lib.orc_powf.restype = C.c_float
         _lib.orc_powf.argtypes = [C.c_float, C.c_float]
+        _lib.orc_powf_n.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.orc_libm_powf_n.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.orc_reflect_n.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.orc_refract_n.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        _lib.orc_fresnel_n.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        _lib.orc_normalize_n.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
         _lib.orc_free.argtypes = [C.c_void_p]
         _lib.orc_save_bmp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p]
         _lib.orc_encode_bmp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -191,3 +197,54 @@ def normalize(v):
 
 def powf(x, y):
     return np.float32(lib().orc_powf(C.c_float(x), C.c_float(y)))
+
+
+# Array forms (one call for the whole array; the per-element calls above cost a ctypes round trip each).
+def _vec3(a):
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+
+
+def powf_n(x, y):
+    """orc_powf of every x[i], y[i]; y broadcasts to x's shape."""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.ascontiguousarray(np.broadcast_to(np.asarray(y, np.float32), x.shape))
+    out = np.zeros_like(x)
+    lib().orc_powf_n(x.size, _p(x), _p(y), _p(out))
+    return out
+
+
+def libm_powf_n(x, y):
+    """The host libm's powf over the same arrays (not the oracle: what tests/test_oracle_powf.py pins it to)."""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.ascontiguousarray(np.broadcast_to(np.asarray(y, np.float32), x.shape))
+    out = np.zeros_like(x)
+    lib().orc_libm_powf_n(x.size, _p(x), _p(y), _p(out))
+    return out
+
+
+def reflect_n(d, n):
+    d = _vec3(d); n = _vec3(n)
+    out = np.zeros_like(d)
+    lib().orc_reflect_n(d.shape[0], _p(d), _p(n), _p(out))
+    return out
+
+
+def refract_n(d, n, ior):
+    d = _vec3(d); n = _vec3(n)
+    out = np.zeros_like(d)
+    lib().orc_refract_n(d.shape[0], _p(d), _p(n), C.c_float(ior), _p(out))
+    return out
+
+
+def fresnel_n(d, n, ior):
+    d = _vec3(d); n = _vec3(n)
+    out = np.zeros(d.shape[0], np.float32)
+    lib().orc_fresnel_n(d.shape[0], _p(d), _p(n), C.c_float(ior), _p(out))
+    return out
+
+
+def normalize_n(v):
+    v = _vec3(v)
+    out = np.zeros_like(v)
+    lib().orc_normalize_n(v.shape[0], _p(v), _p(out))
+    return out

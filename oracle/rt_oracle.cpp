@@ -97,10 +97,14 @@ M44 eulerMatrix(V3 rot)
 // ------------------------------------------------------------------------------------------------
 // powf: glibc 2.35 sysdeps/ieee754/flt-32/e_powf.c (= ARM optimized-routines powf, tables
 // __powf_log2_data / __exp2f_data), in the form the x86-64 FMA ifunc variant executes it (every a*b+c
-// of the two polynomial kernels is one fused multiply-add; verified against libm's disassembly and
-// exhaustively-sampled outputs in tests/test_oracle_powf.py).  The reference calls std::pow(float,float)
-// -> glibc powf (scene.cpp:824,846,867,887,917,937); restating it makes the oracle independent of the
-// host's libm/CPU and gives the HIP kernel an exact specification.
+// of the two polynomial kernels is one fused multiply-add; verified against libm's disassembly).
+// tests/test_oracle_powf.py pins it: SHA-256 digests of glibc 2.35's outputs over the domains of
+// tests/util_device_math.py (every exponent of x with both signs against 35 values of y, every mantissa
+// of x at four exponents, every exponent of y) and, where the host's glibc is 2.35, libm's powf element by
+// element.  Known limit: for a signalling NaN x and y = +-0 glibc returns x + y (a quiet NaN), this
+// restatement 1; arithmetic never produces a signalling NaN, so no shading input reaches it.
+// The reference calls std::pow(float,float) -> glibc powf (scene.cpp:824,846,867,887,917,937); restating
+// it makes the oracle independent of the host's libm/CPU and gives the HIP kernel an exact specification.
 // ------------------------------------------------------------------------------------------------
 const double kLog2Tab[16][2] = {
 	{ 0x1.661ec79f8f3bep+0, -0x1.efec65b963019p-2 }, { 0x1.571ed4aaf883dp+0, -0x1.b0b6832d4fca4p-2 },
@@ -1364,6 +1368,32 @@ void orc_illuminate(const orc_scene* s, int li, const float* p, float* o)
 	o[0] = L.x; o[1] = L.y; o[2] = L.z; o[3] = I.x; o[4] = I.y; o[5] = I.z; o[6] = dist; o[7] = 0;
 }
 float orc_powf(float x, float y) { return powfRestated(x, y); }
+// array forms: the calls above in a loop
+void orc_powf_n(int64_t count, const float* x, const float* y, float* out)
+{
+	for (int64_t i = 0; i < count; i++) out[i] = orc_powf(x[i], y[i]);
+}
+// the host libm's powf (glibc 2.35 on the build machine: what powfRestated restates), for tests/test_oracle_powf.py and tools/make_golden_powf.py
+void orc_libm_powf_n(int64_t count, const float* x, const float* y, float* out)
+{
+	for (int64_t i = 0; i < count; i++) out[i] = std::pow(x[i], y[i]);
+}
+void orc_reflect_n(int64_t count, const float* d, const float* n, float* out)
+{
+	for (int64_t i = 0; i < count; i++) orc_reflect(d + 3 * i, n + 3 * i, out + 3 * i);
+}
+void orc_refract_n(int64_t count, const float* d, const float* n, float ior, float* out)
+{
+	for (int64_t i = 0; i < count; i++) orc_refract(d + 3 * i, n + 3 * i, ior, out + 3 * i);
+}
+void orc_fresnel_n(int64_t count, const float* d, const float* n, float ior, float* out)
+{
+	for (int64_t i = 0; i < count; i++) out[i] = orc_fresnel(d + 3 * i, n + 3 * i, ior);
+}
+void orc_normalize_n(int64_t count, const float* v, float* out)
+{
+	for (int64_t i = 0; i < count; i++) orc_normalize(v + 3 * i, out + 3 * i);
+}
 
 int orc_bvh_counts(const orc_scene* s, int obj, int64_t* c)
 {

@@ -57,6 +57,15 @@ void orc_skybox(const orc_scene*, const float* d, float* out);
 void orc_normalize(const float* v, float* out);
 void orc_illuminate(const orc_scene*, int light, const float* p, float* out8);
 float orc_powf(float x, float y);   /* restated glibc-2.35 FMA-variant powf (see rt_oracle.cpp) */
+/* Array forms of the five calls above: loops over the same functions, element i from d + 3*i / n + 3*i / x[i], y[i]
+ * (fresnel writes one float per element, the vector calls three).  For domains of millions of elements. */
+void orc_powf_n(int64_t count, const float* x, const float* y, float* out);
+/* NOT the oracle: the host libm's powf in the same loop, the yardstick the restatement is pinned to where the host has glibc 2.35 */
+void orc_libm_powf_n(int64_t count, const float* x, const float* y, float* out);
+void orc_reflect_n(int64_t count, const float* d, const float* n, float* out);
+void orc_refract_n(int64_t count, const float* d, const float* n, float ior, float* out);
+void orc_fresnel_n(int64_t count, const float* d, const float* n, float ior, float* out);
+void orc_normalize_n(int64_t count, const float* v, float* out);
 
 /* BVH of the mesh at object index obj: counts = [nNodes, nLeaves, nRefs, maxDepth, nTris]; dump in
  * pre-order (left child first).  Same layout as oracle/ref_harness.cpp. */
