@@ -172,7 +172,9 @@ int rtx_sobel(rtx_scene* scene, const float* fb_dev, uint32_t row_begin, uint32_
               uint8_t* mask_dev, void* stream);
 
 /* Pass 2 = the SSAAworker loop (scene.cpp:508-540) for rows [row_begin,row_end): every pixel with
- * mask_dev[y*W+x] != 0 is replaced by the mean of 4 castRay samples.  It may run on another stream beside
+ * mask_dev[y*W+x] != 0 is replaced by the mean of 4 castRay samples -- except in the last row and the last column: the
+ * reference's workers never visit them (scene.cpp:369-372), so a flag there is ignored and the pixel keeps its bits, as does
+ * every pixel that is not flagged.  It may run on another stream beside
  * rtx_render_pass1 / rtx_sobel of the NEXT frame into another framebuffer (frames of a sequence overlapped; the
  * caller orders each frame's stages with events): every frame equals the frame rendered alone.  The stages of
  * one framebuffer, and two rtx_render_ssaa calls of the scene, are ordered by the caller as ever. */
