@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(256) rtxDeformPlaceKernel(const rtxplace::Fit 
 		const float* p = nrm + j * 3;
 		v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
 		if (normalise) {
-			// Vec3::normalize through its fp64 factor: the device's exact one (rtx_kernels.hip, normalized)
+			// Vec3::normalize through its fp64 factor: the device's exact one (rtx_math.h, normalized)
 			const V3 u = normalized(mk(v[0], v[1], v[2]));
 			v[0] = u.x; v[1] = u.y; v[2] = u.z;
 		}

@@ -6,6 +6,8 @@
 
 #include <chrono>
 
+#include "rtx_scene.h"
+
 int rtxBvhBuildDevice(const float* tri_pos_dev, uint32_t n_tris, const float* root_lo, const float* root_hi, int32_t ac_penalty, int device, rtx_bvh** out);
 
 namespace {

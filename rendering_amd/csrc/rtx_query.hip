@@ -1,6 +1,7 @@
 // The queries of a loaded scene (include/rtx_query.h, rtx_surface.h, rtx_light.h, rtx_scatter.h, rtx_points.h, rtx_aov.h, rtx_ao.h,
 // rtx_render_light.h, rtx_radiance.h): which kernel a call launches, the host steps the calls share, and the entry points.  Included by rtx_api.hip after
-// the scene's internals (Variant, dispatchVariant, ensureWork, renderOn, plainTileGrid, fail / HIPCHK), as rtx_edit.hip is.
+// its launch bookkeeping (ensureWork, renderOn, plainTileGrid), as rtx_edit.hip is.
+#include "rtx_scene.h"      // (Variant, dispatchVariant, fail / HIPCHK)
 
 namespace {
 

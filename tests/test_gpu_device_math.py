@@ -1,4 +1,4 @@
-"""The device's powf and shading vector helpers (powfRef, reflectDir, refractDir, fresnelKr, normalized in rendering_amd/csrc/rtx_kernels.hip, through
+"""The device's powf and shading vector helpers (powfRef, reflectDir, refractDir, fresnelKr, normalized in rendering_amd/csrc/rtx_math.h, through
 rendering_amd.math_probe(0, ...) and vec_probe(0..3, ...)) against the CPU oracle's array calls over the whole domains of tests/util_device_math.py, under
 that module's comparison rule: equal bits, or both NaN.  tests/test_oracle_powf.py pins the oracle's powf to glibc 2.35 on the same inputs and
 tests/test_device_math_cpu.py shows that the inputs reach every branch.

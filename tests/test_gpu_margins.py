@@ -212,7 +212,7 @@ def test_environment_knobs_need_the_gate(ra, tmp_path, monkeypatch):
 
 # The variant matrix: the ray families of the margins through the kernels the product launches for frames and rtx_trace_rays -- compile-time
 # variants per (PLAIN, BOXES, CULL) for pass 1, SSAA, the single-launch frame and the colour kernel, per (BOXES, CULL) for the hit kernel
-# (rtx_api.hip variantOf; pass1Kernel, ssaaKernel, frameKernel, rayHitKernel, rayColourKernel).  PLAIN follows from the material (Diffuse everywhere, or a Phong mesh),
+# (rtx_scene.h variantOf; rtx_api.hip pass1Kernel, ssaaKernel, frameKernel, rayHitKernel, rayColourKernel).  PLAIN follows from the material (Diffuse everywhere, or a Phong mesh),
 # BOXES is forced with the knob, CULL is the scene's.  Every case asserts the bits it expects, and the list below names every combination
 # on every scene, so no selection of tests can shrink the matrix unnoticed.
 PHONG = "material=phong,0.4,0.1,0.7,10.0\n"

@@ -1,5 +1,5 @@
 """The input domains on which the device's powf and shading vector helpers (powfRef, reflectDir, refractDir, fresnelKr, normalized in
-rendering_amd/csrc/rtx_kernels.hip) are held to the CPU oracle, built once from fixed seeds and shared by tests/test_oracle_powf.py,
+rendering_amd/csrc/rtx_math.h) are held to the CPU oracle, built once from fixed seeds and shared by tests/test_oracle_powf.py,
 tests/test_device_math_cpu.py (what the domains reach, on the oracle alone) and tests/test_gpu_device_math.py (the device).
 
 Comparison rule (same()): two float32 results are equal when their bits are equal, or when both are NaN of any payload and sign -- x86 and

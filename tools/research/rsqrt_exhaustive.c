@@ -1,4 +1,4 @@
-// Exhaustive proof-by-enumeration for the fast path of invLenD (rendering_amd/csrc/rtx_kernels.hip):
+// Exhaustive proof-by-enumeration for the fast path of invLenD (rendering_amd/csrc/rtx_math.h):
 //     reference (geometry.h:104-112):  f = (float)(1.0 / sqrt((double)l2))
 //     fast path: y0 = v_rsq_f32(l2) (any value within +-3 ulp of the truth is tried here), one Newton step with exact fp32 residuals (FMA),
 //     a second exact residual decides whether the candidate is certainly the reference's value; otherwise the caller takes the fp64 path.
