@@ -386,289 +386,10 @@ int stamp(rtx_scene* s, int which, hipStream_t st)
 // the flatten of a mesh on the host and on the device (uses the scene's internals above and the tree of rtx_bvh.hip)
 #include "rtx_flatten.hip"
 
-namespace {
-
-// The fields of a mesh object's record that derive from its mesh (bx: the mesh's root box, its six floats of meshBounds).
-void meshObjectRecord(const float* bx, Object& d, const Mesh& dm, const rtx_scene::SrcMesh& sm)
-{
-	for (int c = 0; c < 3; c++) { d.rootBox[2 * c] = bx[c]; d.rootBox[2 * c + 1] = bx[3 + c]; }
-	d.fatRadius = dm.fatRadius; memcpy(d.centre, dm.centre, 12); d.radius = dm.radius;
-	d.meshFlags = (dm.nNodes ? 1u : 0u) | (dm.boxesRegular ? 2u : 0u) | (dm.nWide ? 4u : 0u);
-	d.nodes = dm.nodes; d.refA = dm.refA; d.refB = dm.refB; d.refC = dm.refC; d.wide = dm.wide; d.prune = dm.prune;
-	d.nNodes = dm.nNodes; d.vmax = dm.vmax;
-	d.srcStride = (dm.prune && sm.base) ? sm.nWide : 0u;
-	// The box test inflates a slot's true box by 216 dmax |orig - v0|_inf P (pruneAlive): with the origin about a mesh size away
-	// that is 216 P mesh sizes, so only meshes of small triangles gain from it; the plane test does not depend on P.
-	d.pruneBoxes = (dm.prune && std::isfinite(dm.rootRec.P) && dm.rootRec.P < 1.0f / 216.0f) ? 1u : 0u;
-}
-
-// A mesh of a description, checked before anything of it is uploaded (rtx_scene_create, rtx_scene_set_objects).
-int checkMesh(const rtx_mesh& m)
-{
-	if (!m.node_bounds || !m.node_skip || !m.leaf_begin || !m.leaf_count || (m.n_refs && !m.refs) || (m.n_tris && (!m.tri_pos || !m.tri_nrm || !m.tri_uv)))
-		return fail(RTX_ERR_ARG, "mesh arrays missing");
-	if (m.normal_map && !m.tri_tb) return fail(RTX_ERR_ARG, "normal map without tangents");
-	return RTX_OK;
-}
-
-// What of a mesh stays when its triangles move (rtx_scene_update_mesh): uv and maps, into a bag of their own.
-int uploadMeshFixed(const rtx_mesh& m, DevBag& fixed, Mesh& dm)
-{
-	HIPCHK(fixed.upload(m.tri_uv, (size_t)m.n_tris * 6, &dm.uv));
-	HIPCHK(fixed.upload(m.diffuse_map, (size_t)m.diffuse_w * m.diffuse_h * 3, &dm.diffuse));
-	HIPCHK(fixed.upload(m.normal_map, (size_t)m.normal_w * m.normal_h * 3, &dm.normal));
-	HIPCHK(fixed.upload(m.specular_map, (size_t)m.specular_w * m.specular_h, &dm.specular));
-	dm.dW = m.diffuse_w; dm.dH = m.diffuse_h; dm.nW = m.normal_w; dm.nH = m.normal_h; dm.sW = m.specular_w; dm.sH = m.specular_h;
-	return RTX_OK;
-}
-
-// Mesh `mi` of a description as the load uploads it, for nLights lights: the geometry, normals and tangents into `owned` (what
-// rtx_scene_update_mesh replaces), uv and maps into `fixed`.
-int uploadMesh(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, DevBag& owned, DevBag& fixed, Mesh& dm, rtx_scene::SrcMesh& sm,
-               rtx_scene::MeshLeaves& leaves, float bounds[6])
-{
-	memset(&dm, 0, sizeof(dm));
-	int rc;
-	if ((rc = uploadMeshGeometry(s, m, mi, nLights, owned, dm, sm, leaves, bounds))) return rc;
-	HIPCHK(owned.upload(m.tri_nrm, (size_t)m.n_tris * 9, &dm.nrm));
-	HIPCHK(owned.upload(m.tri_tb, m.tri_tb ? (size_t)m.n_tris * 6 : 0, &dm.tb));
-	return uploadMeshFixed(m, fixed, dm);
-}
-
-// The objects of a description, checked before anything is uploaded or replaced (rtx_scene_create, rtx_scene_set_objects).
-int checkObjects(uint32_t n, const rtx_object* objects, uint32_t nMeshes)
-{
-	if (n && !objects) return fail(RTX_ERR_ARG, "objects is NULL");
-	for (uint32_t i = 0; i < n; i++) {
-		const rtx_object& o = objects[i];
-		if (o.type < RTX_OBJ_SPHERE || o.type > RTX_OBJ_MESH) return fail(RTX_ERR_ARG, "bad object type");
-		if (o.material < 0 || o.material > 3) return fail(RTX_ERR_ARG, "bad material");
-		if (o.type == RTX_OBJ_MESH && (o.mesh < 0 || (uint32_t)o.mesh >= nMeshes)) return fail(RTX_ERR_ARG, "bad mesh index");
-	}
-	return RTX_OK;
-}
-
-// The object records of a description (checked: checkObjects) over the mesh records, source records and root boxes of its meshes.
-std::vector<Object> objectRecords(uint32_t n, const rtx_object* objects, const std::vector<Mesh>& meshes, const std::vector<rtx_scene::SrcMesh>& sms,
-                                  const std::vector<float>& meshBounds)
-{
-	std::vector<Object> objs(n);
-	for (uint32_t i = 0; i < n; i++) {
-		const rtx_object& o = objects[i];
-		Object& d = objs[i];
-		memset(&d, 0, sizeof(d));
-		d.type = o.type; d.material = o.material;
-		memcpy(d.pos, o.pos, 12); memcpy(d.color, o.color, 12); memcpy(d.normal, o.normal, 12);
-		d.ior = o.ior; d.ambient = o.ambient; d.diffuse = o.diffuse; d.specular = o.specular; d.nSpecular = o.n_specular;
-		d.r2 = o.radius2; d.mesh = o.mesh;
-		if (o.type == RTX_OBJ_MESH) meshObjectRecord(&meshBounds[(size_t)o.mesh * 6], d, meshes[o.mesh], sms[o.mesh]);
-	}
-	return objs;
-}
-
-// The Mesh[] and Object[] arrays and the spheres' entry of the cost estimate (sb: analyticEstimate) into `bag`.
-int uploadRecords(const std::vector<Mesh>& meshes, const std::vector<Object>& objs, const std::vector<float>& sb, DevBag& bag, const Mesh** devMeshes,
-                  const Object** devObjs, const float** devSpheres)
-{
-	HIPCHK(bag.upload(sb.data(), sb.size(), devSpheres));
-	HIPCHK(bag.upload(meshes.data(), meshes.size(), devMeshes));
-	HIPCHK(bag.upload(objs.data(), objs.size(), devObjs));
-	return RTX_OK;
-}
-
-// No object is a triangle mesh: the kernels without the walk are launched (over the current records).
-void chooseAnalytic(rtx_scene* s)
-{
-	s->analytic = true;
-	for (const Object& d : s->objectRecs) if (d.type == RTX_OBJ_MESH) s->analytic = false;
-}
-
-// The lights of a description, checked before anything is uploaded or replaced (rtx_scene_create, rtx_scene_set_lights).
-int checkLights(uint32_t n, const rtx_light* lights)
-{
-	if (n && !lights) return fail(RTX_ERR_ARG, "lights is NULL");
-	for (uint32_t i = 0; i < n; i++) {
-		const rtx_light& l = lights[i];
-		if (l.type < RTX_LIGHT_DISTANT || l.type > RTX_LIGHT_AREA) return fail(RTX_ERR_ARG, "bad light type");
-		if (l.type == RTX_LIGHT_AREA && (!l.points || l.n_points == 0)) return fail(RTX_ERR_ARG, "area light without sample points");
-	}
-	return RTX_OK;
-}
-
-// The light records and the area lights' sample points into `bag`: recs = the records as the device holds them, *dev = their array.
-int uploadLights(uint32_t n, const rtx_light* lights, DevBag& bag, std::vector<Light>& recs, const Light** dev)
-{
-	recs.resize(n);
-	for (uint32_t i = 0; i < n; i++) {
-		const rtx_light& l = lights[i];
-		Light& d = recs[i];
-		memset(&d, 0, sizeof(d));
-		d.type = l.type; memcpy(d.color, l.color, 12); d.intensity = l.intensity;
-		memcpy(d.dir, l.dir, 12); memcpy(d.pos, l.pos, 12);
-		d.nPoints = l.n_points;
-		if (l.type == RTX_LIGHT_AREA) HIPCHK(bag.upload(l.points, (size_t)l.n_points * 3, &d.points));
-	}
-	HIPCHK(bag.upload(recs.data(), recs.size(), dev));
-	return RTX_OK;
-}
-
-// What preparing a view and the launches read of the lights beside their records: the lights that have a source copy of the prune
-// records, the light terms of the first-frame estimate, the counts of the argument block.
-void deriveLights(rtx_scene* s, uint32_t n, const rtx_light* lights)
-{
-	s->srcLightPos.clear(); s->srcLightIsPoint.clear(); s->estLights.clear();
-	for (uint32_t i = 0; i < n; i++) {
-		const rtx_light& l = lights[i];
-		s->srcLightPos.push_back({ { l.pos[0], l.pos[1], l.pos[2] } });
-		s->srcLightIsPoint.push_back(l.type == RTX_LIGHT_POINT ? 1 : 0);
-		if (l.type == RTX_LIGHT_POINT) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f } });
-		else if (l.type == RTX_LIGHT_DISTANT) s->estLights.push_back({ { l.dir[0], l.dir[1], l.dir[2], 1.0f } });
-		// an area light casts n_points shadow rays per shaded point (scene.cpp:790-806) from about its centre: a point light whose shadow counts n_points times
-		else if (l.type == RTX_LIGHT_AREA) s->estLights.push_back({ { l.pos[0], l.pos[1], l.pos[2], 2.0f + 4.0f * (float)std::min<uint32_t>(l.n_points, 4096u) } });
-	}
-	s->params.nLights = n;
-	s->params.nSrcLights = s->knobs.sources ? std::min<uint32_t>(n, kMaxSrcLights) : 0u;
-}
-
-// The PLAIN kernel family holds while every object is Diffuse and no light an area light (over the current records).
-void choosePlain(rtx_scene* s)
-{
-	s->plain = true;
-	for (const Object& d : s->objectRecs) if (d.material != 0) s->plain = false;
-	for (const Light& l : s->lightRecs) if (l.type == RTX_LIGHT_AREA) s->plain = false;
-}
-
-// The spheres' and planes' share of what preparing a view reads (rtx_scene_create; again after rtx_scene_set_object, rtx_edit.hip): the planes the
-// cost estimate casts shadows on, the longest plane normal a shadow ray's origin is offset along and, returned, the spheres' entry of the estimate.
-std::vector<float> analyticEstimate(rtx_scene* s, const rtx_object* objects, size_t n)
-{
-	std::vector<float> sb;
-	s->estPlanes.clear();
-	s->srcNmax = 1.0f;
-	for (size_t i = 0; i < n; i++) {
-		const rtx_object& o = objects[i];
-		if (o.type == RTX_OBJ_PLANE) {
-			s->estPlanes.push_back({ { o.pos[0], o.pos[1], o.pos[2], o.normal[0], o.normal[1], o.normal[2] } });
-			const double nl = std::sqrt((double)o.normal[0] * o.normal[0] + (double)o.normal[1] * o.normal[1] + (double)o.normal[2] * o.normal[2]);
-			if (!(nl <= 1e30)) s->srcNmax = INFINITY; else s->srcNmax = std::max(s->srcNmax, (float)(nl * 1.000001));
-		}
-		// spheres take part in the first-frame cost estimate like leaves: a mirror or a glass ball is where the deep recursions start
-		if (o.type != RTX_OBJ_SPHERE || !(o.radius2 > 0) || !std::isfinite(o.radius2)) continue;
-		const float r = std::sqrt(o.radius2), w = (o.material == 1 || o.material == 2) ? 4000.0f : 300.0f;
-		sb.insert(sb.end(), { o.pos[0] - r, o.pos[1] - r, o.pos[2] - r, o.pos[0] + r, o.pos[1] + r, o.pos[2] + r, w, 0.0f });
-	}
-	s->params.srcNmax2 = s->srcNmax * s->srcNmax * 1.00001f;
-	return sb;
-}
-
-} // namespace
+// loading a scene: checks, uploads, rtx_scene_create / destroy / set_view (uses the view preparation above and uploadMeshGeometry of rtx_flatten.hip)
+#include "rtx_upload.hip"
 
 extern "C" {
-
-const char* rtx_last_error(void) { return gErr.c_str(); }
-
-int rtx_device_count(int* count)
-{
-	if (!count) return fail(RTX_ERR_ARG, "count is NULL");
-	*count = 0;
-	int n = 0;
-	hipError_t e = hipGetDeviceCount(&n);
-	if (e != hipSuccess) return fail(RTX_ERR_NO_DEVICE, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-	*count = n;
-	return RTX_OK;
-}
-
-int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
-{
-	if (!desc || !out) return fail(RTX_ERR_ARG, "desc/out is NULL");
-	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RTX_ERR_NO_DEVICE, "no HIP device visible");
-	if (device < 0 || device >= n) return fail(RTX_ERR_ARG, "device index out of range");
-	HIPCHK(hipSetDevice(device));
-	hipDeviceProp_t prop;
-	HIPCHK(hipGetDeviceProperties(&prop, device));
-
-	// (a scene that cannot be completed is destroyed on the way out)
-	std::unique_ptr<rtx_scene, void (*)(rtx_scene*)> hold(new rtx_scene, rtx_scene_destroy);
-	rtx_scene* s = hold.get();
-	readKnobs(s->knobs);
-	s->tileQueues.reserve(16);
-	s->device = device;
-	s->numCUs = prop.multiProcessorCount;
-	memset(&s->params, 0, sizeof(Params));
-
-	// meshes: nodes -> 32-byte records, leaf references -> (v0, e1, e2, tri) in three parallel arrays
-	int rc;
-	std::vector<Mesh> meshes(desc->n_meshes);
-	s->meshOwned.resize(desc->n_meshes);
-	s->meshFixed.resize(desc->n_meshes);
-	for (uint32_t mi = 0; mi < desc->n_meshes; mi++) {
-		const rtx_mesh& m = desc->meshes[mi];
-		if ((rc = checkMesh(m))) return rc;
-		rtx_scene::SrcMesh sm;
-		rtx_scene::MeshLeaves leaves{ nullptr, 0 };
-		float bounds[6];
-		// (the mesh's own allocations are what rtx_scene_update_mesh replaces; uv and maps stay for the mesh's life)
-		if ((rc = uploadMesh(s, m, mi, desc->n_lights, s->meshOwned[mi], s->meshFixed[mi], meshes[mi], sm, leaves, bounds))) return rc;
-		s->meshBounds.insert(s->meshBounds.end(), bounds, bounds + 6);
-		s->meshLeaves.push_back(leaves);
-		s->srcMeshes.push_back(sm);
-	}
-	if ((rc = checkObjects(desc->n_objects, desc->objects, desc->n_meshes))) return rc;
-	std::vector<Object> objs = objectRecords(desc->n_objects, desc->objects, meshes, s->srcMeshes, s->meshBounds);
-	if ((rc = checkLights(desc->n_lights, desc->lights))) return rc;
-	{
-		const std::vector<float> sb = analyticEstimate(s, desc->objects, desc->n_objects);
-		const float* dev = nullptr;
-		if ((rc = uploadRecords(meshes, objs, sb, s->recordsOwned, &s->params.meshes, &s->params.objects, &dev))) return rc;
-		if (!sb.empty()) s->meshLeaves.push_back({ dev, (uint32_t)(sb.size() / 8) });
-	}
-	s->meshRecs = meshes; s->objectRecs = objs;
-	chooseAnalytic(s);
-	chooseBoxPrune(s);
-	s->objectDescs.assign(desc->objects, desc->objects + desc->n_objects);
-	if ((rc = uploadLights(desc->n_lights, desc->lights, s->lightsOwned, s->lightRecs, &s->params.lights))) return rc;
-	s->params.nObjects = desc->n_objects;
-	deriveLights(s, desc->n_lights, desc->lights);
-	choosePlain(s);
-	if (desc->sky_w && desc->sky_h && desc->sky[0]) {
-		const float* faces[6];
-		for (int k = 0; k < 6; k++) {
-			if (!desc->sky[k]) return fail(RTX_ERR_ARG, "skybox face missing");
-			HIPCHK(s->owned.upload(desc->sky[k], (size_t)desc->sky_w * desc->sky_h * 3, &faces[k]));
-		}
-		HIPCHK(s->owned.upload(faces, 6, &s->params.sky));
-		s->params.skyW = desc->sky_w; s->params.skyH = desc->sky_h;
-	}
-	if ((rc = setView(s, &desc->view))) return rc;
-	if ((rc = ensureWork(s))) return rc;
-	if ((rc = prepareView(s))) return rc;
-	if ((rc = prepEnd(s))) return rc;
-	*out = hold.release();
-	return RTX_OK;
-}
-
-void rtx_scene_destroy(rtx_scene* s)
-{
-	if (!s) return;
-	(void)hipSetDevice(s->device);
-	(void)hipDeviceSynchronize();
-	delete s;
-}
-
-int rtx_scene_set_view(rtx_scene* s, const rtx_view* v)
-{
-	if (!s || !v) return fail(RTX_ERR_ARG, "scene/view is NULL");
-	int rc = setView(s, v);
-	if (rc) return rc;
-	s->viewSerial++;
-	s->lastFused.valid = false;
-	if ((rc = ensureWork(s))) return rc;
-	if ((rc = prepBegin(s))) return rc;
-	if ((rc = prepareView(s))) return rc;
-	return prepEnd(s);
-}
 
 namespace {
 
@@ -1769,240 +1490,11 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 // the ray, point and first-hit queries of a loaded scene: their kernel selectors, shared host steps and entry points (uses the scene's internals above)
 #include "rtx_query.hip"
 
-extern "C" {
+// the host half of the view batches (uses the selectors of rtx_query.hip and ensureWork / renderOn above)
+#include "rtx_views_api.hip"
 
-namespace {
-
-// What the batch calls and the plan's probe refuse of a batch's sizes; *items = the batch's tiles.  who: the call's name.
-int checkViewSizes(const char* who, uint32_t n, const uint32_t* w, const uint32_t* h, size_t stride, uint64_t* items)
-{
-	const std::string name = who;
-	if (n > rtxviews::kMaxViews) return fail(RTX_ERR_ARG, name + ": more than RTX_VIEWS_MAX_VIEWS views");
-	uint64_t total = 0;
-	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t W = *(const uint32_t*)((const char*)w + i * stride), H = *(const uint32_t*)((const char*)h + i * stride);
-		if (W == 0 || H == 0) return fail(RTX_ERR_ARG, name + ": view " + std::to_string(i) + " has a zero width or height");
-		if (W > rtxviews::kMaxSide || H > rtxviews::kMaxSide) return fail(RTX_ERR_ARG, name + ": view " + std::to_string(i) + " is larger than RTX_VIEWS_MAX_SIDE");
-		total += rtxviews::tilesOf(W, H);
-	}
-	if (total > rtxviews::kMaxItems) return fail(RTX_ERR_ARG, name + ": more than RTX_VIEWS_MAX_TILES tiles in all");
-	*items = total;
-	return RTX_OK;
-}
-
-// The record of view t of a batch (rtx_view_target or rtx_view_aov_target: their size and camera fields are the same) whose items start at
-// `at`: the camera and size as the kernels read them, no buffers.  Returns the first item of the next view.
-extern "C++" template <typename Target> uint32_t fillViewRec(ViewRec& r, const Target& t, uint32_t at)
-{
-	r.width = t.width; r.height = t.height; r.scale = t.scale; r.aspect = t.aspect;
-	memcpy(r.camPos, t.cam_pos, 12); memcpy(r.camM, t.cam_matrix, 64);
-	r.firstItem = at;
-	r.fb = nullptr; r.mask = nullptr;
-	r.tilesX = rtxviews::tilesAcross(t.width); r.pad[0] = r.pad[1] = r.pad[2] = 0;
-	return at + (uint32_t)rtxviews::tilesOf(t.width, t.height);
-}
-
-// The staging buffer of the batch calls with `bytes` in it and free to be filled: the previous call's copy out of it has been made (the
-// only wait besides the growth of a table).  The calls on one scene never overlap, so rtx_render_views and rtx_render_views_aov share it.
-int viewsStageFor(rtx_scene* s, size_t bytes)
-{
-	if (s->viewsStagePending) { HIPCHK(hipEventSynchronize(s->viewsStaged)); s->viewsStagePending = false; }
-	HIPCHK(s->viewsStage.reserve(bytes));
-	return RTX_OK;
-}
-
-// ... and its copy into the device's table, queued on st with the event the next call waits for
-int viewsStageCopy(rtx_scene* s, size_t bytes, hipStream_t st)
-{
-	HIPCHK(hipMemcpyAsync(s->viewsTable.get(), s->viewsStage.host(), bytes, hipMemcpyHostToDevice, st));
-	HIPCHK(s->viewsStaged.create(hipEventDisableTiming));
-	HIPCHK(hipEventRecord(s->viewsStaged, st));
-	s->viewsStagePending = true;
-	return RTX_OK;
-}
-
-} // namespace
-
-int rtx_views_plan_probe(uint32_t n_views, const uint32_t* sizes2, uint32_t* items3_out, size_t cap_items, size_t* n_items)
-{
-	if (!n_items || (n_views && !sizes2)) return fail(RTX_ERR_ARG, "rtx_views_plan_probe: NULL argument");
-	uint64_t items = 0;
-	if (int rc = checkViewSizes("rtx_render_views", n_views, sizes2, sizes2 + 1, 8, &items)) return rc;
-	*n_items = (size_t)items;
-	if (!items3_out || cap_items < items) return RTX_OK;
-	// the table as rtx_render_views lays it out, read as the kernels read it
-	std::vector<uint32_t> first(n_views + 1, 0u);
-	for (uint32_t v = 0; v < n_views; v++) first[v + 1] = first[v] + (uint32_t)rtxviews::tilesOf(sizes2[2 * v], sizes2[2 * v + 1]);
-	for (uint32_t item = 0; item < (uint32_t)items; item++) {
-		const uint32_t v = rtxviews::viewOfItem([&](uint32_t i) { return first[i]; }, n_views, item);
-		const rtxviews::Tile t = rtxviews::tileOfItem(item, first[v], rtxviews::tilesAcross(sizes2[2 * v]));
-		items3_out[3 * (size_t)item] = v; items3_out[3 * (size_t)item + 1] = t.tx; items3_out[3 * (size_t)item + 2] = t.ty;
-	}
-	return RTX_OK;
-}
-
-int rtx_render_views(rtx_scene* s, uint32_t n_views, const rtx_view_target* views, int with_ssaa, void* stream)
-{
-	RoctxRange range("Render views (rtx_render_views)");
-	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
-	if (n_views == 0) return RTX_OK;
-	if (!views) return fail(RTX_ERR_ARG, "rtx_render_views: views is NULL");
-	uint64_t items64 = 0;
-	if (int rc = checkViewSizes("rtx_render_views", n_views, &views[0].width, &views[0].height, sizeof(rtx_view_target), &items64)) return rc;
-	for (uint32_t i = 0; i < n_views; i++) {
-		if (!views[i].fb_dev) return fail(RTX_ERR_ARG, "rtx_render_views: view " + std::to_string(i) + " has no framebuffer (fb_dev is NULL)");
-		if (with_ssaa && !views[i].mask_dev) return fail(RTX_ERR_ARG, "rtx_render_views: view " + std::to_string(i) + " has no mask (mask_dev is NULL) and SSAA is asked for");
-	}
-	if (s->params.bandH && s->params.nParts > 1) return fail(RTX_ERR_ARG, "rtx_render_views: the rows are shared among devices (rtx_set_row_ownership); deal out views, not rows");
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_views collects no statistics (rtx_counters_enable)");
-	if (showNormals(s)) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_views does not render the normals view (RTX_FLAG_SHOW_NORMALS)");
-	const uint32_t nItems = (uint32_t)items64;
-	// (sizes the recursion frames for the current view's depth; the tile lists, tile costs and events are neither used nor touched from here on)
-	int rc = ensureWork(s);
-	if (rc) return rc;
-	hipStream_t st = (hipStream_t)stream;
-	if ((rc = renderOn(s, st))) return rc;
-	// the batch's scratch: only a larger batch than any before allocates (which waits for the device)
-	const size_t recBytes = (size_t)n_views * sizeof(ViewRec), tableBytes = recBytes + ((size_t)n_views + 1) * sizeof(uint32_t);
-	HIPCHK(s->viewsTable.reserve(tableBytes));
-	HIPCHK(s->viewsWork.reserve(64));
-	if (with_ssaa) { HIPCHK(s->viewsItemView.reserve(nItems)); HIPCHK(s->viewsList.reserve((size_t)nItems * 64)); }
-	// the staging buffer is free again once the previous call's copy out of it has been made
-	if ((rc = viewsStageFor(s, tableBytes))) return rc;
-	ViewRec* recs = (ViewRec*)s->viewsStage.host();
-	uint32_t* first = (uint32_t*)(s->viewsStage.host() + recBytes);
-	uint32_t at = 0;
-	for (uint32_t i = 0; i < n_views; i++) {
-		first[i] = at;
-		at = fillViewRec(recs[i], views[i], at);
-		recs[i].fb = views[i].fb_dev; recs[i].mask = views[i].mask_dev;
-	}
-	first[n_views] = at;
-	if ((rc = viewsStageCopy(s, tableBytes, st))) return rc;
-	HIPCHK(hipMemsetAsync(s->viewsWork.get(), 0, 64 * sizeof(uint32_t), st));
-	ViewsKernArgs k;
-	k.P = s->params;
-	k.A.views = (const ViewRec*)s->viewsTable.get(); k.A.first = (const uint32_t*)(s->viewsTable.get() + recBytes);
-	k.A.nViews = n_views; k.A.nItems = nItems;
-	k.A.itemView = s->viewsItemView; k.A.list = s->viewsList; k.A.heads = s->viewsWork;
-	const Variant v = variantOf(s);
-	// (the recursion frames of the pass-1 area hold blocksPass1 blocks)
-	const uint32_t itemBlocks = (nItems + 3) / 4;
-	hipLaunchKernelGGL(viewsPass1Kernel(v), dim3(std::min<uint32_t>((uint32_t)s->blocksPass1, itemBlocks)), dim3(256), 0, st, k);
-	HIPCHK(hipGetLastError());
-	if (!with_ssaa) return RTX_OK;
-	hipLaunchKernelGGL(rtxViewsMaskKernel, dim3(itemBlocks), dim3(256), 0, st, k.A);
-	HIPCHK(hipGetLastError());
-	// (the list's length is the device's to know: at most four SSAA items per tile, and a wave that finds the queue empty ends at once)
-	k.P.frames = s->frames + s->framesArea;
-	hipLaunchKernelGGL(viewsSsaaKernel(v), dim3(std::min<uint32_t>((uint32_t)s->blocksSsaa, nItems)), dim3(256), 0, st, k);
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_render_views_aov(rtx_scene* s, uint32_t n_views, const rtx_view_aov_target* views, void* stream)
-{
-	RoctxRange range("First-hit buffers of views (rtx_render_views_aov)");
-	const char* who = "rtx_render_views_aov";
-	if (!s) return fail(RTX_ERR_ARG, "scene is NULL");
-	if (n_views == 0) return RTX_OK;
-	if (!views) return fail(RTX_ERR_ARG, "rtx_render_views_aov: views is NULL");
-	uint64_t items64 = 0;
-	if (int rc = checkViewSizes(who, n_views, &views[0].width, &views[0].height, sizeof(rtx_view_aov_target), &items64)) return rc;
-	// one channel set for the batch: view 0's, in ViewAovRec's order
-	static const char* const kChannel[8] = { "depth_dev", "object_dev", "triangle_dev", "uv_dev", "normal_dev", "albedo_dev", "position_dev", "rays_dev" };
-	auto channels = [](const rtx_view_aov_target& t) {
-		const ViewAovRec c = { t.depth_dev, t.object_dev, t.triangle_dev, t.uv_dev, t.normal_dev, t.albedo_dev, t.position_dev, t.rays_dev };
-		return c;
-	};
-	auto presentOf = [](const ViewAovRec& c) {
-		const void* const p[8] = { c.depth, c.object, c.triangle, c.uv, c.normal, c.albedo, c.position, c.rays };
-		uint32_t m = 0;
-		for (int k = 0; k < 8; k++) if (p[k]) m |= 1u << k;
-		return m;
-	};
-	const uint32_t present = presentOf(channels(views[0]));
-	if (!present) return fail(RTX_ERR_ARG, "rtx_render_views_aov: no output (all eight channels of view 0 are NULL)");
-	for (uint32_t i = 1; i < n_views; i++) {
-		const uint32_t differ = presentOf(channels(views[i])) ^ present;
-		if (!differ) continue;
-		const int k = __builtin_ctz(differ);
-		return fail(RTX_ERR_ARG, std::string(who) + ": view " + std::to_string(i) + ((present >> k & 1u) ? " has no " : " has a ") + kChannel[k] + " but view 0 " +
-		            ((present >> k & 1u) ? "has one" : "has none") + " (a channel is given in every view of a batch or in none)");
-	}
-	if (s->params.bandH && s->params.nParts > 1) return fail(RTX_ERR_ARG, "rtx_render_views_aov: the rows are shared among devices (rtx_set_row_ownership); deal out views, not rows");
-	if (s->stats) return fail(RTX_ERR_UNSUPPORTED, "rtx_render_views_aov collects no statistics (rtx_counters_enable)");
-	const uint32_t nItems = (uint32_t)items64;
-	// (no recursion frames, no tile lists, no events: nothing of the scene's frame state is used or touched from here on)
-	HIPCHK(hipSetDevice(s->device));
-	hipStream_t st = (hipStream_t)stream;
-	int rc = renderOn(s, st);
-	if (rc) return rc;
-	// the batch's table -- the views' records, their channel records, the first item of every view: only a batch of more views than any
-	// before allocates (which waits for the device)
-	const size_t recBytes = (size_t)n_views * sizeof(ViewRec), chanBytes = (size_t)n_views * sizeof(ViewAovRec);
-	const size_t tableBytes = recBytes + chanBytes + ((size_t)n_views + 1) * sizeof(uint32_t);
-	HIPCHK(s->viewsTable.reserve(tableBytes));
-	if ((rc = viewsStageFor(s, tableBytes))) return rc;
-	ViewRec* recs = (ViewRec*)s->viewsStage.host();
-	ViewAovRec* chans = (ViewAovRec*)(s->viewsStage.host() + recBytes);
-	uint32_t* first = (uint32_t*)(s->viewsStage.host() + recBytes + chanBytes);
-	uint32_t at = 0;
-	for (uint32_t i = 0; i < n_views; i++) {
-		first[i] = at;
-		at = fillViewRec(recs[i], views[i], at);
-		chans[i] = channels(views[i]);
-	}
-	first[n_views] = at;
-	if ((rc = viewsStageCopy(s, tableBytes, st))) return rc;
-	ViewsAovKernArgs k;
-	k.P = s->params;
-	k.views = (const ViewRec*)s->viewsTable.get(); k.chans = (const ViewAovRec*)(s->viewsTable.get() + recBytes);
-	k.first = (const uint32_t*)(s->viewsTable.get() + recBytes + chanBytes);
-	k.nViews = n_views; k.nItems = nItems; k.present = present;
-	// one wave per item
-	const bool surface = (present & (VA_NORMAL | VA_ALBEDO | VA_POSITION)) != 0;
-	hipLaunchKernelGGL(viewsAovKernel(variantOf(s), surface), dim3((nItems + 3) / 4), dim3(256), 0, st, k);
-	HIPCHK(hipGetLastError());
-	return RTX_OK;
-}
-
-int rtx_math_probe(int device, int op, uint32_t n, const float* x, const float* y, float* out)
-{
-	if (!x || !out || op < 0 || op > 4) return fail(RTX_ERR_ARG, "bad argument");
-	int cnt = 0;
-	if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(RTX_ERR_NO_DEVICE, "no HIP device visible");
-	HIPCHK(hipSetDevice(device));
-	DevArray<float> dx, dy, dout;
-	const size_t bytes = (size_t)n * sizeof(float);
-	HIPCHK(dx.reserve(n)); HIPCHK(dy.reserve(n)); HIPCHK(dout.reserve(n));
-	HIPCHK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
-	if (y) HIPCHK(hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice));
-	else HIPCHK(hipMemset(dy, 0, bytes));
-	hipLaunchKernelGGL(rtxMathProbeKernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, n, (const float*)dx, (const float*)dy, dout.get());
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-	return RTX_OK;
-}
-
-int rtx_vec_probe(int device, int op, uint32_t n, const float* a, const float* b, float ior, float* out)
-{
-	if (!a || !out || op < 0 || op > 3 || (op < 3 && !b)) return fail(RTX_ERR_ARG, "bad argument");
-	int cnt = 0;
-	if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(RTX_ERR_NO_DEVICE, "no HIP device visible");
-	HIPCHK(hipSetDevice(device));
-	DevArray<float> da, db, dout;
-	const size_t bytes = (size_t)n * 3 * sizeof(float);
-	HIPCHK(da.reserve((size_t)n * 3)); HIPCHK(dout.reserve((size_t)n * 3));
-	HIPCHK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
-	if (b) { HIPCHK(db.reserve((size_t)n * 3)); HIPCHK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); }
-	hipLaunchKernelGGL(rtxVecProbeKernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, n, (const float*)da, (const float*)db, ior, dout.get());
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-	return RTX_OK;
-}
-
-} // extern "C"
+// the math probes of include/rtx_debug.h (uses fail / HIPCHK above)
+#include "rtx_probes.hip"
 
 // multi-GPU: RCCL communicator + frame gather (uses fail / HIPCHK above)
 #include "rtx_comm.hip"

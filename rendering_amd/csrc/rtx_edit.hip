@@ -27,7 +27,7 @@ int editBegin(rtx_scene* s, void* stream)
 	return RTX_OK;
 }
 
-// The spheres' and planes' share of the derived state, from the current descriptions (analyticEstimate, rtx_api.hip).
+// The spheres' and planes' share of the derived state, from the current descriptions (analyticEstimate, rtx_upload.hip).
 int refreshAnalytic(rtx_scene* s)
 {
 	const std::vector<float> sb = analyticEstimate(s, s->objectDescs.data(), s->objectDescs.size());

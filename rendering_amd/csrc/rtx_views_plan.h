@@ -1,6 +1,6 @@
 // The work items of rtx_render_views (include/rtx_views.h): the 8x8 tiles of every view of a batch, numbered view after view
 // and row by row inside a view, and the record a kernel reads of a view.  Plain C++ that the host and the kernels both compile (rtx_views.hip,
-// rtx_api.hip), so that the map from an item to its view and tile exists once and can be checked without a GPU (rtx_views_plan_probe:
+// rtx_views_api.hip), so that the map from an item to its view and tile exists once and can be checked without a GPU (rtx_views_plan_probe:
 // tests/test_render_views_cpu.py).
 #pragma once
 #include <stdint.h>
