@@ -17,7 +17,7 @@ ROOT = os.path.dirname(HERE)
 LIB_RTX = os.path.join(HERE, "librtx_hip.so")
 LIB_HOST = os.path.join(HERE, "librendering_host.so")
 
-__all__ = ["load", "Scene", "Comm", "RtxError", "device_count", "math_probe", "gather_plan", "exported_symbols", "sphere_directions", "cube_cameras"]
+__all__ = ["load", "Scene", "Comm", "RtxError", "device_count", "math_probe", "gather_plan", "exported_symbols", "sphere_directions", "cube_cameras", "decode_texels"]
 
 
 class RtxError(RuntimeError):
@@ -88,6 +88,16 @@ RTX_VIEWS_SYMBOLS = ["rtx_render_views"]
 
 # the extension of include/rtx_views_aov.h: first-hit buffers and primary rays of many views in one call (not part of the drop-in boundary)
 RTX_VIEWS_AOV_SYMBOLS = ["rtx_render_views_aov"]
+
+# the extension of include/rtx_texture.h: texture maps and skybox of a live scene replaced from device memory (not part of the drop-in boundary)
+RTX_TEXTURE_SYMBOLS = ["rtx_scene_set_map", "rtx_scene_set_sky", "rtx_scene_write_texels", "rtx_scene_texture_info"]
+TEXTURE_KINDS = {"diffuse": 0, "normal": 1, "specular": 2, "sky": 3}      # RTX_TEX_*
+TEXELS_STORED, TEXELS_RGB8 = 0, 1                                          # RTX_TEXELS_*
+
+
+class RtxTexels(C.Structure):
+    """rtx_texels (include/rtx_texture.h)"""
+    _fields_ = [("format", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32), ("data_dev", C.c_void_p), ("row_pitch", C.c_int64)]
 
 
 class MeshTopology(C.Structure):
@@ -337,6 +347,17 @@ def load():
     host.rah_euler_matrix.argtypes = [vp, vp]
     host.rah_euler_matrix.restype = None
     host.rah_mesh_pose.argtypes = [vp, i32, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    if hasattr(rtx, "rtx_scene_set_map"):      # (a library without them is reported by exported_symbols)
+        rtx.rtx_scene_set_map.argtypes = [vp, u32, C.c_int32, C.POINTER(RtxTexels), vp]
+        rtx.rtx_scene_set_sky.argtypes = [vp, C.POINTER(RtxTexels), vp]
+        rtx.rtx_scene_write_texels.argtypes = [vp, C.c_int32, u32, u32, u32, C.POINTER(RtxTexels), vp]
+        rtx.rtx_scene_texture_info.argtypes = [vp, C.c_int32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp)]
+        host.rah_decode_texels.argtypes = [i32, vp, C.c_longlong, vp]
+        host.rah_scene_has_gpu.argtypes = [vp]
+        host.rah_mesh_set_map.argtypes = [vp, i32, i32, C.POINTER(RtxTexels), i32, vp]
+        host.rah_scene_set_sky.argtypes = [vp, C.POINTER(RtxTexels), i32, vp]
+        host.rah_write_texels.argtypes = [vp, i32, i32, u32, u32, C.POINTER(RtxTexels), i32, vp]
+        host.rah_texture.argtypes = [vp, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, i32, vp]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -344,7 +365,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS + RTX_TEXTURE_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -371,6 +392,23 @@ def live_device_memory():
     n, b = C.c_size_t(0), C.c_size_t(0)
     _check(rtx.rtx_live_device_memory(C.byref(n), C.byref(b)), "rtx_live_device_memory")
     return n.value, b.value
+
+
+def decode_texels(kind, rgb8):
+    """The loaders' texel arithmetic on the host (rah_decode_texels): uint8 (..., 3) texels, R G B as the BMP loader returns them, into float32
+    (..., 3) -- (...) for "specular" -- as a map of `kind` ("diffuse", "normal", "specular", "sky") stores them: byte / 256; for a normal map
+    Vec3f(c.x*2-1, -(c.y*2-1), c.z).normalize(); for a specular map (c.x+c.y+c.z)/3."""
+    _, host = load()
+    if kind not in TEXTURE_KINDS:
+        raise ValueError("decode_texels: unknown kind %r (%s)" % (kind, ", ".join(TEXTURE_KINDS)))
+    a = np.asarray(rgb8)
+    if a.dtype != np.uint8 or a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("decode_texels: rgb8 must be uint8 (..., 3), got %s %s" % (a.dtype, a.shape))
+    a = np.ascontiguousarray(a)
+    out = np.zeros(a.shape[:-1] if kind == "specular" else a.shape, np.float32)
+    if host.rah_decode_texels(TEXTURE_KINDS[kind], _np_ptr(a), a.size // 3, _np_ptr(out)) != 0:
+        raise RtxError("decode_texels: %s" % kind)
+    return out
 
 
 def _np_ptr(a):
@@ -1719,6 +1757,179 @@ class Scene:
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)
         if self.host.rah_mesh_set_vertices(self.h, index, p, c["n_pos"], n, c["n_nrm"] if normals is not None else 0, int(p_dev), st) != 0:
             raise RtxError("set_vertices: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    # ---- texture maps and skybox (include/rtx_texture.h) -----------------------------------------
+    def has_gpu(self):
+        """True once the scene has been uploaded (gpu(), or any render or query); until then edits change the host's scene alone."""
+        return bool(self.host.rah_scene_has_gpu(self.h))
+
+    def _texels(self, who, kind, image, top_down):
+        """(RtxTexels, in device memory?, what keeps the data alive) of `image` for a map of `kind`: uint8 (H, W, 3) is RGB8, float32 (H, W, 3)
+        -- (H, W) for "specular" -- the stored texels; numpy or torch.  A tensor on the scene's device is used in place while the scene is
+        uploaded; anything else is handed over in host memory.  top_down: row 0 of `image` is the map's last row."""
+        a = image
+        on_device = False
+        if not isinstance(a, np.ndarray):
+            try:
+                import torch
+            except Exception:
+                torch = None
+            if torch is None or not isinstance(a, torch.Tensor):
+                raise ValueError("%s: image must be a numpy array or a torch tensor, got %s" % (who, type(a).__name__))
+            if a.dtype not in (torch.uint8, torch.float32):
+                raise ValueError("%s: image must be uint8 or float32, got %s" % (who, a.dtype))
+            if a.device.type == "cuda":
+                if (a.device.index if a.device.index is not None else torch.cuda.current_device()) != self.device:
+                    raise ValueError("%s: image must be on cuda:%d, the scene's device, or on the host, got %s" % (who, self.device, a.device))
+                on_device = True
+            elif a.device.type != "cpu":
+                raise ValueError("%s: image must be on cuda:%d or on the host, got %s" % (who, self.device, a.device))
+            rgb8 = a.dtype == torch.uint8
+        else:
+            if a.dtype not in (np.uint8, np.float32):
+                raise ValueError("%s: image must be uint8 or float32, got %s" % (who, a.dtype))
+            rgb8 = a.dtype == np.uint8
+        shape = tuple(a.shape)
+        want = (2,) if (kind == "specular" and not rgb8) else (3,)
+        if len(shape) not in want or (len(shape) == 3 and shape[2] != 3):
+            raise ValueError("%s: a %s %s image must have shape %s, got %s" % (who, "uint8" if rgb8 else "float32", kind,
+                                                                                 "(H, W)" if want == (2,) else "(H, W, 3)", shape))
+        if on_device and not self.has_gpu():
+            a, on_device = a.cpu(), False
+        # (rows that are packed go over as they lie, whatever the step from row to row: a view of a wider image, a flipped one)
+        h, w = shape[0], shape[1]
+        item = 1 if rgb8 else 4
+        row = w * item * (3 if len(shape) == 3 else 1)
+        if on_device:
+            strides = tuple(s * item for s in a.stride())
+        else:
+            a = a if isinstance(a, np.ndarray) else a.numpy()
+            strides = a.strides
+        packed = h > 0 and w > 0 and strides[1:] == ((3 * item, item) if len(shape) == 3 else (item,)) and (h == 1 or abs(strides[0]) >= row)
+        if not packed:
+            a = a.contiguous() if on_device else np.ascontiguousarray(a)
+        pitch = strides[0] if packed and h > 1 else row
+        base = a.data_ptr() if on_device else a.ctypes.data
+        if top_down and h:
+            base, pitch = base + (h - 1) * pitch, -pitch
+        return RtxTexels(TEXELS_RGB8 if rgb8 else TEXELS_STORED, w, h, base, pitch), on_device, a
+
+    def _texel_stream(self, stream, on_device, keep):
+        """The stream pointer of a texture edit: `stream`, else torch's current stream of the scene's device while the scene is uploaded."""
+        if not self.has_gpu():
+            return None
+        import torch
+        if isinstance(stream, torch.cuda.Stream) and on_device:
+            keep.record_stream(stream)
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if stream is None else self._stream_ptr(stream)
+
+    @staticmethod
+    def _map_kind(who, kind):
+        if kind not in ("diffuse", "normal", "specular"):
+            raise ValueError("%s: unknown kind %r (diffuse, normal, specular)" % (who, kind))
+        return TEXTURE_KINDS[kind]
+
+    def set_texture(self, index, kind, image, top_down=False, stream=None):
+        """Replaces map `kind` ("diffuse", "normal", "specular") of mesh `index` (scene-file order of the objects) as a whole: afterwards the
+        scene is, bit for bit, a fresh load of the scene file whose mesh names an image file holding `image`.  image: uint8 (H, W, 3) -- R G B
+        as a BMP holds them, decoded with the loader's arithmetic --, or float32 (H, W, 3), (H, W) for "specular": the texels as the scene stores
+        them (texture()); numpy or torch, any size; None removes the map.  Row 0 is the first stored row, the bottom row of a BMP;
+        top_down=True hands the image in from its last row.  A tensor on the scene's device is decoded on the device in place
+        (rtx_scene_set_map; the call waits for `stream`, None: torch's current stream).  ValueError: a bad index, an object that is not a mesh,
+        a wrong dtype, shape or device; RtxError: a refusal of the library (a normal map for a mesh without texture coordinates) -- the
+        scene is then as it was."""
+        self._mesh_counts("set_texture", index)
+        k = self._map_kind("set_texture", kind)
+        if image is None:
+            t, on_device, keep = None, False, None
+        else:
+            t, on_device, keep = self._texels("set_texture", kind, image, top_down)
+        st = self._texel_stream(stream, on_device, keep) if on_device else None
+        if self.host.rah_mesh_set_map(self.h, index, k, C.byref(t) if t is not None else None, int(on_device), st) != 0:
+            raise RtxError("set_texture: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    def write_texture(self, index, kind, image, x0=0, y0=0, top_down=False, stream=None):
+        """Writes `image` (as for set_texture) into map `kind` of mesh `index` at texel (x0, y0) -- the rectangle must lie inside the map, texels
+        outside it keep their bits.  With an uploaded scene the write is queued on `stream` (None: torch's current stream) and the host does
+        not wait (rtx_scene_write_texels): renders queued on that stream before it see the old texels, later ones the new; a tensor on the
+        device must stay as it is until the stream has passed the write.  This is the per-frame path of a video texture."""
+        self._mesh_counts("write_texture", index)
+        k = self._map_kind("write_texture", kind)
+        self._write_texels("write_texture", k, kind, index, image, x0, y0, top_down, stream)
+
+    def _write_texels(self, who, k, kind, index, image, x0, y0, top_down, stream):
+        if image is None:
+            raise ValueError("%s: image is None" % who)
+        if int(x0) < 0 or int(y0) < 0:
+            raise ValueError("%s: x0 and y0 must not be negative, got %d, %d" % (who, x0, y0))
+        t, on_device, keep = self._texels(who, kind, image, top_down)
+        st = self._texel_stream(stream, on_device, keep)
+        if self.host.rah_write_texels(self.h, k, index, int(x0), int(y0), C.byref(t), int(on_device), st) != 0:
+            raise RtxError("%s: %s" % (who, self.host.rah_last_error().decode(errors="replace")))
+
+    def set_skybox(self, faces, top_down=False, stream=None):
+        """Replaces the six skybox faces (the order of the scene file's skyboxes= line) by six images of one size and one format, as for
+        set_texture's "diffuse"; None: the scene loses its skybox (refused while useSkybox is on).  A scene without a skybox gains one;
+        set_flag("useSkybox", 1) then shows it."""
+        if faces is None:
+            ts, on_device, keep = None, False, []
+        else:
+            faces = list(faces)
+            if len(faces) != 6:
+                raise ValueError("set_skybox: six faces are needed, got %d" % len(faces))
+            parts = [self._texels("set_skybox", "sky", f, top_down) for f in faces]
+            if len({p[1] for p in parts}) != 1:
+                raise ValueError("set_skybox: the six faces must all be on the device or all on the host")
+            if len({(p[0].format, p[0].width, p[0].height) for p in parts}) != 1:
+                raise ValueError("set_skybox: the six faces must share one size and one dtype")
+            ts, on_device, keep = (RtxTexels * 6)(*[p[0] for p in parts]), parts[0][1], [p[2] for p in parts]
+        st = None
+        if on_device:
+            for a in keep:
+                st = self._texel_stream(stream, on_device, a)
+        if self.host.rah_scene_set_sky(self.h, ts, int(on_device), st) != 0:
+            raise RtxError("set_skybox: %s" % self.host.rah_last_error().decode(errors="replace"))
+
+    def write_skybox(self, face, image, x0=0, y0=0, top_down=False, stream=None):
+        """write_texture for skybox face `face` (0..5)."""
+        if not 0 <= int(face) < 6:
+            raise ValueError("write_skybox: face %d out of range (0..5)" % face)
+        self._write_texels("write_skybox", TEXTURE_KINDS["sky"], "sky", int(face), image, x0, y0, top_down, stream)
+
+    def _texture(self, who, k, index, host=False):
+        w, h = C.c_int(0), C.c_int(0)
+        live = self.has_gpu() and not host
+        st = self._texel_stream(None, False, None)
+        # (with an uploaded scene the size is the device's; a queued write changes no size)
+        if self.host.rah_texture(self.h, k, index, C.byref(w), C.byref(h), None, 0, None) != 0:
+            raise RtxError("%s: %s" % (who, self.host.rah_last_error().decode(errors="replace")))
+        if not w.value or not h.value:
+            return None
+        shape = (h.value, w.value) if k == TEXTURE_KINDS["specular"] else (h.value, w.value, 3)
+        if live:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device="cuda:%d" % self.device)
+            rc = self.host.rah_texture(self.h, k, index, C.byref(w), C.byref(h), C.c_void_p(out.data_ptr()), 1, st)
+        else:
+            out = np.zeros(shape, np.float32)
+            rc = self.host.rah_texture(self.h, k, index, C.byref(w), C.byref(h), _np_ptr(out), 0, None)
+        if rc != 0:
+            raise RtxError("%s: %s" % (who, self.host.rah_last_error().decode(errors="replace")))
+        return out
+
+    def texture(self, index, kind, host=False):
+        """A float32 copy of map `kind` of mesh `index` as the scene stores it, (H, W, 3) -- (H, W) for "specular" --, row 0 the first stored
+        row: a tensor on the scene's device once the scene is uploaded (copied on torch's current stream, after the writes queued on it),
+        else a numpy array; None where the mesh has no such map.  host=True: always a numpy array, from the host's own copy of the map --
+        the one a later upload starts from --, which is first read back from the device where a write_texture has left it behind."""
+        self._mesh_counts("texture", index)
+        return self._texture("texture", self._map_kind("texture", kind), index, host)
+
+    def skybox_face(self, k, host=False):
+        """texture() for skybox face k (0..5); None for a scene without a skybox."""
+        if not 0 <= int(k) < 6:
+            raise ValueError("skybox_face: face %d out of range (0..5)" % k)
+        return self._texture("skybox_face", TEXTURE_KINDS["sky"], int(k), host)
 
     def deform_times(self):
         """Host wall ms of the stages of the last set_vertices: {kernels (placement and assembly on the device with their read-backs),

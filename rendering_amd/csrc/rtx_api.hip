@@ -1504,3 +1504,6 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 
 // deforming a mesh of a live scene from vertices on the device (include/rtx_deform.h; its kernels come after every other one)
 #include "rtx_deform.hip"
+
+// replacing maps and skybox of a live scene from device memory (include/rtx_texture.h; its kernels come last)
+#include "rtx_texture.hip"

@@ -48,6 +48,8 @@ struct rtx_scene {
 	// device allocations that live as long as the scene.  Their counted bytes, with the meshes', are the scene data resident in HBM
 	// (rtx_scene_bytes: nodes, leaf references, shading arrays, maps, skybox)
 	DevBag owned;
+	// the six skybox faces among them (their table is params.sky): what rtx_scene_set_sky replaces and rtx_scene_write_texels writes (rtx_texture.hip)
+	const float* skyFaces[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 	// the light records and the area lights' sample points: a bag of their own, replaced as a whole by rtx_scene_set_lights (rtx_edit.hip);
 	// the records as uploaded (points: device pointers)
 	DevBag lightsOwned;

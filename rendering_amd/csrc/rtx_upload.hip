@@ -255,6 +255,7 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 			HIPCHK(s->owned.upload(desc->sky[k], (size_t)desc->sky_w * desc->sky_h * 3, &faces[k]));
 		}
 		HIPCHK(s->owned.upload(faces, 6, &s->params.sky));
+		std::copy(faces, faces + 6, s->skyFaces);
 		s->params.skyW = desc->sky_w; s->params.skyH = desc->sky_h;
 	}
 	if ((rc = setView(s, &desc->view))) return rc;

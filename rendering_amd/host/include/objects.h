@@ -103,7 +103,16 @@ public:
 	bool diffuseMapLoaded = false; int diffuseMapWidth = 0, diffuseMapHeight = 0; std::vector<Vec3f> diffuseMap;
 	bool normalMapLoaded = false; int normalMapWidth = 0, normalMapHeight = 0; std::vector<Vec3f> normalMap;
 	bool specularMapLoaded = false; int specularMapWidth = 0, specularMapHeight = 0; std::vector<float> specularMap;
+	// [kind]: the GPU scene's map has been written since this copy was made (Scene::writeTexels); read back before anything reads it (Scene::syncMaps)
+	bool mapStale[3] = { false, false, false };
 };
+
+// The loaders' texel arithmetic (objects.cpp:395-446, scene.cpp:292-311), each formula written once: n texels of 3 bytes, R G B as loadBMP
+// returns them, into 3 n floats -- n for the specular map.  kind: RTX_TEX_* of include/rtx_texture.h (0 diffuse, 1 normal, 2 specular, 3 sky).
+void decodeColourTexels(const unsigned char* rgb8, size_t n, float* out);      // byte / 256 (diffuse maps and skybox faces)
+void decodeNormalTexels(const unsigned char* rgb8, size_t n, float* out);      // Vec3f(c.x*2-1, -(c.y*2-1), c.z).normalize()
+void decodeSpecularTexels(const unsigned char* rgb8, size_t n, float* out);    // (c.x + c.y + c.z) / 3.0f
+bool decodeTexels(int kind, const unsigned char* rgb8, size_t n, float* out);  // false: no such kind
 
 // The values of an [object] block's keys (NULL: the key is absent).  The .scene parser applies every key=value line of a block through
 // applyObjectKeys, and so does Scene::addObject: an added object is the object its block loads.  material, name and the maps are the text

@@ -15,6 +15,7 @@
 struct rtx_scene;
 struct rtx_scene_desc;
 struct rtx_comm;
+struct rtx_texels;
 
 typedef struct { size_t x0, x1, y0, y1; } tileInfo;
 
@@ -101,6 +102,21 @@ public:
 	void setVertices(size_t index, const float* P, size_t nP, const float* N, size_t nN, bool onDevice, void* stream);
 	// host wall ms of the last setVertices: {the device call without the rebuild, the rebuild (rtx_scene_update_mesh), the host mirror, whole call}
 	double lastDeformMs[4] = { 0, 0, 0, 0 };
+	// Texture maps and skybox replaced or written into (include/rtx_texture.h; kind: RTX_TEX_*, index: the object, or the sky face).  The
+	// texels are a rtx_texels record whose data is in host memory, or with onDevice in device memory produced on `stream`.  With a live GPU
+	// scene the device decodes them (host texels go up as they are, never decoded) and this Scene's own copy of the map -- which a later
+	// flatten uploads -- is read back: at once after setMap / setSky, before the next reader after writeTexels, which is asynchronous
+	// (mapStale, skyStale; syncMaps).  Without one the edit is decoded into the host copy by the loaders' functions (objects.h).  texels ==
+	// NULL removes the map / the skybox.  Refused, the scene as it was: a bad index, kind or record, an object that is no mesh, a normal
+	// map for a mesh without texture coordinates, a rectangle outside the map, removing the skybox while useSkybox is on.
+	void setMap(size_t index, int kind, const rtx_texels* texels, bool onDevice, void* stream);
+	void setSky(const rtx_texels* faces6, bool onDevice, void* stream);
+	void writeTexels(int kind, size_t index, uint32_t x0, uint32_t y0, const rtx_texels& texels, bool onDevice, void* stream);
+	// the host copy, current: size and texels (NULL where there is none)
+	const float* texture(int kind, size_t index, int& width, int& height);
+	void syncMaps();
+	bool skyStale = false;
+	bool hasGpu() const { return gpu_ != nullptr; }
 	void syncTrees();                          // meshes moved on the GPU: their `ac` read back from the device (done by every reader of `ac`)
 	// host wall ms of the last moveObject: {placement (Mesh::place), upload of the triangles, rtx_scene_set_object, rtx_scene_update_mesh}
 	double lastMoveMs[4] = { 0, 0, 0, 0 };

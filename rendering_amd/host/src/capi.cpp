@@ -5,6 +5,8 @@
 
 #include "../../../include/rtx.h"
 #include "../../../include/rtx_views.h"
+#include "../../../include/rtx_texture.h"
+#include <hip/hip_runtime_api.h>
 #include "scene.h"
 #include "stats.h"
 #include "util.h"
@@ -313,6 +315,78 @@ int rah_mesh_set_vertices(void* h, int obj, const float* P, long long nP, const 
 	return guarded<int>(-1, [&] {
 		if (obj < 0 || nP < 0 || nN < 0) { noteError("setVertices: bad index or count"); LOG_ERROR(); }
 		((Scene*)h)->setVertices((size_t)obj, P, (size_t)nP, N, (size_t)nN, onDevice != 0, stream);
+		return 0;
+	});
+}
+
+// The loaders' texel arithmetic (objects.h, decodeTexels): n RGB8 texels into 3 n floats, n for RTX_TEX_SPECULAR.  -1: no such kind.
+int rah_decode_texels(int kind, const unsigned char* rgb8, long long n, float* out)
+{
+	if (n < 0 || (n && (!rgb8 || !out))) return -1;
+	return decodeTexels(kind, rgb8, (size_t)n, out) ? 0 : -1;
+}
+
+// 1: the scene has been uploaded (Scene::gpu has run), 0: it lives on the host alone
+int rah_scene_has_gpu(void* h) { return ((Scene*)h)->hasGpu() ? 1 : 0; }
+
+// Map `kind` (RTX_TEX_DIFFUSE / NORMAL / SPECULAR) of mesh `obj` replaced by `texels` (Scene::setMap; NULL: removed); onDevice: its data is in
+// device memory, produced on `stream`.  0, or -1 with rah_last_error: the scene is then as it was.
+int rah_mesh_set_map(void* h, int obj, int kind, const rtx_texels* texels, int onDevice, void* stream)
+{
+	return guarded<int>(-1, [&] {
+		if (obj < 0) { noteError("setMap: object index out of range"); LOG_ERROR(); }
+		((Scene*)h)->setMap((size_t)obj, kind, texels, onDevice != 0, stream);
+		return 0;
+	});
+}
+
+// The six skybox faces replaced (Scene::setSky; NULL: the scene loses its skybox).  0, or -1 with rah_last_error.
+int rah_scene_set_sky(void* h, const rtx_texels* faces6, int onDevice, void* stream)
+{
+	return guarded<int>(-1, [&] {
+		((Scene*)h)->setSky(faces6, onDevice != 0, stream);
+		return 0;
+	});
+}
+
+// A rectangle of texels written at (x0, y0) into map `kind` of mesh `index`, or into sky face `index` for RTX_TEX_SKY (Scene::writeTexels):
+// queued on `stream` with a live GPU scene.  0, or -1 with rah_last_error.
+int rah_write_texels(void* h, int kind, int index, unsigned x0, unsigned y0, const rtx_texels* texels, int onDevice, void* stream)
+{
+	return guarded<int>(-1, [&] {
+		if (index < 0 || !texels) { noteError("writeTexels: bad index or texels"); LOG_ERROR(); }
+		((Scene*)h)->writeTexels(kind, (size_t)index, x0, y0, *texels, onDevice != 0, stream);
+		return 0;
+	});
+}
+
+// Size of map `kind` of mesh `index` (of sky face `index`), 0 x 0 where there is none, and with `out` its stored texels: into host memory from
+// the host's copy (read back first where a write left it behind), or with outOnDevice into device memory by a copy queued on `stream`
+// (a live GPU scene only).  0, or -1 with rah_last_error.
+int rah_texture(void* h, int kind, int index, int* width, int* height, float* out, int outOnDevice, void* stream)
+{
+	return guarded<int>(-1, [&] {
+		Scene* s = (Scene*)h;
+		if (index < 0) { noteError("texture: index out of range"); LOG_ERROR(); }
+		if (!outOnDevice && (out || !s->hasGpu())) {
+			const float* p = s->texture(kind, (size_t)index, *width, *height);
+			if (out && p) memcpy(out, p, (size_t)*width * *height * (kind == RTX_TEX_SPECULAR ? 1 : 3) * sizeof(float));
+			return 0;
+		}
+		if (!s->hasGpu()) { noteError("texture: a device copy without a GPU scene"); LOG_ERROR(); }
+		uint32_t devIndex = (uint32_t)index;
+		if (kind != RTX_TEX_SKY) {
+			if (!meshOf(h, index)) { noteError("texture: no such mesh"); LOG_ERROR(); }
+			devIndex = 0;
+			for (int i = 0; i < index; ++i) devIndex += s->objects[i]->objectType == ObjectType::Mesh;
+		}
+		uint32_t w = 0, ht = 0;
+		const float* dev = nullptr;
+		if (rtx_scene_texture_info(s->gpu(), kind, devIndex, &w, &ht, &dev) != RTX_OK) { noteError(rtx_last_error()); LOG_ERROR(); }
+		*width = (int)w; *height = (int)ht;
+		if (dev && out && hipMemcpyAsync(out, dev, (size_t)w * ht * (kind == RTX_TEX_SPECULAR ? 1 : 3) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+			noteError("texture: the copy could not be queued"); LOG_ERROR();
+		}
 		return 0;
 	});
 }

@@ -399,14 +399,48 @@ struct Pixels {
 	int w = 0, h = 0;
 	std::unique_ptr<unsigned char[]> data;
 	explicit Pixels(const std::string& fn) { data.reset(loadBMP(fn.c_str(), w, h)); }
-	Vec3f at(size_t i) const
-	{
-		float r = data[i * 3], g = data[i * 3 + 1], b = data[i * 3 + 2];
-		r /= 256; g /= 256; b /= 256;
-		return Vec3f(r, g, b);
-	}
 	size_t count() const { return (size_t)w * h; }
 };
+Vec3f texelColour(const unsigned char* p)
+{
+	float r = p[0], g = p[1], b = p[2];
+	r /= 256; g /= 256; b /= 256;
+	return Vec3f(r, g, b);
+}
+}
+
+void decodeColourTexels(const unsigned char* rgb8, size_t n, float* out)
+{
+	for (size_t i = 0; i < n; ++i) {
+		const Vec3f c = texelColour(rgb8 + i * 3);
+		out[i * 3] = c.x; out[i * 3 + 1] = c.y; out[i * 3 + 2] = c.z;
+	}
+}
+
+void decodeNormalTexels(const unsigned char* rgb8, size_t n, float* out)
+{
+	for (size_t i = 0; i < n; ++i) {
+		const Vec3f c = texelColour(rgb8 + i * 3);
+		const Vec3f v = Vec3f(c.x * 2 - 1, -(c.y * 2 - 1), c.z).normalize();     // objects.cpp:433
+		out[i * 3] = v.x; out[i * 3 + 1] = v.y; out[i * 3 + 2] = v.z;
+	}
+}
+
+void decodeSpecularTexels(const unsigned char* rgb8, size_t n, float* out)
+{
+	for (size_t i = 0; i < n; ++i) {
+		const Vec3f c = texelColour(rgb8 + i * 3);
+		out[i] = (c.x + c.y + c.z) / 3.0f;
+	}
+}
+
+bool decodeTexels(int kind, const unsigned char* rgb8, size_t n, float* out)
+{
+	if (kind == 0 || kind == 3) decodeColourTexels(rgb8, n, out);
+	else if (kind == 1) decodeNormalTexels(rgb8, n, out);
+	else if (kind == 2) decodeSpecularTexels(rgb8, n, out);
+	else return false;
+	return true;
 }
 
 bool Mesh::loadDiffuseMap(const std::string& filename)
@@ -415,7 +449,7 @@ bool Mesh::loadDiffuseMap(const std::string& filename)
 	Pixels px(filename);
 	diffuseMapWidth = px.w; diffuseMapHeight = px.h;
 	diffuseMap.resize(px.count());
-	for (size_t i = 0; i < px.count(); ++i) diffuseMap[i] = px.at(i);
+	if (px.count()) decodeColourTexels(px.data.get(), px.count(), &diffuseMap[0].x);      // (Vec3f is 3 packed floats)
 	return true;
 }
 
@@ -425,10 +459,7 @@ bool Mesh::loadNormalMap(const std::string& filename)
 	Pixels px(filename);
 	normalMapWidth = px.w; normalMapHeight = px.h;
 	normalMap.resize(px.count());
-	for (size_t i = 0; i < px.count(); ++i) {
-		const Vec3f c = px.at(i);
-		normalMap[i] = Vec3f(c.x * 2 - 1, -(c.y * 2 - 1), c.z).normalize();     // objects.cpp:433
-	}
+	if (px.count()) decodeNormalTexels(px.data.get(), px.count(), &normalMap[0].x);
 	return true;
 }
 
@@ -438,10 +469,7 @@ bool Mesh::loadSpecularMap(const std::string& filename)
 	Pixels px(filename);
 	specularMapWidth = px.w; specularMapHeight = px.h;
 	specularMap.resize(px.count());
-	for (size_t i = 0; i < px.count(); ++i) {
-		const Vec3f c = px.at(i);
-		specularMap[i] = (c.x + c.y + c.z) / 3.0f;
-	}
+	if (px.count()) decodeSpecularTexels(px.data.get(), px.count(), specularMap.data());
 	return true;
 }
 

@@ -18,6 +18,7 @@
 #include "../../../include/rtx_debug.h"
 #include "../../../include/rtx_scene_edit.h"
 #include "../../../include/rtx_deform.h"
+#include "../../../include/rtx_texture.h"
 #include "stats.h"
 #include "timer.h"
 #include "util.h"
@@ -302,11 +303,7 @@ void Scene::loadSkybox()
 		}
 		skyboxWidth = w; skyboxHeight = h;
 		skyboxes[k].resize((size_t)w * h);
-		for (size_t i = 0; i < skyboxes[k].size(); ++i) {
-			float r = px[i * 3], g = px[i * 3 + 1], b = px[i * 3 + 2];
-			r /= 256; g /= 256; b /= 256;                  // scene.cpp:354
-			skyboxes[k][i] = Vec3f(r, g, b);
-		}
+		if (!skyboxes[k].empty()) decodeColourTexels(px.get(), skyboxes[k].size(), &skyboxes[k][0].x);      // scene.cpp:354
 	}
 }
 
@@ -447,6 +444,7 @@ rtx_mesh flattenMesh(const Mesh& m, FlatScene::MeshArrays& A, bool withTree)
 FlatScene* flattenScene(Scene& sc)
 {
 	sc.syncTrees();
+	sc.syncMaps();
 	auto* fs = new FlatScene;
 	fillView(sc, fs->desc.view);
 	for (auto& op : sc.objects) {
@@ -791,6 +789,239 @@ void Scene::setVertices(size_t index, const float* P, size_t nP, const float* N,
 	if (N) m.topologyNormalsStale = true;
 	lastDeformMs[2] = tMirrored - tStart;
 	lastDeformMs[3] = now() - tStart;
+}
+
+// ------------------------------------------------------------------------------------------------
+// texture maps and skybox replaced or written into (scene.h; include/rtx_texture.h)
+// ------------------------------------------------------------------------------------------------
+namespace {
+[[noreturn]] void refuse(const std::string& what)
+{
+	noteError(what);
+	LOG_ERROR();
+}
+
+uint32_t texChannels(int kind) { return kind == RTX_TEX_SPECULAR ? 1u : 3u; }
+size_t texRowBytes(int kind, const rtx_texels& t) { return (size_t)t.width * (t.format == RTX_TEXELS_STORED ? texChannels(kind) * 4u : 3u); }
+uint64_t texPitch(const rtx_texels& t) { return t.row_pitch < 0 ? 0ull - (uint64_t)t.row_pitch : (uint64_t)t.row_pitch; }
+
+// the checks of the library (rtx_texture.hip), for the edits that stay on the host
+void checkTexels(const char* who, int kind, const rtx_texels& t)
+{
+	const std::string w = std::string(who) + ": ";
+	if (t.format != RTX_TEXELS_STORED && t.format != RTX_TEXELS_RGB8) refuse(w + "format is no RTX_TEXELS_*");
+	if (!t.width || !t.height) refuse(w + "a zero width or height");
+	if (!t.data_dev) refuse(w + "the texels are NULL");
+	if (texPitch(t) < texRowBytes(kind, t)) refuse(w + "|row_pitch| is below one row");
+}
+
+// a checked rectangle of texels in host memory into the host map `dst` of dstW texels per row, at (x0, y0): stored texels as they are,
+// bytes through the loaders' functions (objects.h)
+void applyTexels(int kind, const rtx_texels& t, float* dst, uint32_t dstW, uint32_t x0, uint32_t y0)
+{
+	const uint32_t ch = texChannels(kind);
+	for (uint32_t r = 0; r < t.height; ++r) {
+		const unsigned char* src = (const unsigned char*)t.data_dev + (int64_t)r * t.row_pitch;
+		float* out = dst + ((size_t)(y0 + r) * dstW + x0) * ch;
+		if (t.format == RTX_TEXELS_STORED) memcpy(out, src, (size_t)t.width * ch * sizeof(float));
+		else decodeTexels(kind, src, t.width, out);
+	}
+}
+
+// checked texels of host memory in device memory, as they are: the bytes from the lowest row's first to the highest row's last, the record
+// pointing into them with the caller's pitch.  Freed with the object (hipFree waits for the device: a queued kernel has read them by then).
+struct StagedTexels {
+	rtx_texels t{};
+	void* dev = nullptr;
+	StagedTexels() = default;
+	StagedTexels(const StagedTexels&) = delete;
+	~StagedTexels() { if (dev) (void)hipFree(dev); }
+	void stage(int kind, const rtx_texels& in)
+	{
+		const size_t span = (size_t)(in.height - 1) * texPitch(in) + texRowBytes(kind, in);
+		const unsigned char* first = (const unsigned char*)in.data_dev + (in.row_pitch < 0 ? (int64_t)(in.height - 1) * in.row_pitch : 0);
+		hipCheck(hipMalloc(&dev, span), "hipMalloc (texels)");
+		hipCheck(hipMemcpy(dev, first, span, hipMemcpyHostToDevice), "hipMemcpy (texels)");
+		t = in;
+		t.data_dev = (const unsigned char*)dev + ((const unsigned char*)in.data_dev - first);
+	}
+};
+
+// the host copy of map `kind` of a mesh
+float* mapData(Mesh& m, int kind)
+{
+	if (kind == RTX_TEX_DIFFUSE) return m.diffuseMap.empty() ? nullptr : &m.diffuseMap[0].x;
+	if (kind == RTX_TEX_NORMAL) return m.normalMap.empty() ? nullptr : &m.normalMap[0].x;
+	return m.specularMap.empty() ? nullptr : m.specularMap.data();
+}
+void mapSize(const Mesh& m, int kind, bool& loaded, int& w, int& h)
+{
+	if (kind == RTX_TEX_DIFFUSE) { loaded = m.diffuseMapLoaded; w = m.diffuseMapWidth; h = m.diffuseMapHeight; }
+	else if (kind == RTX_TEX_NORMAL) { loaded = m.normalMapLoaded; w = m.normalMapWidth; h = m.normalMapHeight; }
+	else { loaded = m.specularMapLoaded; w = m.specularMapWidth; h = m.specularMapHeight; }
+	if (!loaded) w = h = 0;
+}
+// ... of another size (w = h = 0: the mesh has no such map), its texels unset
+void mapResize(Mesh& m, int kind, int w, int h)
+{
+	const bool loaded = w > 0 && h > 0;
+	const size_t n = (size_t)w * h;
+	if (kind == RTX_TEX_DIFFUSE) { m.diffuseMapLoaded = loaded; m.diffuseMapWidth = w; m.diffuseMapHeight = h; m.diffuseMap.assign(n, Vec3f(0, 0, 0)); }
+	else if (kind == RTX_TEX_NORMAL) { m.normalMapLoaded = loaded; m.normalMapWidth = w; m.normalMapHeight = h; m.normalMap.assign(n, Vec3f(0, 0, 0)); }
+	else { m.specularMapLoaded = loaded; m.specularMapWidth = w; m.specularMapHeight = h; m.specularMap.assign(n, 0.0f); }
+}
+}
+
+void Scene::syncMaps()
+{
+	if (!gpu_) return;
+	bool any = skyStale;
+	for (auto& op : objects)
+		if (op->objectType == ObjectType::Mesh) { const auto& m = static_cast<const Mesh&>(*op); any = any || m.mapStale[0] || m.mapStale[1] || m.mapStale[2]; }
+	if (!any) return;
+	hipCheck(hipSetDevice(device), "hipSetDevice");
+	hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");      // (a write may be queued on any stream)
+	uint32_t meshIndex = 0;
+	for (auto& op : objects) {
+		if (op->objectType != ObjectType::Mesh) continue;
+		auto& m = static_cast<Mesh&>(*op);
+		const uint32_t mi = meshIndex++;
+		for (int kind = 0; kind < 3; ++kind) {
+			if (!m.mapStale[kind]) continue;
+			uint32_t w = 0, h = 0;
+			const float* dev = nullptr;
+			gpuCheck(rtx_scene_texture_info(gpu_, kind, mi, &w, &h, &dev), "rtx_scene_texture_info");
+			mapResize(m, kind, (int)w, (int)h);
+			if (dev) hipCheck(hipMemcpy(mapData(m, kind), dev, (size_t)w * h * texChannels(kind) * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy (map)");
+			m.mapStale[kind] = false;
+		}
+	}
+	if (skyStale) {
+		for (uint32_t k = 0; k < 6; ++k) {
+			uint32_t w = 0, h = 0;
+			const float* dev = nullptr;
+			gpuCheck(rtx_scene_texture_info(gpu_, RTX_TEX_SKY, k, &w, &h, &dev), "rtx_scene_texture_info");
+			skyboxWidth = (int)w; skyboxHeight = (int)h;
+			skyboxes[k].assign((size_t)w * h, Vec3f(0, 0, 0));
+			if (dev) hipCheck(hipMemcpy(&skyboxes[k][0].x, dev, (size_t)w * h * 3 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy (sky face)");
+		}
+		skyStale = false;
+	}
+}
+
+void Scene::setMap(size_t index, int kind, const rtx_texels* t, bool onDevice, void* stream)
+{
+	if (index >= objects.size()) refuse("setMap: object index out of range");
+	if (objects[index]->objectType != ObjectType::Mesh) refuse("setMap: object " + std::to_string(index) + " is not a mesh");
+	if (kind < RTX_TEX_DIFFUSE || kind > RTX_TEX_SPECULAR) refuse("setMap: kind is no map of a mesh");
+	auto& m = static_cast<Mesh&>(*objects[index]);
+	if (t) checkTexels("setMap", kind, *t);
+	// (the load's rule "normal map without tangents": the tangents come from the texture coordinates)
+	if (t && kind == RTX_TEX_NORMAL && m.objT.empty()) refuse("setMap: normal map without tangents (the mesh's OBJ has no texture coordinates)");
+	if (!gpu_) {
+		if (onDevice) refuse("setMap: texels in device memory without a GPU scene");
+		if (!t) { mapResize(m, kind, 0, 0); return; }
+		std::vector<float> fresh((size_t)t->width * t->height * texChannels(kind));
+		applyTexels(kind, *t, fresh.data(), t->width, 0, 0);
+		mapResize(m, kind, (int)t->width, (int)t->height);
+		memcpy(mapData(m, kind), fresh.data(), fresh.size() * sizeof(float));
+		return;
+	}
+	uint32_t meshIndex = 0;
+	for (size_t i = 0; i < index; ++i) meshIndex += objects[i]->objectType == ObjectType::Mesh;
+	hipCheck(hipSetDevice(device), "hipSetDevice");
+	StagedTexels staged;
+	if (t && !onDevice) { staged.stage(kind, *t); t = &staged.t; }
+	gpuCheck(rtx_scene_set_map(gpu_, meshIndex, kind, t, onDevice ? stream : nullptr), "rtx_scene_set_map");
+	// the decoded map, read back once
+	m.mapStale[kind] = true;
+	syncMaps();
+}
+
+void Scene::setSky(const rtx_texels* faces, bool onDevice, void* stream)
+{
+	if (!faces && skyboxOn()) refuse("setSky: the skybox cannot be removed while useSkybox is on");
+	for (int k = 0; faces && k < 6; ++k) {
+		checkTexels("setSky", RTX_TEX_SKY, faces[k]);
+		if (faces[k].width != faces[0].width || faces[k].height != faces[0].height || faces[k].format != faces[0].format)
+			refuse("setSky: the six faces must share one size and one format");
+	}
+	if (!gpu_) {
+		if (onDevice) refuse("setSky: texels in device memory without a GPU scene");
+		std::vector<Vec3f> fresh[6];
+		for (int k = 0; faces && k < 6; ++k) {
+			fresh[k].assign((size_t)faces[k].width * faces[k].height, Vec3f(0, 0, 0));
+			applyTexels(RTX_TEX_SKY, faces[k], &fresh[k][0].x, faces[k].width, 0, 0);
+		}
+		for (int k = 0; k < 6; ++k) skyboxes[k].swap(fresh[k]);
+		skyboxWidth = faces ? (int)faces[0].width : 0; skyboxHeight = faces ? (int)faces[0].height : 0;
+		return;
+	}
+	hipCheck(hipSetDevice(device), "hipSetDevice");
+	if (viewDirty_) gpu();      // (the library refuses by the flags of the view it holds: a useSkybox switched off since goes up first)
+	StagedTexels staged[6];
+	rtx_texels dev[6];
+	for (int k = 0; faces && k < 6; ++k) {
+		dev[k] = faces[k];
+		if (!onDevice) { staged[k].stage(RTX_TEX_SKY, faces[k]); dev[k] = staged[k].t; }
+	}
+	gpuCheck(rtx_scene_set_sky(gpu_, faces ? dev : nullptr, onDevice ? stream : nullptr), "rtx_scene_set_sky");
+	skyStale = true;
+	syncMaps();
+}
+
+void Scene::writeTexels(int kind, size_t index, uint32_t x0, uint32_t y0, const rtx_texels& t, bool onDevice, void* stream)
+{
+	if (kind < RTX_TEX_DIFFUSE || kind > RTX_TEX_SKY) refuse("writeTexels: kind is no RTX_TEX_*");
+	Mesh* m = nullptr;
+	int w = 0, h = 0;
+	if (kind == RTX_TEX_SKY) {
+		if (index >= 6) refuse("writeTexels: sky face out of range");
+		w = skyboxWidth; h = skyboxHeight;
+	}
+	else {
+		if (index >= objects.size()) refuse("writeTexels: object index out of range");
+		if (objects[index]->objectType != ObjectType::Mesh) refuse("writeTexels: object " + std::to_string(index) + " is not a mesh");
+		m = static_cast<Mesh*>(objects[index].get());
+		bool loaded = false;
+		mapSize(*m, kind, loaded, w, h);
+	}
+	// (the sizes of the host copy are those of the device's map: only writeTexels leaves the copy behind, and it changes no size)
+	if (w <= 0 || h <= 0) refuse("writeTexels: there is no such map");
+	checkTexels("writeTexels", kind, t);
+	if (x0 >= (uint32_t)w || y0 >= (uint32_t)h || t.width > (uint32_t)w - x0 || t.height > (uint32_t)h - y0) refuse("writeTexels: the rectangle does not lie inside the map");
+	if (!gpu_) {
+		if (onDevice) refuse("writeTexels: texels in device memory without a GPU scene");
+		applyTexels(kind, t, kind == RTX_TEX_SKY ? &skyboxes[index][0].x : mapData(*m, kind), (uint32_t)w, x0, y0);
+		return;
+	}
+	uint32_t devIndex = (uint32_t)index;
+	if (m) { devIndex = 0; for (size_t i = 0; i < index; ++i) devIndex += objects[i]->objectType == ObjectType::Mesh; }
+	hipCheck(hipSetDevice(device), "hipSetDevice");
+	StagedTexels staged;
+	const rtx_texels* dt = &t;
+	if (!onDevice) { staged.stage(kind, t); dt = &staged.t; }
+	gpuCheck(rtx_scene_write_texels(gpu_, kind, devIndex, x0, y0, dt, stream), "rtx_scene_write_texels");
+	if (m) m->mapStale[kind] = true; else skyStale = true;
+}
+
+const float* Scene::texture(int kind, size_t index, int& width, int& height)
+{
+	width = height = 0;
+	if (kind < RTX_TEX_DIFFUSE || kind > RTX_TEX_SKY) refuse("texture: kind is no RTX_TEX_*");
+	syncMaps();
+	if (kind == RTX_TEX_SKY) {
+		if (index >= 6) refuse("texture: sky face out of range");
+		if (skyboxWidth <= 0 || skyboxes[index].empty()) return nullptr;
+		width = skyboxWidth; height = skyboxHeight;
+		return &skyboxes[index][0].x;
+	}
+	if (index >= objects.size()) refuse("texture: object index out of range");
+	if (objects[index]->objectType != ObjectType::Mesh) refuse("texture: object " + std::to_string(index) + " is not a mesh");
+	auto& m = static_cast<Mesh&>(*objects[index]);
+	bool loaded = false;
+	mapSize(m, kind, loaded, width, height);
+	return loaded ? mapData(m, kind) : nullptr;
 }
 
 // The lights as the device should hold them now: one rtx_scene_set_lights (nothing to do before the GPU scene exists: it is created
