@@ -1,7 +1,8 @@
 /* Direct light and ambient occlusion at caller-supplied surface points: the two questions the renderer spends most of its
  * rays on -- how much light reaches this point, how open is it -- for a caller who has points and no rays: vertices or lightmap texels to
  * bake, irradiance probes, particles, a G-buffer kept from rtx_render_aov or rtx_surface_rays.  No ray is traced to find the point, and
- * its normal is not looked up: P and N are used as given.  An extension of the C ABI in rtx.h. */
+ * its normal is not looked up: P and N are used as given.  The points of a mesh's lightmap texels are rtx_texel_points' (rtx_bake.h).
+ * An extension of the C ABI in rtx.h. */
 #ifndef RTX_POINTS_H
 #define RTX_POINTS_H
 #include "rtx_light.h"

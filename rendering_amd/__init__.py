@@ -94,6 +94,14 @@ RTX_TEXTURE_SYMBOLS = ["rtx_scene_set_map", "rtx_scene_set_sky", "rtx_scene_writ
 TEXTURE_KINDS = {"diffuse": 0, "normal": 1, "specular": 2, "sky": 3}      # RTX_TEX_*
 TEXELS_STORED, TEXELS_RGB8 = 0, 1                                          # RTX_TEXELS_*
 
+# the extension of include/rtx_bake.h: the surface points of a mesh's texels and the margin fill (not part of the drop-in boundary)
+RTX_BAKE_SYMBOLS = ["rtx_texel_points", "rtx_dilate_texels"]
+
+
+class TexelBuffers(C.Structure):
+    """rtx_texel_buffers (include/rtx_bake.h): three device pointers, any of them NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("points_dev", "tri_dev", "bary_dev")]
+
 
 class RtxTexels(C.Structure):
     """rtx_texels (include/rtx_texture.h)"""
@@ -358,6 +366,9 @@ def load():
         host.rah_scene_set_sky.argtypes = [vp, C.POINTER(RtxTexels), i32, vp]
         host.rah_write_texels.argtypes = [vp, i32, i32, u32, u32, C.POINTER(RtxTexels), i32, vp]
         host.rah_texture.argtypes = [vp, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, i32, vp]
+    if hasattr(rtx, "rtx_texel_points"):      # (a library without them is reported by exported_symbols)
+        rtx.rtx_texel_points.argtypes = [vp, u32, u32, u32, C.POINTER(TexelBuffers), vp]
+        rtx.rtx_dilate_texels.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -365,7 +376,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS + RTX_TEXTURE_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS + RTX_TEXTURE_SYMBOLS + RTX_BAKE_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -1930,6 +1941,83 @@ class Scene:
         if not 0 <= int(k) < 6:
             raise ValueError("skybox_face: face %d out of range (0..5)" % k)
         return self._texture("skybox_face", TEXTURE_KINDS["sky"], int(k), host)
+
+    # ---- texel points of a mesh's UV layout (include/rtx_bake.h) ---------------------------------
+    def _bake_size(self, who, index, width, height):
+        """(device mesh index, w, h) of a map over mesh `index`: the given size, else the size of the mesh's diffuse map."""
+        self._mesh_counts(who, index)
+        if (width is None) != (height is None):
+            raise ValueError("%s: width and height go together" % who)
+        if width is None:
+            w, h = C.c_int(0), C.c_int(0)
+            if self.host.rah_texture(self.h, TEXTURE_KINDS["diffuse"], index, C.byref(w), C.byref(h), None, 0, None) != 0:
+                raise RtxError("%s: %s" % (who, self.host.rah_last_error().decode(errors="replace")))
+            if not w.value or not h.value:
+                raise ValueError("%s: object %d has no diffuse map, and no size is given" % (who, index))
+            width, height = w.value, h.value
+        width, height = int(width), int(height)
+        if width < 1 or height < 1 or width * height > 0x7fffffff:
+            raise ValueError("%s: width and height must be positive, their product at most %d, got %d x %d" % (who, 0x7fffffff, width, height))
+        # (the device's meshes are the mesh objects in scene order)
+        mesh = sum(1 for i in range(index) if self.host.rah_object_type(self.h, i) == OBJECT_TYPES["mesh"])
+        return mesh, width, height
+
+    def texel_points(self, index, width=None, height=None, points=True, tri=True, bary=False, stream=None):
+        """rtx_texel_points: the surface point of every texel of a width x height map laid over mesh `index` (scene-file order of the objects,
+        as in set_texture) by its texture coordinates, on the device (include/rtx_bake.h: texel (i, j) covers the centre
+        ((i + .5) / width, (j + .5) / height); the lowest triangle index owns a shared texel).  The size defaults to the mesh's diffuse map.
+        Returns a dict of the channels asked for, new tensors on the scene's device: "points" float32 (height * width, 6) = {P xyz, N xyz},
+        what light_points, ao_points and radiance_points take; "tri" int32 (height, width), the owning triangle, -1 where no triangle covers
+        the centre (its point is all +0); "bary" float32 (height, width, 2).  Row 0 is the map's first stored row: an image computed from
+        the points goes into set_texture as it is.  Asynchronous on `stream`, which is handled as in trace_rays."""
+        import torch
+        if not (points or tri or bary):
+            raise ValueError("texel_points: nothing to compute (every channel is off)")
+        mesh, w, h = self._bake_size("texel_points", index, width, height)
+        g = self.gpu()
+        dev = torch.device("cuda", self.device)
+        alloc_on, st = _query_stream(stream, dev, ())
+        with torch.cuda.stream(alloc_on):
+            out = {}
+            if points:
+                out["points"] = torch.empty((h * w, 6), dtype=torch.float32, device=dev)
+            if tri:
+                out["tri"] = torch.empty((h, w), dtype=torch.int32, device=dev)
+            if bary:
+                out["bary"] = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
+        buf = TexelBuffers(*[out[k].data_ptr() if k in out else None for k in ("points", "tri", "bary")])
+        _check(self.rtx.rtx_texel_points(g, mesh, w, h, C.byref(buf), st), "rtx_texel_points")
+        return out
+
+    def dilate_texels(self, image, tri, passes=1, stream=None):
+        """rtx_dilate_texels: the margin around the charts, in place.  image: contiguous float32 tensor (H, W) or (H, W, C), C in 1 .. 4, on the
+        scene's device; tri: int32 (H, W) as texel_points returns it.  Per pass every texel with tri == -1 copies the first neighbour (left,
+        right, below, above, then the diagonals) that was covered or filled at the start of the pass, and becomes -2.  Returns `image`."""
+        import torch
+        _check_tensor("dilate_texels", "tri", tri, torch.int32, ("H", "W"), self.device)
+        h, w = tri.shape
+        if image is not None and isinstance(image, torch.Tensor) and image.dim() == 2:
+            _check_tensor("dilate_texels", "image", image, torch.float32, (h, w), self.device)
+            ch = 1
+        else:
+            _check_tensor("dilate_texels", "image", image, torch.float32, (h, w, "C"), self.device)
+            ch = image.shape[2]
+        if not 1 <= ch <= 4:
+            raise ValueError("dilate_texels: image must have 1 .. 4 channels, got %d" % ch)
+        if int(passes) < 0:
+            raise ValueError("dilate_texels: passes must not be negative, got %d" % passes)
+        _, st = _query_stream(stream, image.device, (image, tri))
+        if h and w and int(passes):
+            _check(self.rtx.rtx_dilate_texels(self.gpu(), w, h, ch, _ptr(image), _ptr(tri), int(passes), st), "rtx_dilate_texels")
+        return image
+
+    def bake_light(self, index, width=None, height=None, margin=2, stream=None):
+        """A lightmap of mesh `index`: light_points(texel_points(...)["points"], diffuse=True) as an image (height, width, 3), dilated
+        `margin` passes.  Returns (image, tri); set_texture(index, "diffuse", image) takes the image as it is."""
+        t = self.texel_points(index, width, height, points=True, tri=True, stream=stream)
+        h, w = t["tri"].shape
+        image = self.light_points(t["points"], diffuse=True, stream=stream)["diffuse"].reshape(h, w, 3)
+        return self.dilate_texels(image, t["tri"], margin, stream=stream), t["tri"]
 
     def deform_times(self):
         """Host wall ms of the stages of the last set_vertices: {kernels (placement and assembly on the device with their read-backs),

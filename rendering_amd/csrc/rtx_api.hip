@@ -1507,3 +1507,6 @@ int rtx_cast_rays(rtx_scene* s, uint32_t n, const float* rays, float* hits, floa
 
 // replacing maps and skybox of a live scene from device memory (include/rtx_texture.h; its kernels come last)
 #include "rtx_texture.hip"
+
+// texel points of a mesh's UV layout and the margin fill (include/rtx_bake.h; its kernels come last)
+#include "rtx_bake.hip"

@@ -146,6 +146,8 @@ int rtx_scene_update_mesh(rtx_scene* s, uint32_t mesh, const float* tri_pos_dev,
 	}
 	s->meshOwned[mesh].swap(owned);
 	owned.clear();      // (the old geometry)
+	// (the positions rtx_texel_points interpolates: as many as before, so nothing is allocated)
+	if ((rc = keepTriPos(s->meshTriPos[mesh], tri_pos_dev, nt, hipMemcpyDeviceToDevice))) return rc;
 	s->meshRecs[mesh] = dm; s->objectRecs.swap(objs);
 	s->meshLeaves[mesh] = leaves; s->srcMeshes[mesh] = sm;
 	chooseBoxPrune(s);
@@ -197,6 +199,7 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 	std::vector<rtx_scene::MeshLeaves> leaves(nMeshes, rtx_scene::MeshLeaves{ nullptr, 0 });
 	std::vector<float> bounds((size_t)nMeshes * 6);
 	std::vector<std::shared_ptr<rtx_scene_mesh_deform>> deform(nMeshes);      // (a kept mesh's topology follows it: include/rtx_deform.h)
+	std::vector<DevArray<float>> triPos(nMeshes);                              // (a kept mesh's follow it in step 3: include/rtx_bake.h)
 	for (uint32_t mi = 0; mi < nMeshes; mi++) {
 		const rtx_mesh_source& src = sources[mi];
 		if (src.keep >= 0) {
@@ -209,6 +212,7 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 		const rtx_mesh& m = *src.mesh;
 		if (!src.build) {
 			if ((rc = uploadMesh(s, m, mi, nLights, owned[mi], fixed[mi], meshes[mi], sms[mi], leaves[mi], &bounds[(size_t)mi * 6]))) return rc;
+			if ((rc = keepTriPos(triPos[mi], m.tri_pos, m.n_tris, hipMemcpyHostToDevice))) return rc;
 			continue;
 		}
 		const rtx_mesh_build& b = *src.build;
@@ -216,6 +220,7 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 		if ((rc = uploadMeshFixed(m, fixed[mi], meshes[mi]))) return rc;
 		if ((rc = deviceMesh(s, m.n_tris, b.tri_pos_dev, b.tri_nrm_dev, b.tri_tb_dev, b.root_lo, b.root_hi, b.ac_penalty, mi, owned[mi], meshes[mi], sms[mi], leaves[mi],
 		                     &bounds[(size_t)mi * 6], nullptr))) return rc;
+		if ((rc = keepTriPos(triPos[mi], b.tri_pos_dev, m.n_tris, hipMemcpyDeviceToDevice))) return rc;
 	}
 
 	// 2. the records over them, and the spheres' and planes' share of the derived state (put back if the upload fails)
@@ -233,9 +238,12 @@ int rtx_scene_set_objects(rtx_scene* s, uint32_t nObjects, const rtx_object* obj
 	// 3. everything takes the old scene's place: kept meshes carry their allocations over, what is left behind is freed (nothing queued
 	// reads it: editBegin)
 	for (uint32_t mi = 0; mi < nMeshes; mi++)
-		if (sources[mi].keep >= 0) { owned[mi].swap(s->meshOwned[sources[mi].keep]); fixed[mi].swap(s->meshFixed[sources[mi].keep]); }
-	s->meshOwned.swap(owned); s->meshFixed.swap(fixed);
-	owned.clear(); fixed.clear();
+		if (sources[mi].keep >= 0) {
+			owned[mi].swap(s->meshOwned[sources[mi].keep]); fixed[mi].swap(s->meshFixed[sources[mi].keep]);
+			triPos[mi] = std::move(s->meshTriPos[sources[mi].keep]);
+		}
+	s->meshOwned.swap(owned); s->meshFixed.swap(fixed); s->meshTriPos.swap(triPos);
+	owned.clear(); fixed.clear(); triPos.clear();
 	s->meshDeform.swap(deform);
 	deform.clear();
 	s->recordsOwned.swap(records);

@@ -69,6 +69,13 @@ struct rtx_scene {
 	// per mesh what rtx_scene_deform_mesh needs (include/rtx_deform.h): its topology in device memory and the scratch of its kernels; empty until
 	// rtx_scene_set_mesh_topology, moved with a kept mesh by rtx_scene_set_objects, not counted in rtx_scene_bytes
 	std::vector<std::shared_ptr<rtx_scene_mesh_deform>> meshDeform;
+	// per mesh its triangles' positions (n_tris x 9, as given to rtx_scene_create, rtx_scene_update_mesh or rtx_scene_set_objects): the walk reads
+	// the leaf references' (v0, e1, e2), from which b and c cannot be had again bit for bit; rtx_texel_points interpolates these (include/rtx_bake.h).
+	// Moved with a kept mesh by rtx_scene_set_objects, not counted in rtx_scene_bytes
+	std::vector<DevArray<float>> meshTriPos;
+	// rtx_texel_points / rtx_dilate_texels: the owner (second copy of tri) of every texel, the large triangles' chunk counts and their scan's scratch.
+	// Lazily sized, they only grow
+	DevArray<uint32_t> texelOwner; DevArray<unsigned long long> texelChunks; DevArray<char> texelScanTemp;
 	float editMs[4] = { 0, 0, 0, 0 };  // the last rtx_scene_update_mesh: build, read-back + flatten + upload, sources + estimate queued, whole call (host wall ms)
 	Params params;                // template of the kernel argument block
 	bool stats = false;

@@ -51,6 +51,15 @@ int uploadMesh(rtx_scene* s, const rtx_mesh& m, uint32_t mi, uint32_t nLights, D
 	return uploadMeshFixed(m, fixed, dm);
 }
 
+// A mesh's triangle positions kept beside it for rtx_texel_points (rtx_scene::meshTriPos): nTris x 9 floats from host or device memory.
+int keepTriPos(DevArray<float>& kept, const float* src, uint32_t nTris, hipMemcpyKind kind)
+{
+	if (!nTris) return RTX_OK;
+	HIPCHK(kept.reserve((size_t)nTris * 9));
+	HIPCHK(hipMemcpy(kept, src, (size_t)nTris * 9 * sizeof(float), kind));
+	return RTX_OK;
+}
+
 // The objects of a description, checked before anything is uploaded or replaced (rtx_scene_create, rtx_scene_set_objects).
 int checkObjects(uint32_t n, const rtx_object* objects, uint32_t nMeshes)
 {
@@ -219,6 +228,7 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 	std::vector<Mesh> meshes(desc->n_meshes);
 	s->meshOwned.resize(desc->n_meshes);
 	s->meshFixed.resize(desc->n_meshes);
+	s->meshTriPos.resize(desc->n_meshes);
 	for (uint32_t mi = 0; mi < desc->n_meshes; mi++) {
 		const rtx_mesh& m = desc->meshes[mi];
 		if ((rc = checkMesh(m))) return rc;
@@ -227,6 +237,7 @@ int rtx_scene_create(const rtx_scene_desc* desc, int device, rtx_scene** out)
 		float bounds[6];
 		// (the mesh's own allocations are what rtx_scene_update_mesh replaces; uv and maps stay for the mesh's life)
 		if ((rc = uploadMesh(s, m, mi, desc->n_lights, s->meshOwned[mi], s->meshFixed[mi], meshes[mi], sm, leaves, bounds))) return rc;
+		if ((rc = keepTriPos(s->meshTriPos[mi], m.tri_pos, m.n_tris, hipMemcpyHostToDevice))) return rc;
 		s->meshBounds.insert(s->meshBounds.end(), bounds, bounds + 6);
 		s->meshLeaves.push_back(leaves);
 		s->srcMeshes.push_back(sm);
