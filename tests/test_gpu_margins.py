@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import util_occlusion as OC
+from tests.util_analytic import lattice_obj      # (util_sources and the tests below take it from here)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -18,19 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def lattice_obj(n=16, bump=0.0):
-    """(n+1)^2 vertices on the lattice k / 8 (exact in fp32), two triangles per cell; bump: z = +-bump in a checker pattern."""
-    s = []
-    for j in range(n + 1):
-        for i in range(n + 1):
-            s.append("v %.6f %.6f %.6f" % (i / 8.0, j / 8.0, bump * (1 if (i + j) % 2 else -1)))
-    for j in range(n):
-        for i in range(n):
-            a = j * (n + 1) + i + 1; b = a + 1; c = a + n + 2; d = a + n + 1
-            s.append("f %d %d %d" % (a, b, c)); s.append("f %d %d %d" % (a, c, d))
-    return "\n".join(s) + "\n"
 
 
 def scene_text(mesh, pos=(0, 0, -3), size=(2, 2, 2), rot=(0, 0, 0), cull=1, cam=(0, 0, 0), w=96, h=72, penalty=1, plane_y=-1.5, material=""):
