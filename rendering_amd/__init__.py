@@ -98,6 +98,17 @@ TEXELS_STORED, TEXELS_RGB8 = 0, 1                                          # RTX
 RTX_BAKE_SYMBOLS = ["rtx_texel_points", "rtx_dilate_texels"]
 
 
+# the extension of include/rtx_project.h: surface points projected into cameras, with visibility (not part of the drop-in boundary)
+RTX_PROJECT_SYMBOLS = ["rtx_project_points"]
+PROJECT_CAMERA_FLOATS = 24                                                 # RTX_PROJECT_CAMERA_FLOATS
+PROJ_FRONT, PROJ_INSIDE, PROJ_FACING, PROJ_OPEN = 1, 2, 4, 8               # RTX_PROJ_*
+
+
+class ProjectBuffers(C.Structure):
+    """rtx_project_buffers (include/rtx_project.h): three device pointers, any of them NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("pixel_dev", "depth_dev", "flags_dev")]
+
+
 class TexelBuffers(C.Structure):
     """rtx_texel_buffers (include/rtx_bake.h): three device pointers, any of them NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("points_dev", "tri_dev", "bary_dev")]
@@ -369,6 +380,8 @@ def load():
     if hasattr(rtx, "rtx_texel_points"):      # (a library without them is reported by exported_symbols)
         rtx.rtx_texel_points.argtypes = [vp, u32, u32, u32, C.POINTER(TexelBuffers), vp]
         rtx.rtx_dilate_texels.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp]
+    if hasattr(rtx, "rtx_project_points"):      # (a library without it is reported by exported_symbols)
+        rtx.rtx_project_points.argtypes = [vp, u32, vp, u32, vp, i32, C.POINTER(ProjectBuffers), vp]
     _rtx, _host = rtx, host
     return rtx, host
 
@@ -376,7 +389,7 @@ def load():
 def exported_symbols():
     """(declared, missing) C-ABI symbols of librtx_hip.so -- used by the CPU-side load test."""
     rtx, _ = load()
-    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS + RTX_TEXTURE_SYMBOLS + RTX_BAKE_SYMBOLS
+    missing = [s for s in RTX_SYMBOLS + RTX_EDIT_SYMBOLS + RTX_QUERY_SYMBOLS + RTX_AOV_SYMBOLS + RTX_AO_SYMBOLS + RTX_SURFACE_SYMBOLS + RTX_LIGHT_SYMBOLS + RTX_DEFORM_SYMBOLS + RTX_VIEWS_SYMBOLS + RTX_VIEWS_AOV_SYMBOLS + RTX_SCATTER_SYMBOLS + RTX_POINTS_SYMBOLS + RTX_RENDER_LIGHT_SYMBOLS + RTX_RADIANCE_SYMBOLS + RTX_TEXTURE_SYMBOLS + RTX_BAKE_SYMBOLS + RTX_PROJECT_SYMBOLS
                if not hasattr(rtx, s)]
     return list(RTX_SYMBOLS), missing
 
@@ -2018,6 +2031,112 @@ class Scene:
         h, w = t["tri"].shape
         image = self.light_points(t["points"], diffuse=True, stream=stream)["diffuse"].reshape(h, w, 3)
         return self.dilate_texels(image, t["tri"], margin, stream=stream), t["tri"]
+
+    # ---- surface points projected into cameras (include/rtx_project.h) -------------------------------
+    def camera_table(self, cameras, width=None, height=None):
+        """The camera records of project_points: a float32 tensor (K, 24) on the scene's device, one record per camera of `cameras` --
+        render_views' sequence of (pos, rot) or (pos, rot, fov), K in 1 .. 256 -- at the size width x height (one size for all; the default
+        is the scene's): {cam_pos, scale, aspect, width, height, 0, cam_matrix}, the fields view_target(pos, rot, fov, width, height) holds
+        (rah_view_target), so the renderer's own camera and not a restatement of it.  The scene is not changed."""
+        import torch
+        return torch.from_numpy(self._camera_records(cameras, width, height)).to(torch.device("cuda", self.device))
+
+    def _camera_records(self, cameras, width=None, height=None):
+        """camera_table's records as a numpy array float32 (K, 24).  Host only."""
+        cameras = list(cameras)
+        if not 1 <= len(cameras) <= 256:
+            raise ValueError("camera_table: 1 .. 256 cameras, got %d" % len(cameras))
+        w, h = self.width if width is None else int(width), self.height if height is None else int(height)
+        if w < 1 or h < 1:
+            raise ValueError("camera_table: width and height must be positive, got %d x %d" % (w, h))
+        table = np.zeros((len(cameras), PROJECT_CAMERA_FLOATS), np.float32)
+        t = ViewTarget()
+        for i, cam in enumerate(cameras):
+            if len(cam) not in (2, 3):
+                raise ValueError("camera_table: camera %d must be (pos, rot) or (pos, rot, fov)" % i)
+            self._fill_view_target(t, cam[0], cam[1], cam[2] if len(cam) == 3 else None, w, h)
+            table[i, 0:3] = t.cam_pos
+            table[i, 3:7] = (t.scale, t.aspect, t.width, t.height)
+            table[i, 8:24] = t.cam_matrix
+        return table
+
+    def project_points(self, points, cameras, width=None, height=None, pixel=True, depth=False, flags=True, visibility=True, stream=None):
+        """rtx_project_points: which pixel of each camera a surface point falls into, and whether that camera sees it, on the device
+        (include/rtx_project.h).  points: as for light_points, (n, 6) = {P xyz, N xyz}.  cameras: render_views' sequence of (pos, rot[, fov])
+        at the size width x height (camera_table), or a table tensor float32 (K, 24) on the scene's device, which is used in place (width
+        and height must then be None); K in 1 .. 256.  Returns a dict of the channels asked for, new tensors on the points' device,
+        camera-major: "pixel" float32 (K, n, 2) = (px, py), an integer meaning the centre of that pixel of pass 1 -- the nearest pixel is
+        floor(p + 0.5); "depth" float32 (K, n), the distance from the camera's position; "flags" uint8 (K, n) of PROJ_FRONT | PROJ_INSIDE |
+        PROJ_FACING | PROJ_OPEN.  PROJ_OPEN -- the shadow ray from P + N * bias to the camera meets no opaque object, occluded()'s rule
+        -- is only computed with `visibility`, and only for the pairs that are in front of the camera and inside its frame.
+        Asynchronous on `stream`, which is handled as in trace_rays (a table tensor is recorded on it like the points)."""
+        import torch
+        if not (pixel or depth or flags):
+            raise ValueError("project_points: nothing to compute (every channel is off)")
+        n = _check_rays("project_points", points, self.device, "points")
+        if isinstance(cameras, torch.Tensor):
+            if width is not None or height is not None:
+                raise ValueError("project_points: a camera table has its sizes in it (width and height must be None)")
+            _check_tensor("project_points", "cameras", cameras, torch.float32, ("K", PROJECT_CAMERA_FLOATS), self.device)
+            table = cameras
+        else:
+            # (the upload is queued where the call will run)
+            with torch.cuda.stream(stream if isinstance(stream, torch.cuda.Stream) else None):
+                table = self.camera_table(cameras, width, height)
+            if stream is not None and not isinstance(stream, torch.cuda.Stream):
+                torch.cuda.current_stream(points.device).synchronize()      # (a raw handle: torch cannot order the upload before it)
+        k = table.shape[0]
+        if not 1 <= k <= 256:
+            raise ValueError("project_points: 1 .. 256 cameras, got %d" % k)
+        alloc_on, st = _query_stream(stream, points.device, (points, table))
+        with torch.cuda.stream(alloc_on):
+            out = {}
+            if pixel:
+                out["pixel"] = torch.empty((k, n, 2), dtype=torch.float32, device=points.device)
+            if depth:
+                out["depth"] = torch.empty((k, n), dtype=torch.float32, device=points.device)
+            if flags:
+                out["flags"] = torch.empty((k, n), dtype=torch.uint8, device=points.device)
+        if n:
+            buf = ProjectBuffers(*[out[c].data_ptr() if c in out else None for c in ("pixel", "depth", "flags")])
+            _check(self.rtx.rtx_project_points(self.gpu(), n, _ptr(points), k, _ptr(table), 1 if visibility else 0, C.byref(buf), st),
+                   "rtx_project_points")
+        return out
+
+    def bake_view(self, index, camera, image, width=None, height=None, margin=2, stream=None):
+        """The projective bake of one view onto mesh `index`: texel_points(index, width, height), projected with project_points into
+        `camera` = (pos, rot[, fov]) at the size of `image` -- float32 (H, W, 3) on the scene's device, in the row order of render_views'
+        framebuffers.  A texel whose flags are PROJ_INSIDE | PROJ_FACING | PROJ_OPEN (so PROJ_FRONT too) takes
+        image[floor(py + 0.5), floor(px + 0.5)], every other covered texel is 0; then dilate_texels over `margin` passes.  Returns
+        (texels, seen): float32 (height, width, 3), which set_texture(index, "diffuse", texels) takes as it is, and bool (height, width),
+        the texels that took a pixel.  Several cameras are merged by the caller: torch.where(seen_b[..., None] & ~seen_a[..., None], b, a).
+        `stream` is handled as in trace_rays; with a raw hipStream_t handle the host waits for the device around the gather, which is torch's."""
+        import torch
+        _check_tensor("bake_view", "image", image, torch.float32, ("H", "W", 3), self.device)
+        ih, iw = int(image.shape[0]), int(image.shape[1])
+        if ih < 1 or iw < 1:
+            raise ValueError("bake_view: image is empty")
+        if len(camera) not in (2, 3):
+            raise ValueError("bake_view: camera must be (pos, rot) or (pos, rot, fov)")
+        t = self.texel_points(index, width, height, points=True, tri=True, stream=stream)
+        h, w = t["tri"].shape
+        p = self.project_points(t["points"], [camera], iw, ih, pixel=True, flags=True, visibility=True, stream=stream)
+        alloc_on, _ = _query_stream(stream, image.device, (image,))
+        # (a raw hipStream_t handle: torch cannot order its own work between the calls queued on it, so the host waits on either side)
+        raw = stream is not None and alloc_on is None
+        if raw:
+            torch.cuda.synchronize(image.device)
+        with torch.cuda.stream(alloc_on):
+            want = PROJ_FRONT | PROJ_INSIDE | PROJ_FACING | PROJ_OPEN
+            seen = ((p["flags"][0] & want) == want).reshape(h, w) & (t["tri"] >= 0)
+            # (INSIDE: the nearest pixel is inside the image; the clamp only keeps the texels that are not seen from indexing outside it)
+            near = torch.floor(p["pixel"][0] + 0.5).nan_to_num(0.0, 0.0, 0.0)
+            x = near[:, 0].clamp(0, iw - 1).long().reshape(h, w)
+            y = near[:, 1].clamp(0, ih - 1).long().reshape(h, w)
+            texels = torch.where(seen[..., None], image[y, x], torch.zeros((), dtype=torch.float32, device=image.device)).contiguous()
+        if raw:
+            torch.cuda.current_stream(image.device).synchronize()
+        return self.dilate_texels(texels, t["tri"], margin, stream=stream), seen
 
     def deform_times(self):
         """Host wall ms of the stages of the last set_vertices: {kernels (placement and assembly on the device with their read-backs),

@@ -25,6 +25,7 @@
 #include "../../include/rtx_light.h"
 #include "../../include/rtx_scatter.h"
 #include "../../include/rtx_points.h"
+#include "../../include/rtx_project.h"
 #include "../../include/rtx_render_light.h"
 #include "../../include/rtx_radiance.h"
 #include "../../include/rtx_views.h"
@@ -47,6 +48,7 @@ using rtxown::DevArray; using rtxown::DevBag; using rtxown::Event; using rtxown:
 #include "rtx_light.hip"
 #include "rtx_scatter.hip"
 #include "rtx_points.hip"
+#include "rtx_project.hip"
 #include "rtx_render_light.hip"
 #include "rtx_radiance.hip"
 #include "rtx_views_aov.hip"

@@ -1,5 +1,5 @@
 // The queries of a loaded scene (include/rtx_query.h, rtx_surface.h, rtx_light.h, rtx_scatter.h, rtx_points.h, rtx_aov.h, rtx_ao.h,
-// rtx_render_light.h, rtx_radiance.h): which kernel a call launches, the host steps the calls share, and the entry points.  Included by rtx_api.hip after
+// rtx_render_light.h, rtx_radiance.h, rtx_project.h): which kernel a call launches, the host steps the calls share, and the entry points.  Included by rtx_api.hip after
 // its launch bookkeeping (ensureWork, renderOn, plainTileGrid), as rtx_edit.hip is.
 #include "rtx_scene.h"      // (Variant, dispatchVariant, fail / HIPCHK)
 
@@ -31,6 +31,7 @@ RTX_SELECTOR(rayLightKernel, (const Variant& v), false, (const Params, const uin
 RTX_SELECTOR(rayScatterKernel, (const Variant& v), false, (const Params, const uint32_t*, const rtx_scatter_buffers), rtxRayScatterKernel<M, B, C>)
 RTX_SELECTOR(pointLightKernel, (const Variant& v), false, (const Params, const uint32_t*, const float*, const rtx_light_buffers), rtxPointLightKernel<M, B, C>)
 RTX_SELECTOR(pointAoKernel, (const Variant& v), false, (const Params, const uint32_t*, const AoArgs), rtxPointAoKernel<M, B, C>)
+RTX_SELECTOR(pointProjectKernel, (const Variant& v), false, (const Params, const uint32_t*, const ProjectArgs), rtxPointProjectKernel<M, B, C>)
 RTX_SELECTOR(aoKernel, (const Variant& v), false, (const Params, const AoArgs), rtxAoKernel<M, B, C>)
 RTX_SELECTOR(lightFrameKernel, (const Variant& v), false, (const Params, const rtx_frame_light_buffers), rtxLightFrameKernel<M, B, C>)
 // (PLAIN exists for mesh scenes only: M && T)
@@ -317,6 +318,23 @@ int rtx_ao_points(rtx_scene* s, uint32_t n, const float* points_dev, const rtx_a
 	if (!startRays(s, n, points_dev, stream, c, rc)) return rc;
 	const AoArgs args = { par->dirs_dev, par->n_dirs, par->radius, ao, counts };
 	return launchRays(s, pointAoKernel(variantOf(s)), c, args);
+}
+
+// include/rtx_project.h: the point queries' steps; the cameras are a table in device memory, used as stored
+int rtx_project_points(rtx_scene* s, uint32_t n, const float* points_dev, uint32_t n_cams, const float* cameras_dev, int with_visibility,
+                       const rtx_project_buffers* out, void* stream)
+{
+	RoctxRange range("Project points (rtx_project_points)");
+	if (!s || !out) return fail(RTX_ERR_ARG, "scene/out is NULL");
+	if (!out->pixel_dev && !out->depth_dev && !out->flags_dev) return fail(RTX_ERR_ARG, "rtx_project_points: no output (all three buffers are NULL)");
+	if (!cameras_dev) return fail(RTX_ERR_ARG, "rtx_project_points: cameras_dev is NULL");
+	if (n_cams < 1 || n_cams > 256) return fail(RTX_ERR_ARG, "rtx_project_points: n_cams must be 1 .. 256");
+	if (n != 0 && !points_dev) return fail(RTX_ERR_ARG, "rtx_project_points: points is NULL");
+	RayCall c;
+	int rc;
+	if (!startRays(s, n, points_dev, stream, c, rc)) return rc;
+	const ProjectArgs args = { cameras_dev, n_cams, (with_visibility != 0 && out->flags_dev) ? 1u : 0u, out->pixel_dev, out->depth_dev, out->flags_dev };
+	return launchRays(s, pointProjectKernel(variantOf(s)), c, args);
 }
 
 // include/rtx_radiance.h: the point queries' steps, and rtx_trace_rays' grid for the kernel that shades
